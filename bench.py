@@ -6,14 +6,19 @@ composite) over one batch of synthetic rays already resident in HBM.  Workload =
 TextureEmbeddingPiGAN256SEMANTICDISENTANGLE_DIM_96 (H=256 FiLM-SIREN + 32x96^3 grid, 22 channels), 128x128 rays,
 24+24 hierarchical samples, batch 1 per GPU, procedural (random-init-range) weights, synthetic latents.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line; `--dump-outputs DIR` then writes the last timed step's
+outputs (rgb.npy [B,R,C'], depth.npy [B,R], float32; rank 0; a seeded sample of rays beyond 64 MB, see dump_outputs) for
+output-for-output comparison of two builds (the inputs are seeded).
+Every other leg described below (roofline, CPU baseline, other precisions and shapes, generator steps) runs only with `--full`.
 
 N > 1 without a launcher environment (WORLD_SIZE unset) re-executes itself under `python -m torch.distributed.run
 --nproc-per-node N --master-addr 127.0.0.1`; launched BY torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE from
 the environment.  One rank per GPU, every rank renders its own images (weak scaling, no data-path collective); RCCL carries
 the timing barrier, the max-over-ranks reduce and an all-reduce of ones (`n_ranks_seen`).
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (the SIREN kernel, MFMA-bound): algorithmic
+Prints ONE JSON line on rank 0.  With --full: `roofline` is for the dominant kernel (the SIREN kernel, MFMA-bound): algorithmic
 FLOPs per launch (1,603,584 FLOP/point x points) / its hipEvent-timed average duration.  Extra objects on the
 same line (DESIGN.md §5 has the table): `cpu_baseline` (numpy oracle = port of the reference CPU path, 1 warm-up + 3 timed runs per
 shape, N=1); `f32` (the same step at exact-fp32 precision), `f16x3c2` / `f16x2` (the opt-in reduced-precision forward modes, each with
@@ -53,7 +58,7 @@ def _sig(v, n=6):
     return float(f"{v:.{n}g}")
 
 
-def compact_line(out):
+def compact_line(out, detail=True):
     """The ONE line the driver parses, from the full result object `out` (which goes to bench_detail.json unchanged): the contract's
     keys, `roofline` and `cpu_baseline` as flat objects of scalars, and one scalar (or a small flat object) per extra leg.  No `what`
     strings, no per-kernel tables, no tier legs.  Always < COMPACT_LINE_LIMIT bytes (asserted here and in tests/test_host_cpu.py)."""
@@ -71,13 +76,15 @@ def compact_line(out):
     line = {k: _sig(out[k]) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                       "vs_baseline", "dtype", "data") if k in out}
     line["config"] = {k: v for k, v in out.get("config", {}).items() if not isinstance(v, (dict, list))}
-    line["roofline"] = pick(out.get("roofline", {}), ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms", "points_per_launch",
-                                                      "frac_of_f16x3_ceiling", "frac_executed", "clock_ghz_effective", "frac_at_spec_clock"))
-    line["roofline"].setdefault("traffic", None)
+    if "roofline" in out:                   # --full legs: absent from a plain run's line
+        line["roofline"] = pick(out["roofline"], ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms", "points_per_launch",
+                                                  "frac_of_f16x3_ceiling", "frac_executed", "clock_ghz_effective", "frac_at_spec_clock"))
+        line["roofline"].setdefault("traffic", None)
     if "cpu_baseline" in out:
         line["cpu_baseline"] = pick(out["cpu_baseline"], ("value", "unit", "cores", "threads", "kind", "sample"))
     line["n_ranks_seen"] = out.get("n_ranks_seen")
-    line["launches_per_step"] = out.get("launches_per_step")
+    if "launches_per_step" in out:
+        line["launches_per_step"] = out["launches_per_step"]
     for name, keys in (("f32", ("value", "ms_per_step")), ("sweep64", ("value", "ms_per_step", "roofline_frac")),
                        ("gstep", ("ms", "rays_per_s", "peak_GB")), ("gstep_sparse", ("ms", "peak_GB", "kept_frac")),
                        ("gstep_b6", ("ms", "ms_per_image", "peak_GB")), ("gstep_sparse_b6", ("ms", "ms_per_image", "peak_GB", "kept_frac")),
@@ -93,7 +100,8 @@ def compact_line(out):
     if isinstance(g, dict) and isinstance(g.get("roofline"), dict):          # the step's roofs both ways (bytes / 8 TB/s and FLOP / 2,500 TFLOP/s)
         line["gstep"].update(pick(g["roofline"], ("frac", "frac_flop")))
         line["gstep"]["kernels_ms"] = {k["name"]: _sig(k["ms"], 4) for k in g["roofline"].get("per_kernel", [])}
-    line["detail"] = DETAIL_FILE
+    if detail:                              # --full: every leg in full is in the detail file
+        line["detail"] = DETAIL_FILE
     text = json.dumps(line, separators=(", ", ": "))
     assert len(text.encode()) < COMPACT_LINE_LIMIT and "\n" not in text, len(text)
     return text
@@ -111,6 +119,29 @@ def write_detail(out):
                 f.write(text + "\n")
         except OSError as e:
             print(f"bench.py: could not write {pth}: {e}", file=sys.stderr)
+
+
+DUMP_LIMIT_BYTES = 60 * 2 ** 20     # --dump-outputs: array bytes in all (with the .npy headers below 64 MB either way it is counted)
+
+
+def dump_outputs(path, outputs, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: the arrays the timed path handed its caller in its last step, as float32 <path>/<name>.npy.  Every array is
+    per ray ([B, R, ...]).  When they would take more than `limit` bytes, a fixed seeded sample of rays is written instead: each array as
+    [K, ...] and ray_index.npy (float64) = the flat B * R index of each sampled ray, ascending."""
+    os.makedirs(path, exist_ok=True)
+    flat = {name: t.detach().reshape(t.shape[0] * t.shape[1], *t.shape[2:]) for name, t in outputs.items()}
+    rays = next(iter(flat.values())).shape[0]
+    assert all(t.shape[0] == rays for t in flat.values())
+    per_ray = sum(4 * t[0].numel() for t in flat.values())
+    if rays * per_ray > limit:
+        k = limit // (per_ray + 8)
+        idx = np.sort(np.random.default_rng(seed).choice(rays, size=k, replace=False))
+        sel = torch.from_numpy(idx).to(next(iter(flat.values())).device)
+        flat = {name: t.index_select(0, sel) for name, t in flat.items()}
+        outputs = dict(flat, ray_index=idx.astype(np.float64))
+    for name, t in outputs.items():
+        a = t if isinstance(t, np.ndarray) else t.detach().float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def pmc_traffic():
@@ -649,6 +680,10 @@ def main(argv=None):
     ap.add_argument("--img-size", type=int, default=128)
     ap.add_argument("--num-steps", type=int, default=24)
     ap.add_argument("--batch", type=int, default=1, help="images per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (roofline, CPU baseline, f32 / f16x3c2, sweep64, generator steps, DDP legs); "
+                         "the --no-* / opt-in leg switches below act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--quick-cpu-baseline", action="store_true", help="headline shape only, 1 warm-up + 1 timed run")
     ap.add_argument("--no-gstep", action="store_true", help="skip the generator-step (forward + backward) leg")
@@ -667,6 +702,8 @@ def main(argv=None):
     ap.add_argument("--one-device", action="store_true",
                     help="every rank on cuda:0 (with --dist-backend gloo: RCCL refuses two ranks on one device): the N > 1 code path on a one-GPU box")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the driver's N=1 command with N changed: become the launcher (one rank per GPU over RCCL)
@@ -714,7 +751,7 @@ def main(argv=None):
 
     def timed_render(nat, B, S, N, steps, warmup, seed):
         """W untimed + K timed render steps bracketed by barrier + synchronize; returns (max-over-ranks seconds, own seconds,
-        the resident inputs)."""
+        the resident inputs, the last timed step's (rgb, depth))."""
         R = S * S
         # every rank renders its own images (shard by image, no data-path collective): different latents / poses per rank
         film = proc.film_params(spec, B, seed=seed + rank)
@@ -728,10 +765,10 @@ def main(argv=None):
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            nat.render(o, d, z, u, None, None, *tf, opts, hierarchical=True)
+            last = nat.render(o, d, z, u, None, None, *tf, opts, hierarchical=True)
         barrier()
         own = time.perf_counter() - t0
-        return fdist.max_over_ranks(own, device=dev), own, (o, d, z, tf)
+        return fdist.max_over_ranks(own, device=dev), own, (o, d, z, tf), last[:2]
 
     def gather_floats(v):
         if not use_dist:
@@ -775,8 +812,28 @@ def main(argv=None):
     nat = native.NativeModel(sd, spec, dev, args.precision)
     B, S, N = args.batch, args.img_size, args.num_steps
     R = S * S
-    dt, own, inputs = timed_render(nat, B, S, N, args.steps, args.warmup, 1000)
+    dt, own, inputs, (rgb_last, depth_last) = timed_render(nat, B, S, N, args.steps, args.warmup, 1000)
     value = world * B * R * args.steps / dt
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"rgb": rgb_last, "depth": depth_last})
+    dtype = "f32" if args.precision == "f32" else "f16x3 (error-compensated fp16 MFMA, fp32 accumulate; fp32-class accuracy)"
+    headline = {
+        "metric": f"rays/s/GPU forward render ({S}x{S}, {N}+{N} samples, H=256 FiLM-SIREN + 32x96^3 grid)",
+        "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": dtype, "data": "synthetic",
+        "config": {"workload": f"configs[1]: CelebA_double_semantic_texture_embedding_256_dim_96 generator, {S}x{S}, "
+                               f"{N}+{N} hierarchical samples, batch {B}/GPU, forward-only render, procedural weights",
+                   "img_size": S, "num_steps": N, "batch_per_gpu": B, "sharding": "by image, no collective"},
+    }
+    if not args.full:
+        # a plain run: the headline line only (every other leg, the roofline and the detail file included, is --full)
+        if rank == 0:
+            print(compact_line({**headline, "n_ranks_seen": n_ranks_seen}, detail=False), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     o_, d_, z_, tf_ = inputs
     with native.phase_timing() as one:          # launch groups of one render (every kernel launch of the library is one)
         nat.render(o_, d_, z_, torch.rand((B * R, N), device=dev), None, None, *tf_, opts, hierarchical=True)
@@ -788,7 +845,7 @@ def main(argv=None):
     if not args.no_sweep64:
         # north_star: "rays/s on synthetic 64x64x24-sample batches at 1/2/4/8 GPUs ... as fraction of roofline"
         sB, sS, sN = 4, 64, 24
-        sdt, _, sin = timed_render(nat, sB, sS, sN, args.steps, args.warmup, 2000)
+        sdt, _, sin, _ = timed_render(nat, sB, sS, sN, args.steps, args.warmup, 2000)
         sroof = roofline_of(nat, sin, sB * sS * sS * sN, args.precision, max(5, args.steps // 2))
         sweep = {"workload": f"{sB} images/GPU x {sS}x{sS} rays x {sN}+{sN} samples", "value": world * sB * sS * sS * args.steps / sdt,
                  "unit": "rays/s", "ms_per_step": sdt / args.steps * 1e3, "roofline_frac": sroof["frac"],
@@ -816,16 +873,9 @@ def main(argv=None):
         torch.cuda.empty_cache()
 
     if rank == 0:
-        dtype = "f32" if args.precision == "f32" else "f16x3 (error-compensated fp16 MFMA, fp32 accumulate; fp32-class accuracy)"
         tr = pmc_traffic() if (args.precision == "f16x3" and (B, S, N) == (1, 128, 24)) else None
         out = {
-            "metric": f"rays/s/GPU forward render ({S}x{S}, {N}+{N} samples, H=256 FiLM-SIREN + 32x96^3 grid)",
-            "value": value, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": dtype, "data": "synthetic",
-            "config": {"workload": f"configs[1]: CelebA_double_semantic_texture_embedding_256_dim_96 generator, {S}x{S}, "
-                                   f"{N}+{N} hierarchical samples, batch {B}/GPU, forward-only render, procedural weights",
-                       "img_size": S, "num_steps": N, "batch_per_gpu": B, "sharding": "by image, no collective"},
+            **headline,
             "roofline": {**roof, "traffic": (tr["fetch_x2_bytes"] + tr["write_bytes"]) if tr else None, "traffic_detail": tr,
                          "frac_per_rank": roof_frac_ranks},
             "rays_per_s_per_gpu": value / world, "rays_per_s_per_rank": per_rank, "n_ranks_seen": n_ranks_seen,
@@ -848,7 +898,7 @@ def main(argv=None):
         if world == 1 and not args.no_f32 and args.precision != "f32":
             try:
                 nat32 = native.NativeModel(sd, spec, dev, "f32")
-                fdt, _, fin = timed_render(nat32, B, S, N, args.steps, args.warmup, 1000)
+                fdt, _, fin, _ = timed_render(nat32, B, S, N, args.steps, args.warmup, 1000)
                 out["f32"] = {"value": B * R * args.steps / fdt, "unit": "rays/s", "ms_per_step": fdt / args.steps * 1e3,
                               "dtype": "f32 (exact fp32 MFMA, v_mfma_f32_32x32x2_f32)",
                               "roofline": roofline_of(nat32, fin, B * R * N, "f32", max(5, args.steps // 2))}
@@ -862,7 +912,7 @@ def main(argv=None):
                               ("f16x3c2", "three fp16 MFMAs per product through the geometry trunk and the label / sigma head (sigma and labels bit-identical to the headline's), two in the colour layers and the rgb head"),):
                 try:
                     natx = native.NativeModel(sd, spec, dev, key)
-                    xdt, _, xin = timed_render(natx, B, S, N, args.steps, args.warmup, 1000)
+                    xdt, _, xin, _ = timed_render(natx, B, S, N, args.steps, args.warmup, 1000)
                     xroof = roofline_of(natx, xin, B * R * N, "f16x3", max(5, args.steps // 2))
                     xroof["mfma"] = what
                     xroof.pop("frac_of_f16x3_ceiling", None)
@@ -884,7 +934,7 @@ def main(argv=None):
             # which takes the faster four-launch route
             try:
                 with native.render_fusion("force"):
-                    odt, _, _ = timed_render(nat, B, S, N, args.steps, args.warmup, 1000)
+                    odt, _, _, _ = timed_render(nat, B, S, N, args.steps, args.warmup, 1000)
                     with native.phase_timing() as one1:
                         rgb1 = nat.render(o_, d_, z_, torch.ones((B * R, N), device=dev) * 0.5, None, None, *tf_, opts, hierarchical=True)[0]
                 rgb4 = nat.render(o_, d_, z_, torch.ones((B * R, N), device=dev) * 0.5, None, None, *tf_, opts, hierarchical=True)[0]

@@ -337,41 +337,27 @@ def test_fid_image_dump_shards_by_image_id(tmp_path, world):
     assert len(paths) == 4 and np.asarray(Image.open(paths[0])).shape == (6, 6, 3)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference only exists in the build container")
 @pytest.mark.parametrize("world", [1, 2])
 def test_fid_image_dump_equals_the_references_own_loops(tmp_path, world):
     """fid_evaluation.output_images / output_images_double themselves (AST-extracted from the reference's file -- importing it needs
-    torchvision and pytorch_fid --, executed with a recording save_image) on the same stand-in generator and seeds: same file names, same
-    tensors, same calls."""
-    import ast
-    import copy
-    src = open("/root/reference/fid_evaluation.py").read()
-    fns = [n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name in ("output_images", "output_images_double")]
-    assert len(fns) == 2
-    rec = []
-
-    class _Bar:
-        def __init__(self, *a, **k): pass
-        def update(self, n): pass
-        def close(self): pass
-
-    def save_image(img, path, normalize=False, range=None):
-        assert normalize is True and tuple(range) == (-1, 1)
-        rec.append((os.path.basename(path), img.clone()))
-    ns = dict(copy=copy, os=os, torch=torch, tqdm=_Bar, save_image=save_image)
-    exec(compile(ast.Module(body=fns, type_ignores=[]), "fid_evaluation.py", "exec"), ns)
+    torchvision and pytorch_fid --, executed with a recording save_image; recorded by tools/make_golden.py in
+    tests/golden/fid_dump_loops.npz) on the same stand-in generator and seeds: same file names, same tensors, same calls."""
+    import json
+    from conftest import load_golden
+    g = load_golden("fid_dump_loops")
     for name, stand_in in (("output_images_double", _StandInDouble), ("output_images", _StandInSingle)):
         for rank in range(world):
-            gen_ref, gen_own = stand_in(), stand_in()
-            rec.clear()
-            torch.manual_seed(7 + rank)
-            ns[name](_DDPLike(gen_ref), _DUMP_MD, rank, world, str(tmp_path), num_imgs=9)
-            theirs = list(rec)
+            key = f"{name}_w{world}_r{rank}_"
+            theirs = list(zip(g[key + "names"].tolist(), (torch.from_numpy(a) for a in g[key + "images"])))
+            gen_own = stand_in()
             ours = _run_dump(getattr(callers, name), gen_own, rank, world, 9, tmp_path, seed=7)
             assert [n for n, _ in ours] == [n for n, _ in theirs] and all(torch.equal(a[1], b[1]) for a, b in zip(ours, theirs))
-            assert len(gen_ref.calls) == len(gen_own.calls)
-            for a, b in zip(gen_ref.calls, gen_own.calls):
-                assert all(torch.equal(x, y) for x, y in zip(a[:-1], b[:-1])) and a[-1] == b[-1]
+            metadata = json.loads(str(g[key + "calls_metadata"]))
+            assert len(metadata) == len(gen_own.calls)
+            for c, (md, b) in enumerate(zip(metadata, gen_own.calls)):
+                a = [torch.from_numpy(g[f"{key}call{c}_{j}"]) for j in range(len(b) - 1)]
+                assert len([k for k in g if k.startswith(f"{key}call{c}_")]) == len(a)
+                assert all(torch.equal(x, y) for x, y in zip(a, b[:-1])) and md == b[-1]
 
 
 def test_dump_images_front_end_arguments():

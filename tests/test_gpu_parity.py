@@ -3045,7 +3045,7 @@ def test_bench_under_torch_distributed_run_initialises_rccl():
     from conftest import ROOT
     sys.path.insert(0, ROOT)
     import bench
-    cmd = bench.self_launch_command(1, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-f32", "--no-gstep",
+    cmd = bench.self_launch_command(1, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-f32", "--no-gstep",
                                         "--no-gstep-b6", "--no-sweep64"], script=os.path.join(ROOT, "bench.py"))
     env = dict(os.environ, FENERF_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
@@ -3119,7 +3119,7 @@ def test_bench_gpus_2_on_one_device_over_gloo_prints_a_parseable_line():
     from conftest import ROOT
     import bench
     d = _torchrun_two_ranks([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--one-device", "--dist-backend", "gloo",
-                             "--no-cpu-baseline", "--no-f32", "--no-gstep", "--no-gstep-b6", "--no-sweep64"])
+                             "--full", "--no-cpu-baseline", "--no-f32", "--no-gstep", "--no-gstep-b6", "--no-sweep64"])
     assert d["n_gpus"] == 2 and d["n_ranks_seen"] == 2 and d["scaling"] == "weak" and d["value"] > 1e6
     assert len(json.dumps(d)) < bench.COMPACT_LINE_LIMIT and d["roofline"]["frac"] > 0
     leg = d["gstep_ddp"]

@@ -698,6 +698,27 @@ def test_bench_last_stdout_line_is_compact_and_parses_from_a_tail():
     assert "cpu_baseline" not in l3 and l3["roofline"]["frac"] == pytest.approx(full["roofline"]["frac"], rel=1e-5)
 
 
+def test_bench_dump_outputs_whole_or_a_seeded_sample_under_the_limit(tmp_path):
+    """bench.py --dump-outputs: the last step's per-ray arrays as float32 .npy, whole while they fit; beyond the limit the same seeded
+    sample of rays from every array (ray_index.npy names them), the same from run to run, within the limit."""
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    rgb, depth = torch.rand(2, 1000, 22, generator=g), torch.rand(2, 1000, generator=g)
+    bench.dump_outputs(str(tmp_path / "whole"), {"rgb": rgb, "depth": depth})
+    assert sorted(os.listdir(tmp_path / "whole")) == ["depth.npy", "rgb.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "rgb.npy"), rgb.numpy()) and np.load(tmp_path / "whole" / "depth.npy").dtype == np.float32
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"rgb": rgb, "depth": depth}, limit=20000)
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("rgb", "depth", "ray_index")}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in ("rgb", "depth", "ray_index")}
+    assert all(np.array_equal(a[n], b[n]) for n in a) and a["ray_index"].dtype == np.float64
+    ix = a["ray_index"].astype(np.int64)
+    assert len(ix) > 100 and np.all(np.diff(ix) > 0) and sum(v.nbytes for v in a.values()) <= 20000
+    assert np.array_equal(a["rgb"], rgb.reshape(-1, 22).numpy()[ix]) and np.array_equal(a["depth"], depth.reshape(-1).numpy()[ix])
+    assert bench.DUMP_LIMIT_BYTES + 3 * 4096 <= 64 * 10 ** 6
+
+
 def test_bench_cpu_baseline_is_the_torch_oracle_on_all_cores(monkeypatch):
     """bench.cpu_baseline times oracle/fenerf_oracle_torch.py (every pass on torch's thread pool) under set_num_threads(all cores),
     restores the caller's thread count and honours its time budget; tiny model, 8x8 .. 128x128 replaced by a stub clock-free check of the

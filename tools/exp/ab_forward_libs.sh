@@ -5,7 +5,7 @@
 for v in "" ${VARIANTS:-} ""; do
   if [ -z "$v" ]; then lib=$PWD/fenerf_amd/libfenerf_hip.so; else lib=$PWD/fenerf_amd/libexp_$v.so; fi
   echo -n "${v:-shipped}: "
-  FENERF_LIB=$lib python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-gstep --no-gstep-ddp --no-gstep-b6 --no-f32 --no-sweep64 > /dev/null 2>&1
+  FENERF_LIB=$lib python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-gstep --no-gstep-ddp --no-gstep-b6 --no-f32 --no-sweep64 > /dev/null 2>&1
   python -c "
 import json
 j=json.load(open('bench_detail.json')); r=j['roofline']

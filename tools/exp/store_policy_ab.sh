@@ -5,7 +5,7 @@ for v in "" stpol1 stpol2 stpol3 stpol4 ""; do
   if [ -z "$v" ]; then lib=$PWD/fenerf_amd/libfenerf_hip.so; else lib=$PWD/fenerf_amd/libexp_$v.so; fi
   [ -f $lib ] || continue
   echo -n "${v:-shipped}: "
-  FENERF_LIB=$lib timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-f32 --no-sweep64 --no-gstep-ddp --no-gstep-b6 > /dev/null 2>&1
+  FENERF_LIB=$lib timeout 300 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-f32 --no-sweep64 --no-gstep-ddp --no-gstep-b6 > /dev/null 2>&1
   python - <<PY
 import json
 g = json.load(open("bench_detail.json"))["gstep"]

@@ -633,6 +633,52 @@ def run_inversion_helpers(name="inversion_helpers"):
     print(f"{name}: mask2labels + mIOU + set_trajectory of the inversion script")
 
 
+def run_fid_dump_loops(name="fid_dump_loops"):
+    """output_images / output_images_double of fid_evaluation.py:96-150 (AST-extracted -- importing the file needs torchvision and
+    pytorch_fid --, executed with a recording save_image) on the stand-in generators of tests/test_cli_cpu.py, seeds 7 + rank, 9 images,
+    world 1 and 2: per loop, world and rank the file names, the saved images and the generator's calls in order."""
+    import ast
+    import copy
+    import json
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_cli_cpu as T
+    fn = "fid_evaluation.py"
+    tree = ast.parse(open(os.path.join(ref_import.REFERENCE_ROOT, fn)).read())
+    fns = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name in ("output_images", "output_images_double")]
+    assert len(fns) == 2
+    rec = []
+
+    class _Bar:
+        def __init__(self, *a, **k): pass
+        def update(self, n): pass
+        def close(self): pass
+
+    def save_image(img, path, normalize=False, range=None):
+        assert normalize is True and tuple(range) == (-1, 1)
+        rec.append((os.path.basename(path), img.clone()))
+    ns = dict(copy=copy, os=os, torch=torch, tqdm=_Bar, save_image=save_image)
+    exec(compile(ast.Module(body=fns, type_ignores=[]), fn, "exec"), ns)
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for world in (1, 2):
+            for loop, stand_in in (("output_images_double", T._StandInDouble), ("output_images", T._StandInSingle)):
+                for rank in range(world):
+                    gen = stand_in()
+                    rec.clear()
+                    torch.manual_seed(7 + rank)
+                    ns[loop](T._DDPLike(gen), T._DUMP_MD, rank, world, tmp, num_imgs=9)
+                    key = f"{loop}_w{world}_r{rank}_"
+                    out[key + "names"] = np.array([n for n, _ in rec])
+                    out[key + "images"] = np.stack([np_(img) for _, img in rec])
+                    for c, call in enumerate(gen.calls):
+                        for j, t in enumerate(call[:-1]):
+                            out[key + f"call{c}_{j}"] = np_(t)
+                    out[key + "calls_metadata"] = np.array(json.dumps([call[-1] for call in gen.calls]))
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    print(f"{name}: the FID image dump loops on stand-in generators")
+
+
 def run_multiview_case(refs, name="tiny_multiview"):
     """generate_img of render_multiview_images_double_semantic.py:24-29 (AST-extracted, executed as is) over the script's
     five yaw angles (:68-83) on the tiny reference generator, with the options bag the script builds (:43-54) from a small
@@ -916,8 +962,8 @@ def run_curriculums(refs, name="curriculums"):
 
 
 def main(out_dir=None):
-    """Regenerates every fixture into `out_dir` (default tests/golden).  tests/test_golden_recipe.py calls this into a scratch
-    directory when /root/reference is present and compares the result with the committed files bit for bit."""
+    """Regenerates every fixture into `out_dir` (default tests/golden).  Run into a scratch directory and compared with the committed
+    files, it checks the recipe against the reference."""
     global OUT
     if out_dir is not None:
         OUT = out_dir
@@ -942,6 +988,7 @@ def main(out_dir=None):
     run_mapping_and_full(refs, "tiny_texture_z_full")
     run_caller_helpers()
     run_inversion_helpers()
+    run_fid_dump_loops()
     run_multiview_case(refs)
     run_spatial_grid_case(refs)
     run_style_generator_case(refs)
