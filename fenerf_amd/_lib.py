@@ -132,6 +132,9 @@ _SIGS = {
     "fenerf_siren_backward_film": (_i, [_vp, _i, _i64] + [_vp] * 10),
     "fenerf_siren_film_grads": (_i, [_vp, _i, _i64] + [_vp] * 5 + [C.POINTER(FenerfSirenGrads)] + [_vp] * 3),
     "fenerf_grid_backward": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "fenerf_model_set_grid_grad_mode": (_i, [_vp, _i]),
+    "fenerf_grid_backward_det_workspace_bytes": (_sz, [_vp, _i64]),
+    "fenerf_grid_backward_det": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "fenerf_siren_backward_fuses_grid": (_i, [_vp]),
     "fenerf_siren_backward_grid": (_i, [_vp, _i, _i64] + [_vp] * 13),
     "fenerf_grid_gradient_ncdhw": (_i, [_vp, _vp, _vp, _vp]),
@@ -166,6 +169,7 @@ EXPORTS = tuple(_SIGS)
 N_PHASES = 17        # include/fenerf.h FENERF_N_PHASES
 FUSION_AUTO, FUSION_OFF, FUSION_FORCE = 0, 1, 2      # include/fenerf.h fenerf_set_render_fusion
 TAPE_F32, TAPE_U16, TAPE_F32_W = 0, 1, 2             # include/fenerf.h FENERF_TAPE_*
+GRID_GRAD_ATOMIC, GRID_GRAD_DETERMINISTIC = 0, 1     # include/fenerf.h FENERF_GRID_GRAD_*
 
 _lib = None
 

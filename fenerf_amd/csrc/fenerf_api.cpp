@@ -330,6 +330,22 @@ extern "C" int fenerf_model_set_forward_mode(FenerfModel* m, int mode) {
   return prev;
 }
 
+extern "C" int fenerf_model_set_grid_grad_mode(FenerfModel* m, int mode) {
+  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
+  if (mode != FENERF_GRID_GRAD_ATOMIC && mode != FENERF_GRID_GRAD_DETERMINISTIC) return fail(FENERF_E_INVALID, "unknown grid-gradient mode");
+  const int prev = m->grid_grad_mode;
+  m->grid_grad_mode = mode;
+  return prev;
+}
+
+// the f16x3 chain kernel scatters d(grid features) itself (atomics); in deterministic mode it writes them out instead
+static bool chain_scatters(const FenerfModel* m) { return m && m->differentiable && m->grid_ch && m->precision == FENERF_PREC_F16X3; }
+static bool grid_det(const FenerfModel* m) { return m && m->grid_ch && m->grid_grad_mode == FENERF_GRID_GRAD_DETERMINISTIC; }
+static int det_unsupported(const char* what) {
+  return fail(FENERF_E_UNSUPPORTED, std::string(what) + " accumulates into the grid gradient per call: not available in FENERF_GRID_GRAD_DETERMINISTIC "
+              "mode -- keep every row's d(grid features) (fenerf_siren_backward) and reduce them once with fenerf_grid_backward_det");
+}
+
 extern "C" int fenerf_model_update(FenerfModel* m, const FenerfModelDesc* d, void* stream) {
   if (!m) return fail(FENERF_E_INVALID, "model is NULL");
   std::string err;
@@ -877,7 +893,7 @@ extern "C" int fenerf_siren_film_grads(const FenerfModel* m, int B, int64_t P, c
 }
 
 extern "C" int fenerf_siren_backward_fuses_grid(const FenerfModel* m) {
-  return m && m->differentiable && m->grid_ch && m->precision == FENERF_PREC_F16X3;
+  return chain_scatters(m) && !grid_det(m);
 }
 
 extern "C" int fenerf_siren_backward_grid(const FenerfModel* m, int B, int64_t P, const float* freq_geo, const float* phase_geo,
@@ -894,6 +910,7 @@ extern "C" int fenerf_siren_backward_grid_fmt(const FenerfModel* m, int B, int64
                                               float* scratch_d_e, void* film_ws, void* stream) {
   if (!m) return fail(FENERF_E_INVALID, "model is NULL");
   if (!m->grid_ch) return fail(FENERF_E_UNSUPPORTED, "model has no feature grid");
+  if (grid_det(m)) return det_unsupported("fenerf_siren_backward_grid");
   if (int rcf = check_tape_format(m, tape_format)) return rcf;
   if (!points || !d_grid_cl) return fail(FENERF_E_INVALID, "points / d_grid_cl is NULL");
   if (!fenerf_siren_backward_fuses_grid(m)) {
@@ -1088,12 +1105,28 @@ extern "C" int fenerf_siren_param_grads_pointwise(const FenerfModel* m, int B, i
 
 extern "C" int fenerf_grid_backward(const FenerfModel* m, int64_t total_points, const float* points, const float* d_e,
                                     float* d_grid_cl, void* stream) {
+  if (grid_det(m)) return det_unsupported("fenerf_grid_backward");
   if (!m) return fail(FENERF_E_INVALID, "model is NULL");
   if (!m->grid_ch) return fail(FENERF_E_UNSUPPORTED, "model has no feature grid");
   if (total_points < 0) return fail(FENERF_E_INVALID, "total_points < 0");
   if (total_points == 0) return FENERF_OK;
   if (!points || !d_e || !d_grid_cl) return fail(FENERF_E_INVALID, "NULL pointer");
   { PhaseScope ph(PH_GRID, stream); return launch_grid_backward(m, total_points, points, d_e, d_grid_cl, stream); }
+}
+
+extern "C" size_t fenerf_grid_backward_det_workspace_bytes(const FenerfModel* m, int64_t rows) {
+  if (!m || rows < 0) return 0;
+  return align_up(grid_det_workspace_bytes(m), 256);
+}
+
+extern "C" int fenerf_grid_backward_det(const FenerfModel* m, int64_t rows, int64_t dense_rows, const float* points, const float* d_e,
+                                        float* d_grid_cl, void* workspace, void* stream) {
+  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
+  if (!m->grid_ch) return fail(FENERF_E_UNSUPPORTED, "model has no feature grid");
+  if (rows < 0 || dense_rows < rows || dense_rows < 1) return fail(FENERF_E_INVALID, "need 0 <= rows <= dense_rows and dense_rows >= 1");
+  if (!d_grid_cl || !workspace || (rows > 0 && (!points || !d_e))) return fail(FENERF_E_INVALID, "NULL pointer");
+  PhaseScope ph(PH_GRID, stream);
+  return launch_grid_backward_det(m, rows, dense_rows, points, d_e, d_grid_cl, false, workspace, stream);
 }
 
 extern "C" int fenerf_grid_gradient_ncdhw(const FenerfModel* m, const float* d_grid_cl, float* d_grid_ncdhw, void* stream) {
@@ -1337,7 +1370,7 @@ long long backward_max_points(const FenerfModel* m, long long Pp, bool film16, l
 }
 
 struct BackwardWs {
-  size_t d_out2, d_fc, dump, dump_stride, d_grid_cl, d_e, wgrad, film2, scratch, total;      // dump_stride: bytes of one chunk's dump (split backward: several slots)
+  size_t d_out2, d_fc, dump, dump_stride, d_grid_cl, d_e, det, wgrad, film2, scratch, total;      // dump_stride: bytes of one chunk's dump (split backward: several slots)
   long long max_chunk_points, film_row;   // film_row = floats of one image's four FiLM gradient rows
   int max_nb;
 };
@@ -1365,8 +1398,12 @@ BackwardWs backward_ws(const FenerfModel* m, int B, int R, int N, int film_only,
     const size_t slots = (size_t)(dump_slots < 1 ? 1 : (dump_slots > (int)chunks.size() ? (int)chunks.size() : dump_slots));
     w.dump = take(w.dump_stride * (slots < 1 ? 1 : slots));
   }
-  w.d_grid_cl = take(m->grid_ch && !film_only ? (size_t)m->gd * m->gh * m->gw * 32 * sizeof(float) : 0);
-  w.d_e = take(m->grid_ch && !fenerf_siren_backward_fuses_grid(m) ? (size_t)w.max_chunk_points * 32 * sizeof(float) : 0);
+  // deterministic grid gradient: d(grid features) of every row of both passes, reduced once into the int64 grid of `det`
+  const bool det = grid_det(m) && !film_only;
+  w.d_grid_cl = take(m->grid_ch && !film_only && !det ? (size_t)m->gd * m->gh * m->gw * 32 * sizeof(float) : 0);
+  w.d_e = take(det ? (size_t)2 * B * Pp * 32 * sizeof(float)
+                   : (m->grid_ch && !chain_scatters(m) ? (size_t)w.max_chunk_points * 32 * sizeof(float) : 0));
+  w.det = take(det ? grid_det_workspace_bytes(m) : 0);
   w.wgrad = take(align_up(wg, 256));
   w.film_row = (long long)2 * (m->n_geo + m->n_color) * m->H;
   w.film2 = take((size_t)2 * B * w.film_row * sizeof(float));
@@ -1530,8 +1567,9 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
   const bool film16 = film_only && m->precision == FENERF_PREC_F16X3;
   const std::vector<Chunk> chunks = plan_chunks(nB, Pp, backward_max_points(m, Pp, film16, chunk_points, film_sums_budget_bytes));
   float* const dump0 = (float*)(wb + wsz.dump);
-  float* d_grid_cl = (m->grid_ch && !film_only) ? (float*)(wb + wsz.d_grid_cl) : nullptr;
-  float* d_e = (m->grid_ch && !fenerf_siren_backward_fuses_grid(m)) ? (float*)(wb + wsz.d_e) : nullptr;
+  const bool det = grid_det(m) && !film_only;          // d_e of every row (pass-major, [2B][Pp][32]), one order-independent reduction
+  float* d_grid_cl = (m->grid_ch && !film_only && !det) ? (float*)(wb + wsz.d_grid_cl) : nullptr;
+  float* d_e = (m->grid_ch && (det || !chain_scatters(m))) ? (float*)(wb + wsz.d_e) : nullptr;
   if (d_grid_cl && stage != 2) HIP_TRY(hipMemsetAsync(d_grid_cl, 0, (size_t)m->gd * m->gh * m->gw * 32 * sizeof(float), st));
   float* film2 = (float*)(wb + wsz.film2);      // [d_freq_geo | d_phase_geo: nB x ng H each][d_freq_app | d_phase_app: nB x nc H each]
   float* f2[4] = {film2, film2 + (size_t)nB * ng * H, film2 + (size_t)2 * nB * ng * H, film2 + (size_t)2 * nB * ng * H + (size_t)nB * nc * H};
@@ -1568,7 +1606,8 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
       bp.d_t = dump; bp.film_tiles = dump + (size_t)L * H * (size_t)npts;
       bp.bf16_dump = use_bf16_dump(m, npts);
       if (m->grid_ch && !film_only) {
-        if (fenerf_siren_backward_fuses_grid(m)) { bp.points = pts_c; bp.d_grid_cl = d_grid_cl; bp.box_scale = m->box_scale; bp.gd = m->gd; bp.gh = m->gh; bp.gw = m->gw; }
+        if (det) bp.d_e = d_e + (size_t)g0 * 32;
+        else if (chain_scatters(m)) { bp.points = pts_c; bp.d_grid_cl = d_grid_cl; bp.box_scale = m->box_scale; bp.gd = m->gd; bp.gh = m->gh; bp.gw = m->gw; }
         else bp.d_e = d_e;
       } else if (m->grid_ch) {
         bp.d_e = d_e;      // FiLM-only on an exact-fp32 model: the chain still writes d(grid features); nobody reads them
@@ -1579,7 +1618,7 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
       rc = m->precision == FENERF_PREC_F16X3 ? launch_siren_backward16w(m, bp, stream) : launch_siren_backward(m, bp, stream);
       if (rc) return rc;
     }
-    if (do_chain && m->grid_ch && !film_only && !fenerf_siren_backward_fuses_grid(m)) {
+    if (do_chain && m->grid_ch && !film_only && !det && !chain_scatters(m)) {
       PhaseScope ph(PH_GRID, stream);
       if ((rc = launch_grid_backward(m, npts, pts_c, d_e, d_grid_cl, stream))) return rc;
     }
@@ -1638,6 +1677,11 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
   if (d_grid_cl && stage != 2) {
     PhaseScope ph(PH_GRID, stream);
     if ((rc = launch_grid_unlayout(d_grid_cl, d_grid_ncdhw, m->gd, m->gh, m->gw, stream))) return rc;
+  }
+  if (det && stage != 2) {        // every chain has run: all rows at once, finished straight into the parameter's layout
+    PhaseScope ph(PH_GRID, stream);
+    const long long rows = (long long)nB * Pp;
+    if ((rc = launch_grid_backward_det(m, rows, rows, pts2, d_e, d_grid_ncdhw, true, wb + wsz.det, stream))) return rc;
   }
   return FENERF_OK;
 }

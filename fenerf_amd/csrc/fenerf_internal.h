@@ -56,6 +56,7 @@ struct FenerfModel {
   int precision;    // FENERF_PREC_*
   int differentiable;       // desc->differentiable: the backward-chain stream is resident too
   int forward_mode;         // FENERF_FORWARD_*: the no-grad forward's arithmetic (fenerf_model_set_forward_mode; FENERF_PREC_F16X3 models)
+  int grid_grad_mode;       // FENERF_GRID_GRAD_*: how backward passes form the feature-grid gradient (fenerf_model_set_grid_grad_mode)
   int wgrad_bf16_min_points; // desc->wgrad_bf16_min_points: 0 = fp32-class weight gradients; > 0 = bf16 dump for chunks of at least that many points
   fenerf::BwdShape bsh;
   float* d_bwd_stream;      // [rgb-head^T entries | backward ring] * 256 floats, or nullptr
@@ -177,6 +178,11 @@ int launch_param_grads(const FenerfModel* m, int B, long long P, const float* po
                        int tape_format = 0, const FenerfSirenGrads* weights = nullptr,
                        int film_per_point = 0);    // film_per_point: fp / pp are [B*P][L][H]; g.d_freq_* / d_phase_* are [B*P][n*H] (FENERF_PREC_F32 models)
 int launch_grid_backward(const FenerfModel* m, long long P, const float* points, const float* d_e, float* d_grid_cl, void* stream);
+// fenerf_grid_det.hip: the order-independent grid gradient of ALL `rows` of a backward pass (overwrites `out`: channels-last [D][H][W][32], or
+// the parameter's [1,32,D,H,W] with to_ncdhw); workspace: grid_det_workspace_bytes(m) bytes
+size_t grid_det_workspace_bytes(const FenerfModel* m);
+int launch_grid_backward_det(const FenerfModel* m, long long rows, long long dense_rows, const float* points, const float* d_e, float* out,
+                             bool to_ncdhw, void* workspace, void* stream);
 // fenerf_siren_inputgrad.hip: d points / d dirs from the fp32 d(theta) dump (layer 0 and colour layer 0) + grid_sample's coordinate gradient
 int launch_siren_input_grads(const FenerfModel* m, int B, long long P, const float* points, const float* fp, const float* d_t, const float* w_geo0,
                              const float* w_color0, int w_color0_ld, float* d_points, float* d_dirs, void* stream);

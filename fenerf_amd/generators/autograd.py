@@ -163,6 +163,7 @@ class HierarchicalRenderFunction(torch.autograd.Function):
             B, R, N = ctx.dims
             save, z_c, noise_f, *params = ctx.saved_tensors
             film_only = not any(need[14:])
+            nat.set_grid_grad_mode(_siren_autograd.deterministic_grid(module))
             r, g_grid = nat.render_backward(B, R, N, save, z_c, noise_f if noise_f.numel() else None, opts, g_rgb.contiguous().float(), film_only,
                                             lock_view=ctx.lock_view, tape_format=ctx.tape_format,
                                             weights=_siren_autograd.film_layer_weights(module, params) if ctx.tape_format else None,
@@ -189,9 +190,15 @@ class HierarchicalRenderFunction(torch.autograd.Function):
         film2 = [torch.cat([t, t]) for t in (fg, pg, fa, pa)]            # pass-major: image b' = pass * B + b
         rd2 = torch.cat([rd, rd]) if rd.numel() else None
         film_only = not any(need[14:])
+        det = _siren_autograd.deterministic_grid(module)
+        nat.set_grid_grad_mode(det)
+        rows = _siren_autograd.GridRows(2 * B * Pp) if (det and nat.spec["grid_ch"] and not film_only) else None
         r, d_grid = _siren_autograd.chunked_backward(nat, 2 * B, Pp, film2, pts2, rd2, out2, d_out2, tape2,
                                                   tape_e2 if tape_e2.numel() else None, film_only, tape_format=ctx.tape_format,
-                                                  weights=_siren_autograd.film_layer_weights(module, params) if ctx.tape_format else None)
+                                                  weights=_siren_autograd.film_layer_weights(module, params) if ctx.tape_format else None,
+                                                  grid_rows=rows)
+        if rows is not None:
+            d_grid = rows.reduce(nat)
         fold = lambda t, ok: (t[:B] + t[B:]) if ok else None
         film_grads = (fold(r["d_freq_geo"], need[10]), fold(r["d_phase_geo"], need[11]), fold(r["d_freq_app"], need[12]),
                       fold(r["d_phase_app"], need[13]))
@@ -295,6 +302,11 @@ def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc
     fmt = module.tape_format(nat, film_only=film_only)
     weights = _siren_autograd.film_layer_weights(module, params) if fmt else None
     total, d_grid, film_rows, kept, flags, first = None, None, [], [], [], 0
+    # deterministic grid gradient: the kept rows of every group, reduced once at the scale of the DENSE backward's row count (its padded
+    # points per image per pass) -- the zero rows the dense backward has beside them add nothing, so dense and sparse get the same bits
+    det = _siren_autograd.deterministic_grid(module)
+    nat.set_grid_grad_mode(det)
+    rows = _siren_autograd.GridRows(passes * B * (-(-(R * N) // 32) * 32)) if (det and nat.spec["grid_ch"] and not film_only) else None
     for g, cap in groups:
         ids = None if whole else perm[first:first + len(g)]
         first += len(g)
@@ -304,7 +316,7 @@ def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc
         film_g = (fg, pg, fa, pa) if whole else tuple(t.index_select(0, ids) for t in (fg, pg, fa, pa))
         out, tape, tape_e = nat.siren_forward_save(pts, rd, *film_g, tape_format=fmt)
         r, d_grid = _siren_autograd.chunked_backward(nat, len(g), cap, film_g, pts, rd, out, d_sel, tape, tape_e, film_only, tape_format=fmt,
-                                                  weights=weights, d_grid=d_grid)
+                                                  weights=weights, d_grid=d_grid, grid_rows=rows)
         del out, tape, tape_e, d_sel
         film_rows.append([r[k] for k in _siren_autograd.FILM_KEYS])
         if not film_only:
@@ -315,6 +327,8 @@ def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc
         kept.append(counts[:len(g)].sum())
         flags.append(counts[len(g)])
     # (a count above its bound would mean the bound's argument is wrong: checked without waiting, reported by the next backward)
+    if rows is not None:
+        d_grid = rows.reduce(nat)
     cls = SparseHierarchicalRenderFunction
     cls._check_overflow(flags[0] if whole else torch.stack(flags).max())
     cls.last_kept = (kept[0] if whole else torch.stack(kept).sum(), S * B)            # for reports (a device scalar: read it after the step)
@@ -515,6 +529,7 @@ class HierarchicalWeightStage(torch.autograd.Function):
         need = ctx.needs_input_grad
         if w.get("abi"):        # fenerf_render_backward_stage(2): the kept chunks' weight gradients, the sums, the FiLM fold -- all in the library
             try:
+                nat.set_grid_grad_mode(w["det"])     # the workspace's layout is stage 1's
                 r = nat.render_backward_stage(2, w["keep"], B, w["R"], w["N"], w["save"], None, None, w["opts"], None, lock_view=w["lock_view"],
                                               tape_format=w["tape_format"], weights=w["weights"], chunk_points=w["chunk_points"], carry=w["carry"])
             finally:
@@ -572,11 +587,13 @@ class HierarchicalRenderSplitFunction(torch.autograd.Function):
             keep = max(1, int(getattr(module, "split_keep_chunks", SPLIT_KEEP_CHUNKS)))
             params = module._render_params()
             weights = _siren_autograd.film_layer_weights(module, params) if ctx.tape_format else None
+            det = _siren_autograd.deterministic_grid(module)
+            nat.set_grid_grad_mode(det)
             g_grid, carry = nat.render_backward_stage(1, keep, B, R, N, save, z_c, noise_f if noise_f.numel() else None, opts, g_rgb.contiguous().float(),
                                                       lock_view=ctx.lock_view, tape_format=ctx.tape_format, weights=weights,
                                                       chunk_points=_siren_autograd.BACKWARD_CHUNK_POINTS)
             state = ctx.state
-            state.work = dict(abi=True, nat=nat, B=B, R=R, N=N, save=save, opts=opts, lock_view=ctx.lock_view, tape_format=ctx.tape_format,
+            state.work = dict(abi=True, det=det, nat=nat, B=B, R=R, N=N, save=save, opts=opts, lock_view=ctx.lock_view, tape_format=ctx.tape_format,
                               weights=weights, keep=keep, chunk_points=_siren_autograd.BACKWARD_CHUNK_POINTS, carry=carry, params=params)
             def drop():         # the engine has finished the pass: whatever the weight stage did not consume is dropped (see below)
                 w_, state.work = state.work, None
@@ -613,11 +630,18 @@ class HierarchicalRenderSplitFunction(torch.autograd.Function):
         tape_e = tape_e2 if tape_e2.numel() else None
         weights = _siren_autograd.film_layer_weights(module, module._render_params()) if ctx.tape_format else None
         acc, d_grid = _siren_autograd.GradSum(), None
+        det = _siren_autograd.deterministic_grid(module)
+        nat.set_grid_grad_mode(det)
+        rows = _siren_autograd.GridRows(2 * B * Pp) if det else None         # (this node exists for models with a grid)
         for c in early:
-            d1, d_grid = _siren_autograd.run_chains(nat, 2 * B, Pp, film2, pts2, out2, d_out2, tape2, [c], tape_format=ctx.tape_format, d_grid=d_grid)
+            d1, d_grid = _siren_autograd.run_chains(nat, 2 * B, Pp, film2, pts2, out2, d_out2, tape2, [c], tape_format=ctx.tape_format, d_grid=d_grid,
+                                                    grid_rows=rows)
             _siren_autograd.run_weight_grads(nat, 2 * B, Pp, film2, pts2, rd2, out2, d_out2, tape2, tape_e, [c], d1, tape_format=ctx.tape_format,
                                              weights=weights, acc=acc, finish=False)
-        dumps, d_grid = _siren_autograd.run_chains(nat, 2 * B, Pp, film2, pts2, out2, d_out2, tape2, late, tape_format=ctx.tape_format, d_grid=d_grid)
+        dumps, d_grid = _siren_autograd.run_chains(nat, 2 * B, Pp, film2, pts2, out2, d_out2, tape2, late, tape_format=ctx.tape_format, d_grid=d_grid,
+                                                   grid_rows=rows)
+        if rows is not None:
+            d_grid = rows.reduce(nat)
         state = ctx.state
         state.work = dict(nat=nat, B=B, Pp=Pp, film2=film2, pts2=pts2, rd2=rd2, out2=out2, d_out2=d_out2, tape2=tape2, tape_format=ctx.tape_format,
                           tape_e2=tape_e, chunks=late, dumps=dumps, acc=acc if early else None, params=module._render_params())

@@ -1,5 +1,6 @@
 """Torch-side plumbing over the C-ABI: device pointers, streams, workspaces.  No math lives here."""
 import ctypes as C
+import warnings
 
 import numpy as np
 import torch
@@ -20,6 +21,19 @@ def _stream():
 
 def _f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def alert_not_deterministic(what):
+    """`what` has no deterministic form: under torch.use_deterministic_algorithms(True) raise RuntimeError (warn with warn_only=True), as
+    torch's own operations do; nothing otherwise"""
+    if not torch.are_deterministic_algorithms_enabled():
+        return
+    msg = (f"fenerf_amd: {what} scatters the feature-grid gradient with fp32 atomics and is not deterministic, but torch.use_deterministic_"
+           "algorithms(True) is set (the autograd nodes take the deterministic route unless the module sets deterministic_backward = False)")
+    if torch.is_deterministic_algorithms_warn_only_enabled():
+        warnings.warn(msg)
+    else:
+        raise RuntimeError(msg)
 
 
 def to_host(t):
@@ -118,6 +132,7 @@ class NativeModel:
         self.box_scale = 2 / 0.24       # UniformBoxWarp(0.24), siren.py:181-187 (what _lib.make_desc sets)
         self._ws = {}
         self.pack_generation = 0      # bumped by every re-pack: autograd nodes check that forward and backward saw the same weights
+        self.grid_grad_mode = _lib.GRID_GRAD_ATOMIC     # include/fenerf.h fenerf_model_set_grid_grad_mode (set_grid_grad_mode)
 
     # ---- hidden widths between the instantiated ones: zero padding on the way in, slicing on the way out (padded_hidden_dim above)
     @property
@@ -655,6 +670,7 @@ class NativeModel:
         out, d_out = _f32(out, self.device), _f32(d_out, self.device)
         points = _f32(points, self.device).reshape(B * P, 3)
         d_t = torch.empty((int(_lib.lib().fenerf_siren_dtheta_floats(self._h, B * P)),), dtype=torch.float32, device=self.device)
+        alert_not_deterministic("NativeModel.siren_backward_grid")
         fused = bool(_lib.lib().fenerf_siren_backward_fuses_grid(self._h))
         scratch = None if fused else torch.empty((B * P, 32), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
@@ -735,6 +751,7 @@ class NativeModel:
 
     def grid_backward(self, points, d_e, grid_shape):
         """Scatter d_e [Ptot,32] into the gradient of spatial_embeddings; returns it in the parameter's [1,32,D,H,W] shape."""
+        alert_not_deterministic("NativeModel.grid_backward")
         D, Hh, W = grid_shape
         points = _f32(points, self.device).reshape(-1, 3)
         g = torch.zeros((D, Hh, W, 32), dtype=torch.float32, device=self.device)
@@ -743,6 +760,34 @@ class NativeModel:
             out = torch.empty((1, 32, D, Hh, W), dtype=torch.float32, device=self.device)
             _lib.check(_lib.lib().fenerf_grid_gradient_ncdhw(self._h, _ptr(g), _ptr(out), _stream()))
         return out
+
+    def set_grid_grad_mode(self, deterministic):
+        """fenerf_model_set_grid_grad_mode: how the next backward passes form the feature-grid gradient -- fp32 atomics (False, the
+        default) or the order-independent reduction of fenerf_grid_backward_det (True).  No-op without a grid.  -> the previous mode."""
+        mode = _lib.GRID_GRAD_DETERMINISTIC if deterministic else _lib.GRID_GRAD_ATOMIC
+        prev = self.grid_grad_mode
+        if self.spec["grid_ch"] and mode != prev:
+            rc = _lib.lib().fenerf_model_set_grid_grad_mode(self._h, mode)
+            if rc < 0:
+                raise _lib.FenerfError(rc, _lib.lib().fenerf_last_error().decode())
+            self.grid_grad_mode = mode
+        return prev
+
+    def grid_backward_det(self, points, d_e, dense_rows):
+        """fenerf_grid_backward_det: d_e [rows,32] at points [rows,3] -- every row of a backward pass at once -> the channels-last gradient
+        grid [D,H,W,32], the same bits whatever the order of the rows.  dense_rows (>= rows): the row count of the dense backward of the same
+        render, which sets the scale (a sparse caller passes the dense count and gets the dense result)."""
+        D, Hh, W = self.grid_shape
+        points = _f32(points, self.device).reshape(-1, 3)
+        d_e = _f32(d_e, self.device).reshape(-1, 32)
+        rows = d_e.shape[0]
+        assert points.shape[0] == rows
+        g = torch.empty((D, Hh, W, 32), dtype=torch.float32, device=self.device)
+        l = _lib.lib()
+        with torch.cuda.device(self.device):
+            ws = self._workspace("grid_det", l.fenerf_grid_backward_det_workspace_bytes(self._h, rows))
+            _lib.check(l.fenerf_grid_backward_det(self._h, rows, int(dense_rows), _ptr(points), _ptr(d_e), _ptr(g), C.c_void_p(ws.data_ptr()), _stream()))
+        return g
 
     def siren_forward_rays(self, origins, dirs, z, fg, pg, fa, pa, lock_view=False):
         """origins/dirs [B,R,3], z [B,R,N] -> [B,R,N,C]"""
@@ -848,6 +893,8 @@ class NativeModel:
         """fenerf_render_backward: every gradient of the render in ONE call -> (dict like siren_param_grads -- FiLM gradients [B, n*H], both
         passes summed; weight / bias gradients unless film_only --, d_grid [1,32,D,H,W] or None)."""
         dev = self.device
+        if self.spec["grid_ch"] and not film_only and self.grid_grad_mode == _lib.GRID_GRAD_ATOMIC:
+            alert_not_deterministic("NativeModel.render_backward (atomic grid-gradient mode)")
         res, g, d_grid = self._render_grad_buffers(B, film_only)
         wts, keep = self._film_weight_struct(weights)
         l = _lib.lib()
@@ -870,6 +917,8 @@ class NativeModel:
         wts, keep = self._film_weight_struct(weights)
         with torch.cuda.device(dev):
             if stage == 1:
+                if self.spec["grid_ch"] and self.grid_grad_mode == _lib.GRID_GRAD_ATOMIC:
+                    alert_not_deterministic("NativeModel.render_backward_stage (atomic grid-gradient mode)")
                 res, g, d_grid = self._render_grad_buffers(B, False)
                 nbytes = int(l.fenerf_render_backward_split_workspace_bytes(self._h, B, R, N, int(chunk_points), int(keep_chunks)))
                 # The workspace must survive until stage 2.  The model's persistent scratch when no other two-stage backward holds it (a

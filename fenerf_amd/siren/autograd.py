@@ -130,6 +130,35 @@ def film_layer_weights(module, params):
     return [W for W, _ in roles["geo"]], [W for W, _ in roles["color"]]
 
 
+def deterministic_grid(module):
+    """True: this backward pass forms the feature-grid gradient with the order-independent reduction (fenerf_grid_backward_det: the same
+    bits run to run, for any chunking, one- or two-node, dense or sparse) instead of fp32 atomics.  `module.deterministic_backward` when
+    set (True / False); None (default) follows torch.are_deterministic_algorithms_enabled() at the time the backward runs."""
+    v = getattr(module, "deterministic_backward", None)
+    return torch.are_deterministic_algorithms_enabled() if v is None else bool(v)
+
+
+class GridRows:
+    """Deterministic grid gradient: d(grid features) of EVERY row of one backward pass with the points they were sampled at, reduced by ONE
+    fenerf_grid_backward_det call.  dense_rows: the row count of the dense backward of the same render (it sets the scale, so a sparse
+    backward that passes only its kept rows gets the dense backward's bits)."""
+
+    def __init__(self, dense_rows):
+        self.dense_rows, self.points, self.d_e = int(dense_rows), [], []
+
+    def add(self, points, d_e):
+        self.points.append(points.reshape(-1, 3))
+        self.d_e.append(d_e.reshape(-1, 32))
+
+    def reduce(self, nat):
+        """-> the channels-last gradient grid [D,H,W,32]"""
+        cat = lambda v: v[0] if len(v) == 1 else torch.cat(v, 0)
+        if not self.d_e:
+            empty = torch.empty((0, 32), dtype=torch.float32, device=nat.device)
+            return nat.grid_backward_det(empty[:, :3], empty, self.dense_rows)
+        return nat.grid_backward_det(cat(self.points), cat(self.d_e), self.dense_rows)
+
+
 class InputGrads(typing.NamedTuple):
     """what chunked_backward needs to also deliver the gradients wrt the SIREN's inputs (NativeModel.siren_input_grads)"""
     w_geo0: torch.Tensor                  # layer 0's nn.Linear weight [H, 3]
@@ -140,7 +169,7 @@ class InputGrads(typing.NamedTuple):
 
 
 def chunked_backward(nat, nB, Pp, film, points, dirs, out, d_out, tape, tape_e, film_only, max_points=None, tape_format=0, weights=None,
-                     input_grads=None, d_grid=None):
+                     input_grads=None, d_grid=None, grid_rows=None):
     """fenerf_siren_backward + fenerf_siren_param_grads over `nB` images of `Pp` points (a multiple of 32) in chunks of at most
     `max_points` points: tiles, tapes and outputs of an image range are contiguous, FiLM parameters are per image, and every gradient
     is a sum over points, so chunk results simply add.  A chunk is a run of WHOLE images while those fit (the curriculum's early
@@ -152,6 +181,8 @@ def chunked_backward(nat, nB, Pp, film, points, dirs, out, d_out, tape, tape_e, 
     input_grads: None or an InputGrads: every chunk also fills its rows of the gradients wrt the sample positions / view directions
     from its d(theta) dump (NativeModel.siren_input_grads); with `only` set (and film_only) the weight- / FiLM-gradient launches are skipped.
     d_grid: None, or the channels-last gradient grid of an earlier call to add to (returned again).
+    grid_rows: a GridRows (deterministic grid gradient): every chunk's d(grid features) are collected there instead of scattered, and the
+    grid gradient returned is None -- the caller reduces once the backward pass has all its rows.
     -> (grads dict like siren_param_grads with [nB]-leading FiLM gradients, d_grid_cl [D,H,W,32] or None)."""
     max_points = BACKWARD_CHUNK_POINTS if max_points is None else max_points
     max_points = max(128, max_points // 128 * 128)       # whole quads of 32-point tiles except in an image's last chunk
@@ -159,7 +190,9 @@ def chunked_backward(nat, nB, Pp, film, points, dirs, out, d_out, tape, tape_e, 
     G = nat.spec["grid_ch"]
     C = nat.C
     out, d_out = out.reshape(nB, Pp, C), d_out.reshape(nB, Pp, C)
-    if d_grid is None:       # (given: the gradient grid an earlier call of the same backward pass started, scattered into further)
+    if grid_rows is not None:
+        d_grid = None
+    elif d_grid is None:       # (given: the gradient grid an earlier call of the same backward pass started, scattered into further)
         d_grid = torch.zeros(tuple(nat.grid_shape) + (32,), dtype=torch.float32, device=out.device) if G and not film_only else None
     # (first image, images, first point, points) per launch
     if Pp <= max_points:
@@ -219,7 +252,10 @@ def chunked_backward(nat, nB, Pp, film, points, dirs, out, d_out, tape, tape_e, 
         tape_c = tape[g0 * LH:(g0 + nb * n) * LH]
         out_c, d_out_c, pts_c = out[b:b + nb, s:s + n], d_out[b:b + nb, s:s + n], points[b:b + nb, s:s + n]
         with native.cu_budget(chain_cus if (overlap and i > 0) else 0):      # chain i runs beside the weight gradients of chunk i - 1
-            if G and not film_only:
+            if G and not film_only and grid_rows is not None:
+                d_t, d_e = nat.siren_backward(nb, n, *film_c, out_c, d_out_c, tape_c, tape_format=tape_format)
+                grid_rows.add(pts_c, d_e)
+            elif G and not film_only:
                 d_t = nat.siren_backward_grid(nb, n, *film_c, out_c, d_out_c, tape_c, pts_c, d_grid, tape_format=tape_format)
             else:       # no grid, or inversion (only FiLM gradients wanted: nothing to scatter)
                 d_t, _ = nat.siren_backward(nb, n, *film_c, out_c, d_out_c, tape_c, tape_format=tape_format)
@@ -310,23 +346,28 @@ class GradSum:
         return total
 
 
-def run_chains(nat, nB, Pp, film, points, out, d_out, tape, chunks, tape_format=0, d_grid=None):
+def run_chains(nat, nB, Pp, film, points, out, d_out, tape, chunks, tape_format=0, d_grid=None, grid_rows=None):
     """First half of a SPLIT backward (generators/autograd.py HierarchicalRenderSplitFunction): the chain launches of `chunks`, nothing else.
     -> ([d(theta) dump per chunk], d_grid_cl or None).  The dumps stay alive until run_weight_grads has consumed them (each as large as its
     chunk's tape: the price of handing the grid gradient -- final once the last chain has run -- to autograd / DistributedDataParallel
     BEFORE the weight-gradient kernels, so that its all-reduce runs beside them).  d_grid: the channels-last gradient grid to scatter into
-    (a caller that runs some chunks' chains elsewhere passes the same one to every call); None = a fresh zeroed one."""
+    (a caller that runs some chunks' chains elsewhere passes the same one to every call); None = a fresh zeroed one.  grid_rows: a GridRows
+    that collects the chunks' d(grid features) instead (deterministic grid gradient; d_grid is then returned as given)."""
     LH = nat.tape_words_per_point(tape_format)
     G, C = nat.spec["grid_ch"], nat.C
     out, d_out = out.reshape(nB, Pp, C), d_out.reshape(nB, Pp, C)
-    if d_grid is None and G:
+    if d_grid is None and G and grid_rows is None:
         d_grid = torch.zeros(tuple(nat.grid_shape) + (32,), dtype=torch.float32, device=out.device)
     dumps = []
     for b, nb, s, n in chunks:
         film_c = tuple(t[b:b + nb] for t in film)
         g0 = b * Pp + s
         tape_c = tape[g0 * LH:(g0 + nb * n) * LH]
-        if G:
+        if G and grid_rows is not None:
+            d_t, d_e = nat.siren_backward(nb, n, *film_c, out[b:b + nb, s:s + n], d_out[b:b + nb, s:s + n], tape_c, tape_format=tape_format)
+            grid_rows.add(points[b:b + nb, s:s + n], d_e)
+            dumps.append(d_t)
+        elif G:
             dumps.append(nat.siren_backward_grid(nb, n, *film_c, out[b:b + nb, s:s + n], d_out[b:b + nb, s:s + n], tape_c, points[b:b + nb, s:s + n], d_grid,
                                                  tape_format=tape_format))
         else:
@@ -404,9 +445,15 @@ class SirenFunction(torch.autograd.Function):
         if d_points is not None or d_dirs is not None:
             w_geo, w_col = film_layer_weights(module, params)
             input_grads = InputGrads(w_geo[0], w_col[0], d_points, d_dirs, only=film_only and not any(need[3:7]))
+        det = deterministic_grid(module)
+        nat.set_grid_grad_mode(det)
+        rows = GridRows(B * P) if (det and spec["grid_ch"] and not film_only) else None
         r, d_grid = chunked_backward(nat, B, P, (fg, pg, fa, pa), points, dirs if ctx.has_dirs else None, out, d_out, tape,
                                      tape_e if tape_e.numel() else None, film_only, tape_format=ctx.tape_format,
-                                     weights=film_layer_weights(module, params) if ctx.tape_format else None, input_grads=input_grads)
+                                     weights=film_layer_weights(module, params) if ctx.tape_format else None, input_grads=input_grads,
+                                     grid_rows=rows)
+        if rows is not None:
+            d_grid = rows.reduce(nat)
         film_grads = (r["d_freq_geo"] if need[3] else None, r["d_phase_geo"] if need[4] else None,
                       r["d_freq_app"] if need[5] else None, r["d_phase_app"] if need[6] else None)
         if film_only:

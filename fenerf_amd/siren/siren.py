@@ -141,6 +141,12 @@ class _NativeSiren(nn.Module):
     grad_precision = "f32"
     AMP_MIN_POINTS = 65536
     FREQ_FROM_WGRAD = True      # (round 5; False = rounds 2-4: the chain kernel forms sum_p d theta * tape itself -- kept for A/B runs and tests)
+    # Gradient wrt the feature grid (spatial_embeddings) of the differentiable path: None (default) follows torch.use_deterministic_algorithms
+    # at the time the backward runs -- on: every row's d(grid features) is kept and all rows are reduced once in exact int64 arithmetic
+    # (include/fenerf.h FENERF_GRID_GRAD_DETERMINISTIC: the same bits run to run, for any chunking, one- or two-node, dense or sparse); off:
+    # the chain kernels' fp32 atomics (faster; the last bits vary).  True / False force one of the two (False under torch's switch raises,
+    # as torch does for an operation without a deterministic form).
+    deterministic_backward = None
 
     def tape_format(self, nat, film_only):
         """the tape format (_lib.TAPE_*) a differentiable evaluation on `nat` uses"""

@@ -216,6 +216,21 @@ void fenerf_model_destroy(FenerfModel* m);
 #define FENERF_FORWARD_F16X3_COLOR_X2 2
 int fenerf_model_set_forward_mode(FenerfModel* m, int mode);
 
+/* How backward passes form the gradient wrt the feature grid (spatial_embeddings; no reference analogue -- grid_sample's backward raises
+ * under torch.use_deterministic_algorithms(True)).  Returns the previous mode or a negative error.
+ *   FENERF_GRID_GRAD_ATOMIC (default)  the chain kernels scatter with fp32 atomics: the last bits of the sum vary from run to run and with
+ *        the chunking;
+ *   FENERF_GRID_GRAD_DETERMINISTIC     every row's gradient wrt its sampled grid features is kept and ALL rows of the backward pass are
+ *        reduced once by fenerf_grid_backward_det: an exact int64 sum at a scale set by the largest value, so the result is the same bit
+ *        for bit whatever the order, the chunking, the split into stages or the rows that are exactly zero.  In this mode
+ *        fenerf_render_backward, fenerf_render_backward_stage and their workspace queries keep d(grid features) of every row (+ 128 B per
+ *        sample point and the int64 grid of fenerf_grid_backward_det_workspace_bytes); fenerf_siren_backward_fuses_grid returns 0; the
+ *        entry points that ACCUMULATE per call (fenerf_siren_backward_grid[_fmt], fenerf_grid_backward) return FENERF_E_UNSUPPORTED.
+ *        Query workspace sizes under the mode the launch will run in. */
+#define FENERF_GRID_GRAD_ATOMIC 0
+#define FENERF_GRID_GRAD_DETERMINISTIC 1
+int fenerf_model_set_grid_grad_mode(FenerfModel* m, int mode);
+
 /* Training keeps the weights on the GPU, so re-packing them through the host every optimizer step (fenerf_model_update)
  * costs more than the step itself.  For FENERF_PREC_F32 models the packed streams are pure permutations (plus zero
  * padding) of the parameters (FENERF_PREC_F16X3: of their scaled fp16 hi / lo halves): the caller builds them on the device (a gather with an index map obtained ONCE by packing
@@ -530,6 +545,17 @@ int fenerf_siren_param_grads(const FenerfModel* m, int B, int64_t P, const float
                              const FenerfSirenGrads* grads, void* workspace, void* film_ws, void* stream);
 int fenerf_grid_backward(const FenerfModel* m, int64_t total_points, const float* points, const float* d_e, float* d_grid_cl,
                          void* stream);
+/* fenerf_grid_backward_det: the gradient wrt the feature grid of `rows` rows d_e [rows][32] at points [rows][3], written (NOT accumulated)
+ * to d_grid_cl [D][H][W][32], independent of the order of the rows -- give it every row of a backward pass at once.  Arithmetic (any mode):
+ * m = max |d_e| over the finite values, m < 2^e; h = ceil(log2(dense_rows)); k = 62 - e - h.  Per finite non-zero value g and in-bounds
+ * corner, q = rint(double(g * (wx * wy * wz)) * 2^k) (fp32 product, fenerf_grid_backward's trilinear arithmetic) is added into an int64
+ * grid; d_grid_cl = float(double(sum) * 2^-k).  Error <= 2^(e + h - 63) per contribution.  dense_rows >= rows is the row count of the
+ * DENSE backward of the same render (2 B x padded points per image for a hierarchical render): a caller that passes only the rows with a
+ * non-zero gradient passes the dense count too, and both get the same scale -- the same bits.  A non-finite value is left out of m and of
+ * the sums; channel c of every in-bounds corner of it is then set to NaN.  workspace: fenerf_grid_backward_det_workspace_bytes bytes [dev]. */
+size_t fenerf_grid_backward_det_workspace_bytes(const FenerfModel* m, int64_t rows);
+int fenerf_grid_backward_det(const FenerfModel* m, int64_t rows, int64_t dense_rows, const float* points, const float* d_e, float* d_grid_cl,
+                             void* workspace, void* stream);
 /* Inversion steps (inverse_render_double_semantic.py:324-410: the weights are frozen, only the per-image FiLM offsets take gradients;
  * what torch autograd does there is the same backward as in training with the weight-gradient products dropped).  FENERF_PREC_F16X3
  * models only (FENERF_E_UNSUPPORTED otherwise -- use fenerf_siren_backward + fenerf_siren_param_grads with NULL weight pointers):
