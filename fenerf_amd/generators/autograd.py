@@ -126,6 +126,41 @@ def _hierarchical_forward(ctx, module, opts, copts, lock_view, origins, dirs, z_
 USE_RENDER_ABI = True
 
 
+def _abi_forward(ctx, module, opts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, params, film_only):
+    """Forward of the render node (one-node form and render stage of the two-node form) through fenerf_render_forward_save; saves what
+    fenerf_render_backward / fenerf_render_backward_stage need on ctx.  `film_only` as the backward will compute it (the tape's format)."""
+    nat = module.native_differentiable(origins.device)
+    B, R, N = z_c.shape
+    ctx.tape_format = module.tape_format(nat, film_only=film_only)
+    rgb, depth, save = nat.render_forward_save(origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, opts, lock_view=lock_view,
+                                               tape_format=ctx.tape_format)
+    ctx.module, ctx.nat, ctx.opts, ctx.dims, ctx.lock_view = module, nat, opts, (B, R, N), lock_view
+    ctx.pack_generation = nat.pack_generation
+    ctx.save_for_backward(save, z_c, noise_f if noise_f is not None else origins.new_empty(0), *params)
+    ctx.mark_non_differentiable(depth)
+    return rgb, depth
+
+
+def _python_composite_backward(nat, opts, dims, g_rgb, rd, film, out2, z_f, zc, noise_f):
+    """Start of the backward of the Python orchestration, over what _hierarchical_forward saved: the composite backward of both passes
+    -> (d_out2 [2B,Pp,C], film2, rd2): the chain's upstream gradient, FiLM parameters and view directions over 2B pass-major "images"
+    (image b' = pass * B + b: coarse | fine)."""
+    B, R, N, P, Pp = dims
+    C = nat.C
+    fine, coarse = out2[B:, :P].reshape(B * R, N, C), out2[:B, :P].reshape(B * R, N, C)
+    noise = noise_f if noise_f.numel() else None
+    if Pp == P:     # whole tiles per image: the composite backward writes the chain's input directly
+        d_out2 = torch.empty_like(out2)
+        native.composite_backward(g_rgb.reshape(B * R, C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc, noise=noise,
+                                  out_a=d_out2[B:].view(B * R, N, C), out_b=d_out2[:B].view(B * R, N, C))
+    else:
+        d_f, d_c = native.composite_backward(g_rgb.reshape(B * R, C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc, noise=noise)
+        d_out2 = torch.zeros((2 * B, Pp, C), dtype=torch.float32, device=out2.device)
+        d_out2[:B, :P] = d_c.reshape(B, P, C)
+        d_out2[B:, :P] = d_f.reshape(B, P, C)
+    return d_out2, [torch.cat([t, t]) for t in film], torch.cat([rd, rd]) if rd.numel() else None
+
+
 class HierarchicalRenderFunction(torch.autograd.Function):
     """The whole differentiable hierarchical render of generators.py:479-519 as ONE autograd node: coarse SIREN pass ->
     (no-grad) coarse weights -> resampled depths -> fine SIREN pass -> merged composite.  Both passes write their tapes into
@@ -142,16 +177,7 @@ class HierarchicalRenderFunction(torch.autograd.Function):
         ctx.abi = USE_RENDER_ABI and not (_siren_autograd.OVERLAP_WGRAD)
         if not ctx.abi:
             return _hierarchical_forward(ctx, module, opts, copts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, params, film_only=film_only)
-        nat = module.native_differentiable(origins.device)
-        B, R, N = z_c.shape
-        ctx.tape_format = module.tape_format(nat, film_only=film_only)
-        rgb, depth, save = nat.render_forward_save(origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, opts, lock_view=lock_view,
-                                                   tape_format=ctx.tape_format)
-        ctx.module, ctx.nat, ctx.opts, ctx.dims, ctx.lock_view = module, nat, opts, (B, R, N), lock_view
-        ctx.pack_generation = nat.pack_generation
-        ctx.save_for_backward(save, z_c, noise_f if noise_f is not None else origins.new_empty(0), *params)
-        ctx.mark_non_differentiable(depth)
-        return rgb, depth
+        return _abi_forward(ctx, module, opts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, params, film_only)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -159,53 +185,27 @@ class HierarchicalRenderFunction(torch.autograd.Function):
         module, nat, opts = ctx.module, ctx.nat, ctx.opts
         _siren_autograd.check_same_weights(ctx, nat)
         need = ctx.needs_input_grad
+        film_only = not any(need[14:])
         if ctx.abi:
             B, R, N = ctx.dims
             save, z_c, noise_f, *params = ctx.saved_tensors
-            film_only = not any(need[14:])
             nat.set_grid_grad_mode(_siren_autograd.deterministic_grid(module))
             r, g_grid = nat.render_backward(B, R, N, save, z_c, noise_f if noise_f.numel() else None, opts, g_rgb.contiguous().float(), film_only,
                                             lock_view=ctx.lock_view, tape_format=ctx.tape_format,
                                             weights=_siren_autograd.film_layer_weights(module, params) if ctx.tape_format else None,
                                             chunk_points=_siren_autograd.BACKWARD_CHUNK_POINTS, film_sums_budget_bytes=_siren_autograd.FILM_SUMS_BUDGET_BYTES)
-            film_grads = tuple(r[k] if need[10 + i] else None for i, k in enumerate(("d_freq_geo", "d_phase_geo", "d_freq_app", "d_phase_app")))
-            head = (None,) * 10
-            if film_only:
-                return head + film_grads + (None,) * len(params)
-            return head + film_grads + _siren_autograd.assemble_param_grads(module, nat, params, r, None, None, need[14:], d_grid_ncdhw=g_grid)
+            return (None,) * 10 + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, d_grid_ncdhw=g_grid)
         B, R, N, P, Pp = ctx.dims
         pts2, rd, fg, pg, fa, pa, out2, tape2, tape_e2, z_f, zc, noise_f, *params = ctx.saved_tensors
-        C = nat.C
-        fine, coarse = out2[B:, :P].reshape(B * R, N, C), out2[:B, :P].reshape(B * R, N, C)
-        if Pp == P:     # whole tiles per image: the composite backward writes the chain's input directly (coarse | fine halves, pass-major)
-            d_out2 = torch.empty_like(out2)
-            native.composite_backward(g_rgb.reshape(B * R, C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc, noise=noise_f if noise_f.numel() else None,
-                                      out_a=d_out2[B:].view(B * R, N, C), out_b=d_out2[:B].view(B * R, N, C))
-        else:
-            d_f, d_c = native.composite_backward(g_rgb.reshape(B * R, C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc,
-                                                 noise=noise_f if noise_f.numel() else None)
-            d_out2 = torch.zeros((2 * B, Pp, C), dtype=torch.float32, device=out2.device)
-            d_out2[:B, :P] = d_c.reshape(B, P, C)
-            d_out2[B:, :P] = d_f.reshape(B, P, C)
-        film2 = [torch.cat([t, t]) for t in (fg, pg, fa, pa)]            # pass-major: image b' = pass * B + b
-        rd2 = torch.cat([rd, rd]) if rd.numel() else None
-        film_only = not any(need[14:])
-        det = _siren_autograd.deterministic_grid(module)
-        nat.set_grid_grad_mode(det)
-        rows = _siren_autograd.GridRows(2 * B * Pp) if (det and nat.spec["grid_ch"] and not film_only) else None
+        d_out2, film2, rd2 = _python_composite_backward(nat, opts, ctx.dims, g_rgb, rd, (fg, pg, fa, pa), out2, z_f, zc, noise_f)
+        rows = _siren_autograd.begin_grid_gradient(module, nat, 2 * B * Pp, film_only)
         r, d_grid = _siren_autograd.chunked_backward(nat, 2 * B, Pp, film2, pts2, rd2, out2, d_out2, tape2,
                                                   tape_e2 if tape_e2.numel() else None, film_only, tape_format=ctx.tape_format,
                                                   weights=_siren_autograd.film_layer_weights(module, params) if ctx.tape_format else None,
                                                   grid_rows=rows)
         if rows is not None:
             d_grid = rows.reduce(nat)
-        fold = lambda t, ok: (t[:B] + t[B:]) if ok else None
-        film_grads = (fold(r["d_freq_geo"], need[10]), fold(r["d_phase_geo"], need[11]), fold(r["d_freq_app"], need[12]),
-                      fold(r["d_phase_app"], need[13]))
-        head = (None,) * 10
-        if film_only:
-            return head + film_grads + (None,) * len(params)
-        return head + film_grads + _siren_autograd.assemble_param_grads(module, nat, params, r, pts2, d_grid, need[14:])
+        return (None,) * 10 + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, B=B, d_grid_cl=d_grid)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
@@ -225,6 +225,35 @@ class HierarchicalRenderFunction(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------------------------------------------
 class SparseHierarchicalRenderFunction(torch.autograd.Function):
     """HierarchicalRenderFunction's signature and results; see the block comment above."""
+
+    # report and check state of the LAST sparse backward of the process (either sparse node)
+    last_kept = None            # (kept samples: a device scalar -- read it after the step, all samples)
+    last_groups = None          # [(images, slots per image)] of its launch groups
+    _pending = None             # (pinned overflow flag, event of its copy) not yet read
+
+    @staticmethod
+    def _check_overflow(overflowed):
+        """Deferred assertion of the sparse backward's buffer bound: the flag of THIS call is copied to the host without waiting and read by the
+        next call (or by SparseHierarchicalRenderFunction.verify()); a set flag means samples were dropped -- an error, never a silent result."""
+        SparseHierarchicalRenderFunction.verify(wait=False)
+        flag = torch.empty((), dtype=torch.bool, pin_memory=True)
+        flag.copy_(overflowed != 0, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        SparseHierarchicalRenderFunction._pending = (flag, ev)
+
+    @staticmethod
+    def verify(wait=True):
+        if SparseHierarchicalRenderFunction._pending is None:
+            return
+        flag, ev = SparseHierarchicalRenderFunction._pending
+        if not wait and not ev.query():
+            return
+        ev.synchronize()
+        SparseHierarchicalRenderFunction._pending = None
+        if bool(flag):
+            raise RuntimeError("fenerf_amd: sparse backward: more samples carried a non-zero gradient row than the forward's bound allowed for; "
+                               "the gradients of that backward pass are incomplete (please report; siren.sparse_backward = False avoids it)")
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -304,9 +333,7 @@ def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc
     total, d_grid, film_rows, kept, flags, first = None, None, [], [], [], 0
     # deterministic grid gradient: the kept rows of every group, reduced once at the scale of the DENSE backward's row count (its padded
     # points per image per pass) -- the zero rows the dense backward has beside them add nothing, so dense and sparse get the same bits
-    det = _siren_autograd.deterministic_grid(module)
-    nat.set_grid_grad_mode(det)
-    rows = _siren_autograd.GridRows(passes * B * (-(-(R * N) // 32) * 32)) if (det and nat.spec["grid_ch"] and not film_only) else None
+    rows = _siren_autograd.begin_grid_gradient(module, nat, passes * B * (-(-(R * N) // 32) * 32), film_only)
     for g, cap in groups:
         ids = None if whole else perm[first:first + len(g)]
         first += len(g)
@@ -329,20 +356,15 @@ def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc
     # (a count above its bound would mean the bound's argument is wrong: checked without waiting, reported by the next backward)
     if rows is not None:
         d_grid = rows.reduce(nat)
-    cls = SparseHierarchicalRenderFunction
-    cls._check_overflow(flags[0] if whole else torch.stack(flags).max())
-    cls.last_kept = (kept[0] if whole else torch.stack(kept).sum(), S * B)            # for reports (a device scalar: read it after the step)
-    cls.last_groups = [(list(g), c) for g, c in groups]
+    SparseHierarchicalRenderFunction._check_overflow(flags[0] if whole else torch.stack(flags).max())
+    SparseHierarchicalRenderFunction.last_kept = (kept[0] if whole else torch.stack(kept).sum(), S * B)            # for reports (a device scalar: read it after the step)
+    SparseHierarchicalRenderFunction.last_groups = [(list(g), c) for g, c in groups]
     if whole:
         film_g = film_rows[0]
     else:       # rows back into image order
         film_g = [torch.cat([rows[i] for rows in film_rows], 0).index_select(0, torch.argsort(perm)) for i in range(len(_siren_autograd.FILM_KEYS))]
-    fr = dict(zip(_siren_autograd.FILM_KEYS, film_g))
-    film_grads = tuple(fr[k] if need[10 + i] else None for i, k in enumerate(("d_freq_geo", "d_phase_geo", "d_freq_app", "d_phase_app")))
-    head = (None,) * 10
-    if film_only:
-        return head + film_grads + (None,) * len(params)
-    return head + film_grads + _siren_autograd.assemble_param_grads(module, nat, params, total, None, d_grid, need[14:])
+    r = {**(total or {}), **dict(zip(_siren_autograd.FILM_KEYS, film_g))}         # the groups' summed weight gradients, every image's FiLM rows
+    return (None,) * 10 + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, d_grid_cl=d_grid)
 
 
 class SparseSinglePassRenderFunction(torch.autograd.Function):
@@ -376,41 +398,6 @@ class SparseSinglePassRenderFunction(torch.autograd.Function):
         C = nat.C
         d = native.composite_backward(g_rgb.contiguous().float().reshape(B * R, C - 1), rows, zc, opts, noise=noise_f if noise_f.numel() else None)
         return _sparse_siren_backward(ctx, module, nat, ctx.needs_input_grad, B, R, N, 1, d, None, zc, None, origins, dirs, (fg, pg, fa, pa), params)
-
-
-SparseHierarchicalRenderFunction.last_groups = None
-SparseHierarchicalRenderFunction.last_kept = None
-SparseHierarchicalRenderFunction._pending = None
-
-
-def _check_overflow(overflowed):
-    """Deferred assertion of the sparse backward's buffer bound: the flag of THIS call is copied to the host without waiting and read by the
-    next call (or by SparseHierarchicalRenderFunction.verify()); a set flag means samples were dropped -- an error, never a silent result."""
-    cls = SparseHierarchicalRenderFunction
-    cls.verify(wait=False)
-    flag = torch.empty((), dtype=torch.bool, pin_memory=True)
-    flag.copy_(overflowed != 0, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record()
-    cls._pending = (flag, ev)
-
-
-def _verify(wait=True):
-    cls = SparseHierarchicalRenderFunction
-    if cls._pending is None:
-        return
-    flag, ev = cls._pending
-    if not wait and not ev.query():
-        return
-    ev.synchronize()
-    cls._pending = None
-    if bool(flag):
-        raise RuntimeError("fenerf_amd: sparse backward: more samples carried a non-zero gradient row than the forward's bound allowed for; "
-                           "the gradients of that backward pass are incomplete (please report; siren.sparse_backward = False avoids it)")
-
-
-SparseHierarchicalRenderFunction._check_overflow = staticmethod(_check_overflow)
-SparseHierarchicalRenderFunction.verify = staticmethod(_verify)
 
 
 # `siren.sparse_backward = "auto"`: the sparse node while it pays, the dense node otherwise.  What the sparse backward costs is set by the
@@ -534,23 +521,18 @@ class HierarchicalWeightStage(torch.autograd.Function):
                                               tape_format=w["tape_format"], weights=w["weights"], chunk_points=w["chunk_points"], carry=w["carry"])
             finally:
                 nat.release_split_workspace(w["carry"])
-            film_grads = tuple(r[k] if need[2 + i] else None for i, k in enumerate(("d_freq_geo", "d_phase_geo", "d_freq_app", "d_phase_app")))
-            params = w["params"]
-            grid = module._roles(params)["grid"]
-            all_grads = _siren_autograd.assemble_param_grads(module, nat, params, r, None, None, [True] * len(params))
-            no_grid = [g for p_, g in zip(params, all_grads) if p_ is not grid]
-            return (None, None) + film_grads + tuple(g if need[6 + i] else None for i, g in enumerate(no_grid))
-        r = _siren_autograd.run_weight_grads(nat, 2 * B, w["Pp"], w["film2"], w["pts2"], w["rd2"], w["out2"], w["d_out2"], w["tape2"], w["tape_e2"],
-                                             w["chunks"], w["dumps"], tape_format=w["tape_format"],
-                                             weights=_siren_autograd.film_layer_weights(module, w["params"]) if w["tape_format"] else None,
-                                             acc=w["acc"])
-        fold = lambda t, ok: (t[:B] + t[B:]) if ok else None
-        film_grads = (fold(r["d_freq_geo"], need[2]), fold(r["d_phase_geo"], need[3]), fold(r["d_freq_app"], need[4]), fold(r["d_phase_app"], need[5]))
+        else:
+            r = _siren_autograd.run_weight_grads(nat, 2 * B, w["Pp"], w["film2"], w["pts2"], w["rd2"], w["out2"], w["d_out2"], w["tape2"], w["tape_e2"],
+                                                 w["chunks"], w["dumps"], tape_format=w["tape_format"],
+                                                 weights=_siren_autograd.film_layer_weights(module, w["params"]) if w["tape_format"] else None,
+                                                 acc=w["acc"])
         params = w["params"]                                    # module._render_params() order, grid included
         grid = module._roles(params)["grid"]
-        all_grads = _siren_autograd.assemble_param_grads(module, nat, params, r, w["pts2"], None, [True] * len(params))
+        all_grads = _siren_autograd.assemble_param_grads(module, nat, params, r, None, None, [True] * len(params))
         no_grid = [g for p_, g in zip(params, all_grads) if p_ is not grid]
-        return (None, None) + film_grads + tuple(g if need[6 + i] else None for i, g in enumerate(no_grid))
+        # (the library's stage 2 has folded the two passes' FiLM rows already; the Python route's are folded here)
+        return (None, None) + _siren_autograd.film_grads(r, need, 2, None if w.get("abi") else B) \
+            + tuple(g if need[6 + i] else None for i, g in enumerate(no_grid))
 
 
 class HierarchicalRenderSplitFunction(torch.autograd.Function):
@@ -565,16 +547,7 @@ class HierarchicalRenderSplitFunction(torch.autograd.Function):
         if not ctx.abi:
             return _hierarchical_forward(ctx, module, opts, copts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, (),
                                          film_only=False)        # the split form exists for training steps: weight gradients are taken
-        nat = module.native_differentiable(origins.device)
-        B, R, N = z_c.shape
-        ctx.tape_format = module.tape_format(nat, film_only=False)
-        rgb, depth, save = nat.render_forward_save(origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, opts, lock_view=lock_view,
-                                                   tape_format=ctx.tape_format)
-        ctx.module, ctx.nat, ctx.opts, ctx.dims, ctx.lock_view = module, nat, opts, (B, R, N), lock_view
-        ctx.pack_generation = nat.pack_generation
-        ctx.save_for_backward(save, z_c, noise_f if noise_f is not None else origins.new_empty(0))
-        ctx.mark_non_differentiable(depth)
-        return rgb, depth
+        return _abi_forward(ctx, module, opts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, (), film_only=False)
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -606,20 +579,7 @@ class HierarchicalRenderSplitFunction(torch.autograd.Function):
             return (None, g_token, g_grid if ctx.needs_input_grad[2] else None) + (None,) * 14
         B, R, N, P, Pp = ctx.dims
         pts2, rd, fg, pg, fa, pa, out2, tape2, tape_e2, z_f, zc, noise_f = ctx.saved_tensors
-        C = nat.C
-        fine, coarse = out2[B:, :P].reshape(B * R, N, C), out2[:B, :P].reshape(B * R, N, C)
-        if Pp == P:
-            d_out2 = torch.empty_like(out2)
-            native.composite_backward(g_rgb.reshape(B * R, C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc, noise=noise_f if noise_f.numel() else None,
-                                      out_a=d_out2[B:].view(B * R, N, C), out_b=d_out2[:B].view(B * R, N, C))
-        else:
-            d_f, d_c = native.composite_backward(g_rgb.reshape(B * R, C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc,
-                                                 noise=noise_f if noise_f.numel() else None)
-            d_out2 = torch.zeros((2 * B, Pp, C), dtype=torch.float32, device=out2.device)
-            d_out2[:B, :P] = d_c.reshape(B, P, C)
-            d_out2[B:, :P] = d_f.reshape(B, P, C)
-        film2 = [torch.cat([t, t]) for t in (fg, pg, fa, pa)]            # pass-major: image b' = pass * B + b
-        rd2 = torch.cat([rd, rd]) if rd.numel() else None
+        d_out2, film2, rd2 = _python_composite_backward(nat, opts, ctx.dims, g_rgb, rd, (fg, pg, fa, pa), out2, z_f, zc, noise_f)
         chunks = _siren_autograd.plan_chunks(2 * B, Pp)
         # Bounded memory (round 5): only the LAST `split_keep_chunks` chunks' dumps are kept for the weight stage -- their weight-gradient
         # kernels are what the grid gradient's all-reduce runs beside; every earlier chunk takes its chain AND its weight gradients right
@@ -630,9 +590,7 @@ class HierarchicalRenderSplitFunction(torch.autograd.Function):
         tape_e = tape_e2 if tape_e2.numel() else None
         weights = _siren_autograd.film_layer_weights(module, module._render_params()) if ctx.tape_format else None
         acc, d_grid = _siren_autograd.GradSum(), None
-        det = _siren_autograd.deterministic_grid(module)
-        nat.set_grid_grad_mode(det)
-        rows = _siren_autograd.GridRows(2 * B * Pp) if det else None         # (this node exists for models with a grid)
+        rows = _siren_autograd.begin_grid_gradient(module, nat, 2 * B * Pp)       # (this node exists for models with a grid)
         for c in early:
             d1, d_grid = _siren_autograd.run_chains(nat, 2 * B, Pp, film2, pts2, out2, d_out2, tape2, [c], tape_format=ctx.tape_format, d_grid=d_grid,
                                                     grid_rows=rows)

@@ -159,6 +159,15 @@ class GridRows:
         return nat.grid_backward_det(cat(self.points), cat(self.d_e), self.dense_rows)
 
 
+def begin_grid_gradient(module, nat, dense_rows, film_only=False):
+    """Start of every backward pass of the Python route: selects how the library forms the feature-grid gradient (deterministic_grid) and
+    -> the GridRows the pass collects its d(grid features) in (`dense_rows` rows in the dense backward), or None: fp32 atomics, or no grid
+    gradient to form."""
+    det = deterministic_grid(module)
+    nat.set_grid_grad_mode(det)
+    return GridRows(dense_rows) if (det and nat.spec["grid_ch"] and not film_only) else None
+
+
 class InputGrads(typing.NamedTuple):
     """what chunked_backward needs to also deliver the gradients wrt the SIREN's inputs (NativeModel.siren_input_grads)"""
     w_geo0: torch.Tensor                  # layer 0's nn.Linear weight [H, 3]
@@ -168,149 +177,9 @@ class InputGrads(typing.NamedTuple):
     only: bool = False                    # nothing else is wanted (with film_only): the weight- / FiLM-gradient launches are skipped
 
 
-def chunked_backward(nat, nB, Pp, film, points, dirs, out, d_out, tape, tape_e, film_only, max_points=None, tape_format=0, weights=None,
-                     input_grads=None, d_grid=None, grid_rows=None):
-    """fenerf_siren_backward + fenerf_siren_param_grads over `nB` images of `Pp` points (a multiple of 32) in chunks of at most
-    `max_points` points: tiles, tapes and outputs of an image range are contiguous, FiLM parameters are per image, and every gradient
-    is a sum over points, so chunk results simply add.  A chunk is a run of WHOLE images while those fit (the curriculum's early
-    stages: 6-12 images of 32x32x24 = 24,576 points per pass -- one launch of 8 images fills the 256 CUs, eight launches of 192
-    workgroups do not); an image larger than `max_points` is split into point ranges of its own.  The gradient wrt the sampled grid
-    features never exists as a tensor: every chunk scatters it into one channels-last gradient grid (fenerf_siren_backward_grid;
-    inside the chain kernel for f16x3 models).
-    tape_format / weights: the tape's format (_lib.TAPE_*) and, for the 16-bit tape, film_layer_weights(...).
-    input_grads: None or an InputGrads: every chunk also fills its rows of the gradients wrt the sample positions / view directions
-    from its d(theta) dump (NativeModel.siren_input_grads); with `only` set (and film_only) the weight- / FiLM-gradient launches are skipped.
-    d_grid: None, or the channels-last gradient grid of an earlier call to add to (returned again).
-    grid_rows: a GridRows (deterministic grid gradient): every chunk's d(grid features) are collected there instead of scattered, and the
-    grid gradient returned is None -- the caller reduces once the backward pass has all its rows.
-    -> (grads dict like siren_param_grads with [nB]-leading FiLM gradients, d_grid_cl [D,H,W,32] or None)."""
-    max_points = BACKWARD_CHUNK_POINTS if max_points is None else max_points
-    max_points = max(128, max_points // 128 * 128)       # whole quads of 32-point tiles except in an image's last chunk
-    LH = nat.tape_words_per_point(tape_format)          # fp32 words of tape per point
-    G = nat.spec["grid_ch"]
-    C = nat.C
-    out, d_out = out.reshape(nB, Pp, C), d_out.reshape(nB, Pp, C)
-    if grid_rows is not None:
-        d_grid = None
-    elif d_grid is None:       # (given: the gradient grid an earlier call of the same backward pass started, scattered into further)
-        d_grid = torch.zeros(tuple(nat.grid_shape) + (32,), dtype=torch.float32, device=out.device) if G and not film_only else None
-    # (first image, images, first point, points) per launch
-    if Pp <= max_points:
-        per = max(1, max_points // Pp)
-        chunks = [(b, min(per, nB - b), 0, Pp) for b in range(0, nB, per)]
-    else:
-        chunks = [(b, 1, s, min(max_points, Pp - s)) for b in range(nB) for s in range(0, Pp, max_points)]
-    if film_only and nat.film_only_native() and input_grads is None:      # (the input gradients are read from the dump this route does not write)
-        # Inversion on an f16x3 model: the chain writes only its per-tile FiLM sums (fenerf_siren_backward_film) -- no d(theta) dump.
-        # A launch is bounded by the kernel's 32-bit tile arithmetic (2^24 points) and by FILM_SUMS_BUDGET_BYTES of FiLM sums (one
-        # [L][2][H] block per 128 points, or per 16 points when an image is not a multiple of 128 points: 176 B / 1.4 KB per point at
-        # H = 256); an image larger than that is walked in point ranges whose FiLM gradients add.
-        sums_bytes_pp = 4.0 * nat.film_sums_floats(1, Pp) / Pp
-        cap = int(max(128, min(1 << 24, FILM_SUMS_BUDGET_BYTES / sums_bytes_pp)) // 128 * 128)
-        if Pp <= cap:
-            per = max(1, cap // Pp)
-            fchunks = [(b, min(per, nB - b), 0, Pp) for b in range(0, nB, per)]
-        else:
-            fchunks = [(b, 1, s, min(cap, Pp - s)) for b in range(nB) for s in range(0, Pp, cap)]
-        rows, acc = {k: [] for k in FILM_KEYS}, None
-        for b, nb, s, n in fchunks:
-            film_c = tuple(t[b:b + nb] for t in film)
-            g0 = b * Pp + s
-            tape_c = tape[g0 * LH:(g0 + nb * n) * LH]
-            sums = nat.siren_backward_film(nb, n, *film_c, out[b:b + nb, s:s + n], d_out[b:b + nb, s:s + n], tape_c)
-            r = nat.siren_film_grads(nb, n, *film_c, sums)
-            if s == 0:
-                acc = [r[k] for k in FILM_KEYS]
-                for k, t in zip(FILM_KEYS, acc):
-                    rows[k].append(t)
-            else:
-                _add_all(acc, [r[k] for k in FILM_KEYS])
-        return {k: (torch.cat(v, 0) if len(v) > 1 else v[0]) for k, v in rows.items()}, None
-    # ---- chain + weight gradients per chunk.  With more than one chunk the weight gradients of chunk i run on a second stream BESIDE
-    # the chain of chunk i + 1 (OVERLAP_WGRAD): the chain kernel is persistent, one workgroup per CU, and scales with the CUs it is
-    # given; the weight-gradient kernels are HBM-bound and lose nothing on a quarter of the chip (profiles/r04_gstep_overlap.md) -- so the
-    # chain is launched for CHAIN_CUS_FRACTION of the CUs and the weight-gradient grids are sized for the rest (fenerf_set_cu_budget).
-    # The first chain and the last weight-gradient launch have the device to themselves.  Every d(theta) dump is kept alive until the
-    # end of the loop and tied to the side stream (record_stream); scratch is per stream (NativeModel._workspace).
-    dev = out.device
-    inputs_only = bool(input_grads is not None and film_only and input_grads.only)
-    overlap = OVERLAP_WGRAD and len(chunks) > 1 and not inputs_only
-    main = torch.cuda.current_stream(dev)
-    side = _side_stream(dev) if overlap else main
-    n_cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    chain_cus = max(1, int(n_cus * CHAIN_CUS_FRACTION)) if overlap else 0
-    wgrad_cus = max(1, n_cus - chain_cus) if overlap else 0
-    if overlap:
-        side.wait_stream(main)            # everything the weight gradients read (tape, outputs, upstream gradient) was produced on `main`
-    total, film_rows = None, {k: [] for k in FILM_KEYS}
-    acc_img = None           # FiLM gradients of the image whose point ranges are being walked
-    keep = []
-    for i, (b, nb, s, n) in enumerate(chunks):
-        last = i == len(chunks) - 1
-        film_c = tuple(t[b:b + nb] for t in film)
-        g0 = b * Pp + s
-        tape_c = tape[g0 * LH:(g0 + nb * n) * LH]
-        out_c, d_out_c, pts_c = out[b:b + nb, s:s + n], d_out[b:b + nb, s:s + n], points[b:b + nb, s:s + n]
-        with native.cu_budget(chain_cus if (overlap and i > 0) else 0):      # chain i runs beside the weight gradients of chunk i - 1
-            if G and not film_only and grid_rows is not None:
-                d_t, d_e = nat.siren_backward(nb, n, *film_c, out_c, d_out_c, tape_c, tape_format=tape_format)
-                grid_rows.add(pts_c, d_e)
-            elif G and not film_only:
-                d_t = nat.siren_backward_grid(nb, n, *film_c, out_c, d_out_c, tape_c, pts_c, d_grid, tape_format=tape_format)
-            else:       # no grid, or inversion (only FiLM gradients wanted: nothing to scatter)
-                d_t, _ = nat.siren_backward(nb, n, *film_c, out_c, d_out_c, tape_c, tape_format=tape_format)
-        if input_grads is not None:       # a chunk is whole images or a point range of one image: its rows are contiguous
-            dp, dd = input_grads.d_points, input_grads.d_dirs
-            nat.siren_input_grads(pts_c, *film_c, d_t, input_grads.w_geo0, input_grads.w_color0, dp[b:b + nb, s:s + n] if dp is not None else None,
-                                  dd[b:b + nb, s:s + n] if dd is not None else None)
-        if overlap:
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-            d_t.record_stream(side)
-            keep.append(d_t)
-        if inputs_only:        # nothing but d points / d view directions was asked for: the dump has been read, no weight-gradient launch
-            del d_t
-            continue
-        with torch.cuda.stream(side), native.cu_budget(wgrad_cus if (overlap and not last) else 0):
-            r = nat.siren_param_grads(pts_c, dirs[b:b + nb, s:s + n] if dirs is not None else None, *film_c, out_c, d_out_c, tape_c,
-                                      tape_e[g0:g0 + nb * n] if G else None, d_t, film_only=film_only, tape_format=tape_format, weights=weights)
-            del d_t
-            if total is None:
-                total = {k: ([x for x in v] if isinstance(v, list) else v) for k, v in r.items() if k not in FILM_KEYS}
-            else:
-                _add_all(_flat(total), _flat(r, FILM_KEYS))      # one fused launch for all ~40 tensors
-            if s == 0:
-                acc_img = [r[k] for k in FILM_KEYS]
-                for k, t in zip(FILM_KEYS, acc_img):
-                    film_rows[k].append(t)
-            else:
-                _add_all(acc_img, [r[k] for k in FILM_KEYS])
-            if last:
-                for k, rows in film_rows.items():
-                    total[k] = torch.cat(rows, 0) if len(rows) > 1 else rows[0]
-    if inputs_only:
-        return {k: None for k in FILM_KEYS}, None
-    if overlap:
-        main.wait_stream(side)
-        for t in _flat(total):            # allocated on the side stream, consumed by autograd on `main`
-            t.record_stream(main)
-    return total, d_grid
-
-
-_SIDE_STREAMS = {}
-
-
-def _side_stream(dev):
-    """one extra HIP stream per device for the overlapped weight gradients (created once)"""
-    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _SIDE_STREAMS[key]
-
-
 def plan_chunks(nB, Pp, max_points=None):
-    """(first image, images, first point, points) per backward launch -- the chunking of chunked_backward"""
+    """(first image, images, first point, points) per backward launch: whole images while those fit `max_points` (rounded down to whole
+    quads of 32-point tiles, at least one), point ranges of one image otherwise.  The only chunk plan of the Python backward."""
     max_points = BACKWARD_CHUNK_POINTS if max_points is None else max_points
     max_points = max(128, max_points // 128 * 128)
     if Pp <= max_points:
@@ -319,9 +188,42 @@ def plan_chunks(nB, Pp, max_points=None):
     return [(b, 1, s, min(max_points, Pp - s)) for b in range(nB) for s in range(0, Pp, max_points)]
 
 
+def _chunk_views(chunk, Pp, LH, film, tape, *rows):
+    """A chunk's views: (FiLM rows of its images, its `LH` words per point of the tape, its rows of every [nB, Pp, .] tensor of `rows`).
+    A chunk is whole images or a point range of one image, so all of them are contiguous."""
+    b, nb, s, n = chunk
+    g0 = b * Pp + s
+    return (tuple(t[b:b + nb] for t in film), tape[g0 * LH:(g0 + nb * n) * LH]) + tuple(t[b:b + nb, s:s + n] if t is not None else None for t in rows)
+
+
+def chain_chunk(nat, chunk, Pp, film, points, out, d_out, tape, tape_format, want_grid, d_grid, grid_rows):
+    """The chain launch of one chunk -> its d(theta) dump.  want_grid (the model has a grid and weight gradients are wanted): the gradient
+    wrt the sampled grid features goes to `grid_rows` when given (deterministic grid gradient), else the chain scatters it into `d_grid`."""
+    film_c, tape_c, out_c, d_out_c, pts_c = _chunk_views(chunk, Pp, nat.tape_words_per_point(tape_format), film, tape, out, d_out, points)
+    nb, n = chunk[1], chunk[3]
+    if want_grid and grid_rows is not None:
+        d_t, d_e = nat.siren_backward(nb, n, *film_c, out_c, d_out_c, tape_c, tape_format=tape_format)
+        grid_rows.add(pts_c, d_e)
+    elif want_grid:
+        d_t = nat.siren_backward_grid(nb, n, *film_c, out_c, d_out_c, tape_c, pts_c, d_grid, tape_format=tape_format)
+    else:       # no grid, or inversion (only FiLM gradients wanted: nothing to scatter)
+        d_t, _ = nat.siren_backward(nb, n, *film_c, out_c, d_out_c, tape_c, tape_format=tape_format)
+    return d_t
+
+
+def weight_grads_chunk(nat, chunk, Pp, film, points, dirs, out, d_out, tape, tape_e, d_t, film_only, tape_format, weights):
+    """The weight-gradient launch of one chunk over the dump `d_t` its chain left -> siren_param_grads' dict"""
+    film_c, tape_c, pts_c, dirs_c, out_c, d_out_c = _chunk_views(chunk, Pp, nat.tape_words_per_point(tape_format), film, tape, points, dirs, out, d_out)
+    b, nb, s, n = chunk
+    g0 = b * Pp + s
+    return nat.siren_param_grads(pts_c, dirs_c, *film_c, out_c, d_out_c, tape_c, tape_e[g0:g0 + nb * n] if nat.spec["grid_ch"] else None, d_t,
+                                 film_only=film_only, tape_format=tape_format, weights=weights)
+
+
 class GradSum:
-    """The sum of per-chunk siren_param_grads results in chunk order, exactly as chunked_backward forms it: weight / bias gradients add,
-    FiLM gradients are one row per (pass, image) -- written by the image's first point range, added to by its later ones."""
+    """The sum of per-chunk siren_param_grads (or siren_film_grads: no weight part) results in chunk order -- the only one of the Python
+    backward: weight / bias gradients add as ((r0 + r1) + r2) ... with one fused launch per chunk for all ~40 tensors, FiLM gradients are
+    one row per (pass, image) -- the tensor of the image's first point range, added to in place by its later ones."""
 
     def __init__(self):
         self.total, self.film_rows, self.acc_img = None, {k: [] for k in FILM_KEYS}, None
@@ -346,6 +248,103 @@ class GradSum:
         return total
 
 
+def chunked_backward(nat, nB, Pp, film, points, dirs, out, d_out, tape, tape_e, film_only, max_points=None, tape_format=0, weights=None,
+                     input_grads=None, d_grid=None, grid_rows=None):
+    """fenerf_siren_backward + fenerf_siren_param_grads over `nB` images of `Pp` points (a multiple of 32) in chunks of at most
+    `max_points` points (plan_chunks): tiles, tapes and outputs of an image range are contiguous, FiLM parameters are per image, and every
+    gradient is a sum over points, so chunk results simply add (GradSum).  A chunk is a run of WHOLE images while those fit (the
+    curriculum's early stages: 6-12 images of 32x32x24 = 24,576 points per pass -- one launch of 8 images fills the 256 CUs, eight
+    launches of 192 workgroups do not); an image larger than `max_points` is split into point ranges of its own.  The gradient wrt the
+    sampled grid features never exists as a tensor: every chunk scatters it into one channels-last gradient grid
+    (fenerf_siren_backward_grid; inside the chain kernel for f16x3 models).
+    tape_format / weights: the tape's format (_lib.TAPE_*) and, for the 16-bit tape, film_layer_weights(...).
+    input_grads: None or an InputGrads: every chunk also fills its rows of the gradients wrt the sample positions / view directions
+    from its d(theta) dump (NativeModel.siren_input_grads); with `only` set (and film_only) the weight- / FiLM-gradient launches are skipped.
+    d_grid: None, or the channels-last gradient grid of an earlier call to add to (returned again).
+    grid_rows: a GridRows (deterministic grid gradient): every chunk's d(grid features) are collected there instead of scattered, and the
+    grid gradient returned is None -- the caller reduces once the backward pass has all its rows.
+    -> (grads dict like siren_param_grads with [nB]-leading FiLM gradients, d_grid_cl [D,H,W,32] or None)."""
+    C = nat.C
+    LH = nat.tape_words_per_point(tape_format)          # fp32 words of tape per point
+    out, d_out = out.reshape(nB, Pp, C), d_out.reshape(nB, Pp, C)
+    want_grid = bool(nat.spec["grid_ch"]) and not film_only
+    if grid_rows is not None:
+        d_grid = None
+    elif d_grid is None and want_grid:       # (given: the gradient grid an earlier call of the same backward pass started, scattered into further)
+        d_grid = torch.zeros(tuple(nat.grid_shape) + (32,), dtype=torch.float32, device=out.device)
+    acc = GradSum()
+    if film_only and nat.film_only_native() and input_grads is None:      # (the input gradients are read from the dump this route does not write)
+        # Inversion on an f16x3 model: the chain writes only its per-tile FiLM sums (fenerf_siren_backward_film) -- no d(theta) dump.
+        # A launch is bounded by the kernel's 32-bit tile arithmetic (2^24 points) and by FILM_SUMS_BUDGET_BYTES of FiLM sums (one
+        # [L][2][H] block per 128 points, or per 16 points when an image is not a multiple of 128 points: 176 B / 1.4 KB per point at
+        # H = 256); an image larger than that is walked in point ranges whose FiLM gradients add.
+        sums_bytes_pp = 4.0 * nat.film_sums_floats(1, Pp) / Pp
+        cap = int(max(128, min(1 << 24, FILM_SUMS_BUDGET_BYTES / sums_bytes_pp)) // 128 * 128)      # a multiple of 128, at least 128: plan_chunks' own rounding leaves it alone
+        for chunk in plan_chunks(nB, Pp, cap):
+            film_c, tape_c, out_c, d_out_c = _chunk_views(chunk, Pp, LH, film, tape, out, d_out)
+            sums = nat.siren_backward_film(chunk[1], chunk[3], *film_c, out_c, d_out_c, tape_c)
+            acc.add(chunk, nat.siren_film_grads(chunk[1], chunk[3], *film_c, sums))
+        return acc.result(), None
+    # ---- chain + weight gradients per chunk.  With more than one chunk the weight gradients of chunk i run on a second stream BESIDE
+    # the chain of chunk i + 1 (OVERLAP_WGRAD): the chain kernel is persistent, one workgroup per CU, and scales with the CUs it is
+    # given; the weight-gradient kernels are HBM-bound and lose nothing on a quarter of the chip (profiles/r04_gstep_overlap.md) -- so the
+    # chain is launched for CHAIN_CUS_FRACTION of the CUs and the weight-gradient grids are sized for the rest (fenerf_set_cu_budget).
+    # The first chain and the last weight-gradient launch have the device to themselves.  Every d(theta) dump is kept alive until the
+    # end of the loop and tied to the side stream (record_stream); scratch is per stream (NativeModel._workspace).
+    chunks = plan_chunks(nB, Pp, max_points)
+    dev = out.device
+    inputs_only = bool(input_grads is not None and film_only and input_grads.only)
+    overlap = OVERLAP_WGRAD and len(chunks) > 1 and not inputs_only
+    main = torch.cuda.current_stream(dev)
+    side = _side_stream(dev) if overlap else main
+    n_cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    chain_cus = max(1, int(n_cus * CHAIN_CUS_FRACTION)) if overlap else 0
+    wgrad_cus = max(1, n_cus - chain_cus) if overlap else 0
+    if overlap:
+        side.wait_stream(main)            # everything the weight gradients read (tape, outputs, upstream gradient) was produced on `main`
+    total, keep = None, []
+    for i, chunk in enumerate(chunks):
+        last = i == len(chunks) - 1
+        with native.cu_budget(chain_cus if (overlap and i > 0) else 0):      # chain i runs beside the weight gradients of chunk i - 1
+            d_t = chain_chunk(nat, chunk, Pp, film, points, out, d_out, tape, tape_format, want_grid, d_grid, grid_rows)
+        if input_grads is not None:
+            film_c, _, pts_c, dp, dd = _chunk_views(chunk, Pp, LH, film, tape, points, input_grads.d_points, input_grads.d_dirs)
+            nat.siren_input_grads(pts_c, *film_c, d_t, input_grads.w_geo0, input_grads.w_color0, dp, dd)
+        if overlap:
+            ev = torch.cuda.Event()
+            ev.record(main)
+            side.wait_event(ev)
+            d_t.record_stream(side)
+            keep.append(d_t)
+        if inputs_only:        # nothing but d points / d view directions was asked for: the dump has been read, no weight-gradient launch
+            del d_t
+            continue
+        with torch.cuda.stream(side), native.cu_budget(wgrad_cus if (overlap and not last) else 0):
+            r = weight_grads_chunk(nat, chunk, Pp, film, points, dirs, out, d_out, tape, tape_e, d_t, film_only, tape_format, weights)
+            del d_t
+            acc.add(chunk, r)
+            if last:
+                total = acc.result()
+    if inputs_only:
+        return {k: None for k in FILM_KEYS}, None
+    if overlap:
+        main.wait_stream(side)
+        for t in _flat(total):            # allocated on the side stream, consumed by autograd on `main`
+            t.record_stream(main)
+    return total, d_grid
+
+
+_SIDE_STREAMS = {}
+
+
+def _side_stream(dev):
+    """one extra HIP stream per device for the overlapped weight gradients (created once)"""
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _SIDE_STREAMS:
+        _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
+    return _SIDE_STREAMS[key]
+
+
 def run_chains(nat, nB, Pp, film, points, out, d_out, tape, chunks, tape_format=0, d_grid=None, grid_rows=None):
     """First half of a SPLIT backward (generators/autograd.py HierarchicalRenderSplitFunction): the chain launches of `chunks`, nothing else.
     -> ([d(theta) dump per chunk], d_grid_cl or None).  The dumps stay alive until run_weight_grads has consumed them (each as large as its
@@ -353,47 +352,41 @@ def run_chains(nat, nB, Pp, film, points, out, d_out, tape, chunks, tape_format=
     BEFORE the weight-gradient kernels, so that its all-reduce runs beside them).  d_grid: the channels-last gradient grid to scatter into
     (a caller that runs some chunks' chains elsewhere passes the same one to every call); None = a fresh zeroed one.  grid_rows: a GridRows
     that collects the chunks' d(grid features) instead (deterministic grid gradient; d_grid is then returned as given)."""
-    LH = nat.tape_words_per_point(tape_format)
     G, C = nat.spec["grid_ch"], nat.C
     out, d_out = out.reshape(nB, Pp, C), d_out.reshape(nB, Pp, C)
     if d_grid is None and G and grid_rows is None:
         d_grid = torch.zeros(tuple(nat.grid_shape) + (32,), dtype=torch.float32, device=out.device)
-    dumps = []
-    for b, nb, s, n in chunks:
-        film_c = tuple(t[b:b + nb] for t in film)
-        g0 = b * Pp + s
-        tape_c = tape[g0 * LH:(g0 + nb * n) * LH]
-        if G and grid_rows is not None:
-            d_t, d_e = nat.siren_backward(nb, n, *film_c, out[b:b + nb, s:s + n], d_out[b:b + nb, s:s + n], tape_c, tape_format=tape_format)
-            grid_rows.add(points[b:b + nb, s:s + n], d_e)
-            dumps.append(d_t)
-        elif G:
-            dumps.append(nat.siren_backward_grid(nb, n, *film_c, out[b:b + nb, s:s + n], d_out[b:b + nb, s:s + n], tape_c, points[b:b + nb, s:s + n], d_grid,
-                                                 tape_format=tape_format))
-        else:
-            dumps.append(nat.siren_backward(nb, n, *film_c, out[b:b + nb, s:s + n], d_out[b:b + nb, s:s + n], tape_c, tape_format=tape_format)[0])
-    return dumps, d_grid
+    return [chain_chunk(nat, c, Pp, film, points, out, d_out, tape, tape_format, bool(G), d_grid, grid_rows) for c in chunks], d_grid
 
 
 def run_weight_grads(nat, nB, Pp, film, points, dirs, out, d_out, tape, tape_e, chunks, dumps, tape_format=0, weights=None, acc=None, finish=True):
     """Second half of a split backward: the weight-gradient launches of `chunks` over the dumps run_chains left, summed like
     chunked_backward does (acc: a GradSum that already holds earlier chunks' gradients).  Frees each dump after its chunk.
     -> grads dict (FiLM gradients with [nB] leading), or the GradSum itself when not `finish`."""
-    LH = nat.tape_words_per_point(tape_format)
-    G, C = nat.spec["grid_ch"], nat.C
+    C = nat.C
     out, d_out = out.reshape(nB, Pp, C), d_out.reshape(nB, Pp, C)
     acc = GradSum() if acc is None else acc
-    for i, (b, nb, s, n) in enumerate(chunks):
-        film_c = tuple(t[b:b + nb] for t in film)
-        g0 = b * Pp + s
-        tape_c = tape[g0 * LH:(g0 + nb * n) * LH]
+    for i, chunk in enumerate(chunks):
         d_t, dumps[i] = dumps[i], None
-        r = nat.siren_param_grads(points[b:b + nb, s:s + n], dirs[b:b + nb, s:s + n] if dirs is not None else None, *film_c,
-                                  out[b:b + nb, s:s + n], d_out[b:b + nb, s:s + n], tape_c, tape_e[g0:g0 + nb * n] if G else None, d_t,
-                                  tape_format=tape_format, weights=weights)
+        r = weight_grads_chunk(nat, chunk, Pp, film, points, dirs, out, d_out, tape, tape_e, d_t, False, tape_format, weights)
         del d_t
-        acc.add((b, nb, s, n), r)
+        acc.add(chunk, r)
     return acc.result() if finish else acc
+
+
+def film_grads(r, need, first, B=None):
+    """The four FiLM gradients of a backward's return tuple: r[k] where input `first` + i of the node needs one, else None.
+    B: r holds the two passes of B images each (pass-major), folded into one row per image here."""
+    fold = (lambda t: t) if B is None else (lambda t: t[:B] + t[B:])
+    return tuple(fold(r[k]) if need[first + i] else None for i, k in enumerate(FILM_KEYS))
+
+
+def grads_tail(module, nat, params, r, need, first, film_only, B=None, d_grid_cl=None, d_grid_ncdhw=None):
+    """The end of a backward's return tuple: film_grads(...) for inputs `first` .. `first` + 3, then one slot per parameter (inputs from
+    `first` + 4 on): all None for a FiLM-only backward, else assemble_param_grads(...)."""
+    if film_only:
+        return film_grads(r, need, first, B) + (None,) * len(params)
+    return film_grads(r, need, first, B) + assemble_param_grads(module, nat, params, r, None, d_grid_cl, need[first + 4:], d_grid_ncdhw=d_grid_ncdhw)
 
 
 def check_same_weights(ctx, nat):
@@ -430,10 +423,6 @@ class SirenFunction(torch.autograd.Function):
         module, nat = ctx.module, ctx.nat
         check_same_weights(ctx, nat)
         points, dirs, fg, pg, fa, pa, out, tape, tape_e, *params = ctx.saved_tensors
-        roles = module._roles(params)
-        spec = nat.spec
-        ng, C = spec["n_geo"], spec["output_dim"]
-        n_lab = C - 4
         B, P = points.shape[0], points.shape[1]
         d_out = d_out.contiguous().float()
         need = ctx.needs_input_grad
@@ -445,20 +434,14 @@ class SirenFunction(torch.autograd.Function):
         if d_points is not None or d_dirs is not None:
             w_geo, w_col = film_layer_weights(module, params)
             input_grads = InputGrads(w_geo[0], w_col[0], d_points, d_dirs, only=film_only and not any(need[3:7]))
-        det = deterministic_grid(module)
-        nat.set_grid_grad_mode(det)
-        rows = GridRows(B * P) if (det and spec["grid_ch"] and not film_only) else None
+        rows = begin_grid_gradient(module, nat, B * P, film_only)
         r, d_grid = chunked_backward(nat, B, P, (fg, pg, fa, pa), points, dirs if ctx.has_dirs else None, out, d_out, tape,
                                      tape_e if tape_e.numel() else None, film_only, tape_format=ctx.tape_format,
                                      weights=film_layer_weights(module, params) if ctx.tape_format else None, input_grads=input_grads,
                                      grid_rows=rows)
         if rows is not None:
             d_grid = rows.reduce(nat)
-        film_grads = (r["d_freq_geo"] if need[3] else None, r["d_phase_geo"] if need[4] else None,
-                      r["d_freq_app"] if need[5] else None, r["d_phase_app"] if need[6] else None)
-        if film_only:
-            return (None, d_points, d_dirs) + film_grads + (None,) * len(params)
-        return (None, d_points, d_dirs) + film_grads + assemble_param_grads(module, nat, params, r, points, d_grid, need[7:])
+        return (None, d_points, d_dirs) + grads_tail(module, nat, params, r, need, 3, film_only, d_grid_cl=d_grid)
 
 
 class PointwiseSirenFunction(torch.autograd.Function):
@@ -485,9 +468,7 @@ class PointwiseSirenFunction(torch.autograd.Function):
         points, dirs, fg, pg, fa, pa, out, tape, *params = ctx.saved_tensors
         need = ctx.needs_input_grad
         r = nat.siren_backward_pointwise(points, dirs if ctx.has_dirs else None, fg, pg, fa, pa, out, d_out.contiguous().float(), tape)
-        film_grads = (r["d_freq_geo"] if need[3] else None, r["d_phase_geo"] if need[4] else None,
-                      r["d_freq_app"] if need[5] else None, r["d_phase_app"] if need[6] else None)
-        return (None, None, None) + film_grads + assemble_param_grads(module, nat, params, r, points, None, need[7:])
+        return (None, None, None) + grads_tail(module, nat, params, r, need, 3, False)
 
 
 def siren_apply_pointwise(module, points, dirs, fg, pg, fa, pa):

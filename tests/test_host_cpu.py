@@ -548,6 +548,55 @@ def test_backward_chunk_plan_and_grid_digest():
     assert native.NativeModel._grid_checksum(odd).shape == (45,)
 
 
+def test_backward_gradient_sum_over_chunks_is_the_sequential_sum():
+    """siren/autograd.py GradSum, the one sum of per-chunk gradients of the Python backward, over fake per-chunk results for plans from
+    plan_chunks -- a plan is whole-image chunks (here 2 + 2 + 1 images) or point ranges of single images (here 4 x 128 + 32 points of
+    each of 3 images), so both kinds are fed, and one sum is carried across both (the two-node backward hands its GradSum on):
+    weight / bias gradients bit-identical to the left-to-right sum ((r0 + r1) + r2) ..., FiLM gradients one row per image in image
+    order, each the left-to-right sum over that image's point ranges.  A result without a weight part (the FiLM-only route) sums too."""
+    from fenerf_amd.siren import autograd as SA
+    gen = torch.Generator().manual_seed(7)
+    rnd = lambda *shape: torch.randn(*shape, generator=gen) * 10.0 ** torch.randint(-3, 4, shape, generator=gen).float()
+    widths = dict(zip(SA.FILM_KEYS, (24, 24, 8, 8)))
+
+    def fake(nb, weights=True):
+        r = {k: rnd(nb, w) for k, w in widths.items()}
+        if weights:
+            r.update(geo_w=[rnd(8, 3), rnd(8, 8)], geo_b=[rnd(8), rnd(8)], head_w=rnd(32, 8), rgb_b=rnd(3))
+        return r
+
+    def check(plans, weights):
+        chunks = [c for plan in plans for c in plan]
+        results = [fake(nb, weights) for _, nb, _, _ in chunks]
+        flat = lambda r: [t for k in sorted(r) if k not in SA.FILM_KEYS for t in (r[k] if isinstance(r[k], list) else [r[k]])]
+        want_w = [t.clone() for t in flat(results[0])]
+        for r in results[1:]:
+            want_w = [a + b for a, b in zip(want_w, flat(r))]
+        want_film = {k: [] for k in SA.FILM_KEYS}
+        for (b, nb, s, n), r in zip(chunks, results):
+            for k in SA.FILM_KEYS:
+                if s == 0:
+                    want_film[k].append(r[k].clone())
+                else:
+                    want_film[k][-1] = want_film[k][-1] + r[k]
+        acc = SA.GradSum()
+        for c, r in zip(chunks, results):
+            acc.add(c, r)
+        got = acc.result()
+        assert sorted(got) == sorted(results[0])
+        assert len(flat(got)) == len(want_w) and all(torch.equal(a, b) for a, b in zip(flat(got), want_w))
+        images = sum(nb for _, nb, s, _ in chunks if s == 0)
+        for k in SA.FILM_KEYS:
+            assert got[k].shape == (images, widths[k]) and torch.equal(got[k], torch.cat(want_film[k], 0)), k
+
+    whole, ranges = SA.plan_chunks(5, 256, 512), SA.plan_chunks(3, 544, 128)
+    assert [nb for _, nb, _, _ in whole] == [2, 2, 1] and len(ranges) == 15 and ranges[4] == (0, 1, 512, 32) and ranges[5] == (1, 1, 0, 128)
+    for weights in (True, False):
+        check([whole], weights)
+        check([ranges], weights)
+        check([whole, ranges], weights)
+
+
 @pytest.mark.parametrize("n_layers", [1, 2, 3, 4])
 def test_label_head_fold_backward_is_the_gradient_of_the_fold(n_layers):
     """The label head (activation-free Linear stack, siren.py label_layer_linear; reference siren.py:1000-1012) is folded into one
