@@ -79,14 +79,9 @@ __global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_ker
       for (int s = 0; s < SLOTS; ++s) {
         const int i = lane + 64 * s;
         if (i < M) {
-          const float zi = s_z[wv][i];
-          int rank = 0;
-          for (int j = 0; j < M; ++j) {
-            const float zj = s_z[wv][j];
-            rank += (zj < zi || (zj == zi && j < i)) ? 1 : 0;
-          }
+          const int rank = merge_rank(s_z[wv], M, i);   // a permutation for any depths, NaN included: the store addresses below stay in the ray
           s_ord[wv][rank] = i;
-          s_zs[wv][rank] = zi;
+          s_zs[wv][rank] = s_z[wv][i];
         }
       }
     } else {
@@ -125,7 +120,7 @@ __global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_ker
         if (P.noise) x = __fadd_rn(x, __fmul_rn(P.noise[ray * M + k], P.o.noise_std));
         float act;
         if (P.o.clamp_mode == FENERF_CLAMP_SOFTPLUS) { act = softplus_f(x); dact[s] = x > 20.f ? 1.f : 1.f / (1.f + expf(-x)); }
-        else { act = fmaxf(x, 0.f); dact[s] = x > 0.f ? 1.f : 0.f; }
+        else { act = relu_f(x); dact[s] = x > 0.f ? 1.f : (x != x ? x : 0.f); }   // NaN in, NaN out (F.relu)
         alpha[s] = M > 1 ? 1.f - expf(-delta[s] * act) : 0.f;
         tt[s] = 1.f - alpha[s] + 1e-10f;
         float acc = 0.f;
@@ -188,7 +183,10 @@ __global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_ker
       const int k = lane + 64 * s;
       if (k < M) {
         const float dalpha = T[s] * gw[s] - S[s] / tt[s];
-        const float dsigma = (M > 1) ? dalpha * delta[s] * (1.f - alpha[s]) * dact[s] : 0.f;
+        float dsigma = (M > 1) ? dalpha * delta[s] * (1.f - alpha[s]) * dact[s] : 0.f;
+        // relu at x <= 0: autograd SELECTS a zero there (threshold_backward), it does not multiply by zero -- a non-finite upstream gradient
+        // stops at a clamped sample.  (A finite product is already the zero, with its sign: unchanged.)
+        if (P.o.clamp_mode != FENERF_CLAMP_SOFTPLUS && dact[s] == 0.f && dsigma != dsigma) dsigma = 0.f;
         if (staged) {
           float* o = s_out[wv] + s_ord[wv][k] * C;
           for (int c = 0; c < nch; ++c) o[c] = wp[s] * g[c];
@@ -291,7 +289,9 @@ __global__ __launch_bounds__(256) void resample_kernel(long long BR, int K, int 
       const int i = lane + 64 * s;
       if (i < NS) {
         const float ui = u[ray * NS + i];
-        int inds = 0;                                   // torch.searchsorted(cdf, u) (left): #knots < u  (:286)
+        // torch.searchsorted(cdf, u) (left): #knots < u  (:286).  A count of K + 1 comparisons, each false when either side is NaN:
+        // 0 <= inds <= K + 1, so 0 <= below, above <= K whatever the weights, depths and draws hold -- no index depends on a value otherwise
+        int inds = 0;
         for (int j = 0; j <= K; ++j) inds += s_cdf[wv][j] < ui ? 1 : 0;
         const int below = inds - 1 > 0 ? inds - 1 : 0;  // (:287-288)
         const int above = inds < K ? inds : K;
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void ray_setup_kernel(int B, int S, int N, flo
   // camera origin on the unit sphere (:220-228)
   const float theta = theta_in[b];
   float phi = phi_in[b];
-  phi = fminf(fmaxf(phi, 1e-5f), 3.14159265358979323846f - 1e-5f);
+  phi = phi != phi ? phi : fminf(fmaxf(phi, 1e-5f), 3.14159265358979323846f - 1e-5f);   // torch.clamp hands a NaN on
   const float sp = sinf(phi), cp = cosf(phi), st = sinf(theta), ct = cosf(theta);
   const float ox = __fmul_rn(sp, ct), oy = cp, oz = __fmul_rn(sp, st);
   // look-at basis (:230-248): forward = normalize(normalize(-o)), left = normalize(up x f), up' = normalize(f x left)

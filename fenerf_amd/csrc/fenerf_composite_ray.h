@@ -44,6 +44,30 @@ __device__ __forceinline__ float softplus_f(float x) {  // F.softplus(beta=1, th
   return x > 20.f ? x : log1pf(expf(x));
 }
 
+// F.relu (volumetric_rendering.py:32) hands a NaN on; fmaxf(NaN, 0) would return 0 and render a finite pixel from a NaN density.
+// Finite x: the value fmaxf(x, 0.f) gives.
+__device__ __forceinline__ float relu_f(float x) { return x > 0.f ? x : (x != x ? x : 0.f); }
+
+// Sorted position of source sample i among the M depths in s_z: the total order of torch.sort on the CPU (generators.py:510) -- ascending,
+// NaN after +Inf, equal depths and NaNs among themselves by source index.  Total, so the M ranks are a permutation of 0 .. M-1 for ANY
+// bit pattern in s_z: every s_ord slot is written exactly once, and the row addresses derived from s_ord stay inside the ray.
+__device__ __forceinline__ int merge_rank(const float* s_z, const int M, const int i) {
+  const float zi = s_z[i];
+  int rank = 0;
+  if (zi == zi) {
+    for (int j = 0; j < M; ++j) {
+      const float zj = s_z[j];
+      rank += (zj < zi || (zj == zi && j < i)) ? 1 : 0;   // a NaN zj compares false: it sorts after every number
+    }
+  } else {
+    for (int j = 0; j < M; ++j) {
+      const float zj = s_z[j];
+      rank += (zj == zj || j < i) ? 1 : 0;                // after every number and after the NaNs in front of it
+    }
+  }
+  return rank;
+}
+
 // s_z [MAXM] (z by source index / cdf), s_zs [MAXM + 1] (sorted z), s_ord [MAXM] (sorted position -> source index), s_w [MAXM] (weights by
 // sorted position): this wave's LDS scratch.  P.M <= MAXM.
 template <bool MERGE, int MAXM>
@@ -66,14 +90,9 @@ __device__ __forceinline__ void composite_ray(const CompositeParams& P, const lo
     for (int s = 0; s < SLOTS; ++s) {
       const int i = lane + 64 * s;
       if (i < M) {
-        const float zi = s_z[i];
-        int rank = 0;
-        for (int j = 0; j < M; ++j) {
-          const float zj = s_z[j];
-          rank += (zj < zi || (zj == zi && j < i)) ? 1 : 0;   // stable ascending (torch.sort, generators.py:510)
-        }
+        const int rank = merge_rank(s_z, M, i);   // stable ascending, NaN last (torch.sort, generators.py:510)
         s_ord[rank] = i;
-        s_zs[rank] = zi;
+        s_zs[rank] = s_z[i];
       }
     }
   } else {
@@ -101,7 +120,7 @@ __device__ __forceinline__ void composite_ray(const CompositeParams& P, const lo
       const float delta = (k == M - 1) ? 1e10f : (s_zs[k + 1] - zk[s]);
       float x = sg[s];
       if (P.noise) x = __fadd_rn(x, __fmul_rn(P.noise[ray * M + k], P.o.noise_std));
-      const float act = P.o.clamp_mode == FENERF_CLAMP_SOFTPLUS ? softplus_f(x) : fmaxf(x, 0.f);
+      const float act = P.o.clamp_mode == FENERF_CLAMP_SOFTPLUS ? softplus_f(x) : relu_f(x);
       // M == 1: the reference builds delta_inf from deltas[:, :, :1] of an EMPTY deltas tensor (:23-25), so every
       // per-sample tensor is empty and rgb / depth / weights_sum come out 0 -- reproduce that.
       alpha[s] = M > 1 ? 1.f - expf(-delta * act) : 0.f;
@@ -172,7 +191,7 @@ __device__ __forceinline__ void composite_ray(const CompositeParams& P, const lo
       const int i = lane + 64 * s;
       if (i < M) {
         const float ui = P.u[ray * M + i];
-        int inds = 0;
+        int inds = 0;   // a count of K + 1 comparisons (false for a NaN on either side): 0 <= below, above <= K = M - 2 for any values
         for (int j = 0; j <= K; ++j) inds += s_z[j] < ui ? 1 : 0;
         const int below = inds - 1 > 0 ? inds - 1 : 0;
         const int above = inds < K ? inds : K;

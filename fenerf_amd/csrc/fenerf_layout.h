@@ -109,6 +109,8 @@ constexpr long long film_tile_floats(long long tiles, int L, int H) { return til
 // partial sums instead (fenerf_siren_wgrad.hip), so inversion -- FiLM gradients only, no weight-gradient launch -- keeps the fp32 tape.
 // Gradient accuracy: 1.1e-4 (max-norm relative, simulated and measured) on top of the 3.5e-5 of the bf16x3 products: between the fp32
 // class (6e-5 asserted) and the AMP class (3e-3), hence a tier of its own (siren.grad_precision = "tape16"), never the default.
+// Code 0xffff is reserved: a NaN or +-Inf phase is stored as it and read back as NaN (tape16_phase, fenerf_trig.h); a finite phase that
+// would round to it is stored as 0.
 constexpr int dump16_feature(int nb, int g, int t) { return 32 * nb + 16 * (g >> 1) + 4 * (g & 1) + 8 * (t >> 2) + (t & 3); }
 constexpr int tape_feature(int g, int half, int i) { return 32 * (g >> 2) + 8 * (g & 3) + 4 * half + i; }
 

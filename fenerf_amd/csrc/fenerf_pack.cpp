@@ -492,6 +492,7 @@ int pack_weights_bwd(const FenerfModelDesc* d, std::vector<float>& blob, std::st
 // ------------------------------------------------------------------------------------------------
 static inline uint16_t bf16_rne(float v) {
   uint32_t b; memcpy(&b, &v, 4);
+  if (v != v) return (uint16_t)((b >> 16) | 0x0040u);   // a NaN stays a NaN: the rounding add would carry 0x7fffffff into -0
   return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
 }
 static inline float bf16_f32(uint16_t h) { uint32_t b = (uint32_t)h << 16; float v; memcpy(&v, &b, 4); return v; }

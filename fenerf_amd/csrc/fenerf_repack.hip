@@ -101,6 +101,7 @@ __global__ void repack_gather_f16_kernel(const float* flat, const float* scale, 
 
 __device__ __forceinline__ uint16_t bf16_rne_bits(float v) {
   const unsigned b = __builtin_bit_cast(unsigned, v);
+  if (v != v) return (uint16_t)((b >> 16) | 0x0040u);   // a NaN stays a NaN (bf16_rne, fenerf_pack.cpp)
   return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
 }
 

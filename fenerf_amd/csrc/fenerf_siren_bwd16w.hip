@@ -300,7 +300,7 @@ __device__ __forceinline__ EpiOut epi_compute(const f32x4& acc, const EpiIn& q, 
     float th, tr = 0.f;
     if (T16) {    // frac(theta) as 16-bit fixed point: already reduced to [0, 1) revolutions
       const unsigned w = q.tu[r >> 1];
-      th = (float)((r & 1) ? (w >> 16) : (w & 0xffffu)) * (1.f / 65536.f);
+      th = tape16_phase((r & 1) ? (w >> 16) : (w & 0xffffu));
     } else {
       const float p[4] = {q.p.x, q.p.y, q.p.z, q.p.w}, t[4] = {q.t.x, q.t.y, q.t.z, q.t.w};
       tr = t[r];

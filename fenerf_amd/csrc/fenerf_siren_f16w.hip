@@ -131,8 +131,13 @@ __device__ __forceinline__ void st_u4_nt(const void* g_uniform, unsigned voff, c
 struct TapeQ { unsigned q[4]; };
 // frac(theta) in revolutions -> round-to-nearest 16-bit fixed point in the low half of the result (65536 wraps to 0 = the same phase):
 // fr * 2^16 + 2^23 rounds to an integer in the mantissa (RNE)
+// A NaN or +-Inf theta (sin of it is NaN) takes the reserved code TAPE16_NONFINITE (fenerf_trig.h).  A finite phase that rounds to that
+// code -- frac * 2^16 in (65534.5, 65535.5) -- is stored as the nearer of its neighbours 0xfffe and 0 (= one revolution): at most 2^-16
+// rev off instead of 2^-17, for one code in 65,536.  (The mask only serves the comparison: v_perm takes the low halves anyway.)
 __device__ __forceinline__ unsigned phase_u16(float theta) {
-  return __builtin_bit_cast(unsigned, __builtin_fmaf(__builtin_amdgcn_fractf(theta), 65536.f, 8388608.f));
+  const float v = __builtin_amdgcn_fractf(theta) * 65536.f;                                   // exact: a power of two
+  const unsigned c = __builtin_bit_cast(unsigned, v + 8388608.f) & 0xffffu;                   // RNE to an integer in the mantissa
+  return !(__builtin_fabsf(theta) < __builtin_inff()) ? TAPE16_NONFINITE : (c == TAPE16_NONFINITE ? (v < 65535.f ? 0xfffeu : 0u) : c);
 }
 #define LDS_FENCE() asm volatile("" ::: "memory")
 #ifndef FENERF_WAVE_HALF_COPIES

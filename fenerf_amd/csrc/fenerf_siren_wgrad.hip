@@ -144,7 +144,7 @@ __device__ __forceinline__ void stage_tape16_sin(const uint4 (&v)[Dump16<H>::PER
     const unsigned w[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      const float th = (float)((t & 1) ? (w[t >> 1] >> 16) : (w[t >> 1] & 0xffffu)) * (1.f / 65536.f);
+      const float th = tape16_phase((t & 1) ? (w[t >> 1] >> 16) : (w[t >> 1] & 0xffffu));
       dst[dump16_feature(nb, g, t) * WG_LD + 16 * odd + n] = sin_rev_reduced(th);
     }
   }
@@ -593,9 +593,8 @@ __global__ __launch_bounds__(NW * 64, 1) void siren_wgrad_sq_bf16_kernel(WgradPa
       const int hs = tid + NW * 64 * q, s16 = hs >> 1, rt = hs & 1;
       const int nb = s16 >> 7, odd = (s16 >> 6) & 1, n = s16 & 15, g = (s16 >> 4) & 3;
       const unsigned w0 = vb16[q].x, w1 = vb16[q].y;
-      const float k = 1.f / 65536.f;
-      const float x[4] = {sin_rev_reduced((float)(w0 & 0xffffu) * k), sin_rev_reduced((float)(w0 >> 16) * k),
-                          sin_rev_reduced((float)(w1 & 0xffffu) * k), sin_rev_reduced((float)(w1 >> 16) * k)};
+      const float x[4] = {sin_rev_reduced(tape16_phase(w0 & 0xffffu)), sin_rev_reduced(tape16_phase(w0 >> 16)),
+                          sin_rev_reduced(tape16_phase(w1 & 0xffffu)), sin_rev_reduced(tape16_phase(w1 >> 16))};
       stage_split4(reinterpret_cast<unsigned short*>(dst + H * WG_LD + dump16_feature(nb, g, 4 * rt) * WG_LD) + 16 * odd + n, x);
     } else {
       const float4 b = vb[q];

@@ -49,9 +49,18 @@ __device__ __forceinline__ float rev_reduce(float t) {
 __device__ __forceinline__ float sin_rev_reduced(float r) { return __builtin_amdgcn_sinf(r); }
 __device__ __forceinline__ float cos_rev_reduced(float r) { return __builtin_amdgcn_cosf(r); }
 
-// sin(2 pi t), cos(2 pi t) for any finite t.  Measured on MI355X: max abs error of v_sin_f32 1.25e-7 -- tighter than a degree-9
+// sin(2 pi t), cos(2 pi t) for any finite t; for t = +-Inf or NaN the instructions return NaN, as torch.sin / torch.cos do (measured
+// through every forward route and the chain kernels: the freq-pinf / coord-pinf / coord-ninf cases of tests/test_gpu_nonfinite.py have the
+// reference's NaN mask, profiles/nonfinite_report.log -- no select needed).  Measured on MI355X: max abs error of v_sin_f32 1.25e-7 -- tighter than a degree-9
 // polynomial evaluated in fp32 (2.1e-7) and one quarter-rate instruction instead of thirteen.
 __device__ __forceinline__ float sin2pi(float t) { return sin_rev_reduced(rev_reduce(t)); }
 __device__ __forceinline__ float cos2pi(float t) { return cos_rev_reduced(rev_reduce(t)); }
+
+// 16-bit tape (fenerf_layout.h): code -> frac(theta) in revolutions.  Code 0xffff is reserved for a phase that is not finite (phase_u16,
+// fenerf_siren_f16w.hip): it decodes to NaN, so an activation or cosine recomputed from the tape is the NaN the forward computed.
+constexpr unsigned TAPE16_NONFINITE = 0xffffu;
+__device__ __forceinline__ float tape16_phase(unsigned code) {
+  return code == TAPE16_NONFINITE ? __builtin_nanf("") : (float)code * (1.f / 65536.f);
+}
 
 }  // namespace fenerf

@@ -285,7 +285,7 @@ class SparseHierarchicalRenderFunction(torch.autograd.Function):
         origins, dirs, zc, z_f, coarse, fine, noise_f, fg, pg, fa, pa, *params = ctx.saved_tensors
         d_f, d_c = native.composite_backward(g_rgb.contiguous().float().reshape(B * R, nat.C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc,
                                              noise=noise_f if noise_f.numel() else None)
-        return _sparse_siren_backward(ctx, module, nat, need, B, R, N, 2, d_c, d_f, zc, z_f, origins, dirs, (fg, pg, fa, pa), params)
+        return _sparse_siren_backward(ctx, module, nat, need, B, R, N, 2, d_c, d_f, zc, z_f, origins, dirs, (fg, pg, fa, pa), params, g_rgb)
 
 
 def _record_bound(ctx, opts, sig, noise, B, R):
@@ -305,7 +305,7 @@ def _record_bound(ctx, opts, sig, noise, B, R):
         ctx.cap_host, ctx.cap_ready = None, None
 
 
-def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc, z_f, origins, dirs, film, params):
+def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc, z_f, origins, dirs, film, params, g_rgb):
     """The SIREN part of a sparse backward: d_c (/ d_f) [B*R, N, C] = gradients wrt the outputs of the pass(es) -> the autograd node's
     return tuple (10 Nones, four FiLM gradients, parameter gradients).  passes = 2: coarse | fine; 1: d_f = z_f = None."""
     fg, pg, fa, pa = film
@@ -356,7 +356,14 @@ def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc
     # (a count above its bound would mean the bound's argument is wrong: checked without waiting, reported by the next backward)
     if rows is not None:
         d_grid = rows.reduce(nat)
-    SparseHierarchicalRenderFunction._check_overflow(flags[0] if whole else torch.stack(flags).max())
+    # A non-finite UPSTREAM gradient makes every row of its ray non-zero (0 * NaN), clamped samples included -- more rows than the
+    # forward's bound, which knows the densities only.  That is no error of the bound: the reference's gradients of such a step are
+    # non-finite too (a GradScaler skips it).  So the flag is raised only while the upstream gradient is finite; otherwise the rows that
+    # were dropped are made up for by a NaN added to every gradient this node returns (all on the device, nothing waits).
+    overflowed = (flags[0] if whole else torch.stack(flags).max()) != 0
+    g_ok = torch.isfinite(g_rgb).all()
+    SparseHierarchicalRenderFunction._check_overflow(overflowed & g_ok)
+    poison = torch.where(overflowed & ~g_ok, float("nan"), 0.0)
     SparseHierarchicalRenderFunction.last_kept = (kept[0] if whole else torch.stack(kept).sum(), S * B)            # for reports (a device scalar: read it after the step)
     SparseHierarchicalRenderFunction.last_groups = [(list(g), c) for g, c in groups]
     if whole:
@@ -364,7 +371,9 @@ def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc
     else:       # rows back into image order
         film_g = [torch.cat([rows[i] for rows in film_rows], 0).index_select(0, torch.argsort(perm)) for i in range(len(_siren_autograd.FILM_KEYS))]
     r = {**(total or {}), **dict(zip(_siren_autograd.FILM_KEYS, film_g))}         # the groups' summed weight gradients, every image's FiLM rows
-    return (None,) * 10 + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, d_grid_cl=d_grid)
+    grads = _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, d_grid_cl=d_grid)
+    torch._foreach_add_([t for t in grads if t is not None], poison)
+    return (None,) * 10 + grads
 
 
 class SparseSinglePassRenderFunction(torch.autograd.Function):
@@ -397,7 +406,7 @@ class SparseSinglePassRenderFunction(torch.autograd.Function):
         origins, dirs, zc, rows, noise_f, fg, pg, fa, pa, *params = ctx.saved_tensors
         C = nat.C
         d = native.composite_backward(g_rgb.contiguous().float().reshape(B * R, C - 1), rows, zc, opts, noise=noise_f if noise_f.numel() else None)
-        return _sparse_siren_backward(ctx, module, nat, ctx.needs_input_grad, B, R, N, 1, d, None, zc, None, origins, dirs, (fg, pg, fa, pa), params)
+        return _sparse_siren_backward(ctx, module, nat, ctx.needs_input_grad, B, R, N, 1, d, None, zc, None, origins, dirs, (fg, pg, fa, pa), params, g_rgb)
 
 
 # `siren.sparse_backward = "auto"`: the sparse node while it pays, the dense node otherwise.  What the sparse backward costs is set by the

@@ -13,6 +13,33 @@
  *   - all randomness (stratified jitter, importance-sampling u, sigma noise, camera pose) is drawn by the
  *     caller and passed in: the library is deterministic.
  *   - a FenerfModel is immutable after create/update and may be used from several threads/streams.
+ *
+ * Non-finite values.  No entry point validates its inputs; NaN and +-Inf go through the arithmetic as they go through the
+ * reference's torch ops (tests/test_gpu_nonfinite.py against oracles pinned to the reference, tests/test_nonfinite_cpu.py):
+ *   - addresses never depend on a loaded VALUE in a way a NaN / Inf can steer: the grid gather / scatter converts a corner to a voxel
+ *     index only behind `0 <= corner <= size - 1`, which is false for NaN and +-Inf (such a point samples 0, as F.grid_sample does);
+ *     searchsorted is a count of K + 1 comparisons, so 0 <= below, above <= K; the merge's ranks are a permutation of 0 .. 2N-1 for any
+ *     depths (total order: ascending, NaN after +Inf, equal depths and NaNs by source index -- torch.sort on the CPU); the sparse
+ *     selection's slots are popcounts bounded by `cap`.
+ *   - fenerf_composite / fenerf_merge_composite / fenerf_render_forward / fenerf_composite_backward: a NaN density, noise draw or depth
+ *     makes the ray's later weights, weights_sum, depth and pixel NaN (relu and softplus alike: F.relu(NaN) = NaN); +Inf density is an
+ *     opaque sample (finite ray), -Inf an empty one; a NaN colour reaches its channel even at weight 0 (0 * NaN).  Other rays are
+ *     untouched, bit for bit.  The backward selects a zero at a relu-clamped sample, as autograd does: a non-finite upstream
+ *     gradient or transmittance does not pass through it.
+ *   - fenerf_resample / fenerf_sample_pdf: a NaN weight makes every sample of that ray NaN (the reference's answer), no other ray's.
+ *   - fenerf_siren_forward* / fenerf_render_*: a non-finite coordinate, view direction, FiLM parameter, weight or grid value reaches
+ *     exactly the outputs it reaches in the reference (the point's row; rgb only for a view direction or a grid channel; the image for a
+ *     FiLM parameter); sin / cos of +-Inf are NaN.  With a feature grid, the reference's result for an Inf COORDINATE is undefined
+ *     (float -> int); here the point samples 0 from the grid and its row is NaN.
+ *   - backward: a non-finite upstream gradient or a NaN made by the forward reaches the gradients it reaches under torch autograd, at
+ *     every tape format (the 16-bit tape reserves code 0xffff for a non-finite phase); the deterministic grid gradient has NaN at
+ *     exactly the voxel-channels non-finite rows touch, the atomic one at least there.  With an Inf (not NaN) the KIND may differ
+ *     (NaN for Inf, e.g. inf - inf in a split product) and a few more elements may be non-finite than in the reference.
+ *   - host / device packing keep a NaN weight a NaN in every half (bf16 rounding by integer add carried 0x7fffffff into -0 before).
+ *   - fenerf_mapping_forward / _backward, fenerf_label_head_backward: the mask of the PyTorch ops / fp64 autograd, element for element.
+ *   - the sparse backward of the Python package: a non-finite upstream gradient may keep more rows than its buffer bound; that is not an
+ *     overflow error -- every gradient of that step then carries a NaN.
+ *   Not covered by tests yet: per-point-modulated and one-launch local kernels, input gradients, the FiLM-only inversion route.
  */
 #ifndef FENERF_H_
 #define FENERF_H_

@@ -214,12 +214,14 @@ def sample_from_3dgrid(coords, grid):
                 wy = (iy - y0) if dy else (y0 + 1 - iy)
                 wz = (iz - z0) if dz else (z0 + 1 - iz)
                 w = (wx * wy * wz).astype(dt)
+                # a NaN / Inf coordinate fails every comparison: no corner is in bounds and the sample is 0, as F.grid_sample returns it
+                # (its weight is SELECTED away, not multiplied by 0; and no NaN is ever converted to an index)
                 ok = (xi >= 0) & (xi <= W - 1) & (yi >= 0) & (yi <= Hh - 1) & (zi >= 0) & (zi <= D - 1)
-                xc = np.clip(xi, 0, W - 1).astype(np.int64)
-                yc = np.clip(yi, 0, Hh - 1).astype(np.int64)
-                zc = np.clip(zi, 0, D - 1).astype(np.int64)
+                xc = np.where(ok, xi, 0).astype(np.int64)
+                yc = np.where(ok, yi, 0).astype(np.int64)
+                zc = np.where(ok, zi, 0).astype(np.int64)
                 vals = g[:, zc, yc, xc]  # [C,B,P]
-                out += (np.moveaxis(vals, 0, -1) * (w * ok)[..., None]).astype(dt)
+                out += np.where(ok[..., None], np.moveaxis(vals, 0, -1) * w[..., None], 0).astype(dt)
     return out
 
 

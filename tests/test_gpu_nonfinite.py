@@ -1,0 +1,901 @@
+"""NaN / Inf propagation of the native kernels against the reference's semantics (include/fenerf.h "Non-finite values").
+
+Every case injects ONE non-finite value into the ordinary inputs of a neighbouring finite test and knows, from the structure of the
+operation, the dependency set D of that value (a point's row, a ray, an image, an output channel, everything).  The reference mask
+R (a subset of D) comes from the oracles, which tests/test_nonfinite_cpu.py pins to the reference's own answers.  Asserted per case:
+
+  containment    outside D the native result is finite and within the bound the finite test of that operation asserts -- and, where the
+                 kernel's rows are independent, bit for bit what the same call returns without the injection;
+  no swallowing  on every element of R the native result is non-finite (NaN or Inf: f16x3 splits an Inf into inf and inf - inf);
+  converse       for a NaN injection, D \\ R is finite and within the bound too.  For an Inf injection the count of non-finite native
+                 elements on D \\ R is printed ([nonfinite] lines; INTEGRATION.md lists the cases where it is not zero).
+
+Nothing here depends on a fault: include/fenerf.h states why no loaded value can move an address (the audit this file presupposes)."""
+import contextlib
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from fenerf_amd import _lib, native, procedural as proc
+from fenerf_amd import grid_det_emulation as E
+from fenerf_amd.generators import volumetric_rendering as VR
+from fenerf_amd.siren import siren as S
+from oracle import fenerf_oracle as O
+from oracle import fenerf_oracle_grad as OG
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+VALUES = {"nan": np.nan, "pinf": np.inf, "ninf": -np.inf}
+
+
+def T(a):
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32, device=DEV)
+
+
+def N_(t):
+    return t.detach().cpu().numpy()
+
+
+@contextlib.contextmanager
+def quiet():
+    with np.errstate(all="ignore"):
+        yield
+
+
+FIGURES = {}        # case -> its figures summed over the output tensors of the case; one [nonfinite] line per case when the test ends
+
+
+def note(case, **fig):
+    case = case.split("|")[0]          # "case|detail": the detail goes into assertion messages only
+    tot = FIGURES.setdefault(case, dict(D=0, R=0, inside=0, outside=0, extra=0))
+    for k, v in fig.items():
+        tot[k] += v
+
+
+@pytest.fixture(autouse=True)
+def report_lines():
+    FIGURES.clear()
+    yield
+    for case, f in FIGURES.items():
+        print(f"[nonfinite] {case}: |D| {f['D']} |R| {f['R']} native non-finite inside D {f['inside']} outside D {f['outside']} on D\\R {f['extra']}")
+
+
+def check(case, name, got, ref, D, bound, nan_injection, clean=None):
+    """got / ref / D (bool) of one output tensor; bound: max |got - ref| on finite elements (a float, or an array that broadcasts);
+    clean: the native result of the same call without the injection (rows outside D must be those bits).  -> the figures, also summed into FIGURES"""
+    got, ref, D = np.asarray(got), np.asarray(ref), np.broadcast_to(np.asarray(D), np.shape(got))
+    assert got.shape == ref.shape, (case, name, got.shape, ref.shape)
+    R = ~np.isfinite(ref)
+    assert not (R & ~D).any(), (case, name, "the reference mask leaves the dependency set: D is wrong")
+    bad = ~np.isfinite(got)
+    fig = dict(D=int(D.sum()), R=int(R.sum()), inside=int((bad & D).sum()), outside=int((bad & ~D).sum()), extra=int((bad & D & ~R).sum()))
+    note(case, **fig)
+    err = np.abs(np.where(bad | R, 0, got - np.where(R, 0, ref)))
+    bound = np.broadcast_to(np.asarray(bound, dtype=np.float64), got.shape)
+    assert fig["outside"] == 0, (case, name, "a non-finite value leaked out of D", np.argwhere(bad & ~D)[:4].tolist())
+    assert (err[~D] <= bound[~D]).all(), (case, name, "outside D", float(err[~D].max()))
+    if clean is not None:
+        clean = np.asarray(clean)
+        assert np.array_equal(got[~D], clean[~D]), (case, name, "outside D the call must return what it returns without the injection")
+    assert bad[R].all(), (case, name, "swallowed", int((R & ~bad).sum()), "of", fig["R"], np.argwhere(R & ~bad)[:4].tolist())
+    if nan_injection:
+        assert fig["extra"] == 0, (case, name, "non-finite where the reference is finite", np.argwhere(bad & D & ~R)[:4].tolist())
+        keep = D & ~R
+        assert (err[keep] <= bound[keep]).all(), (case, name, "D \\ R", float(err[keep].max()))
+    return fig
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# composite (fenerf_composite): D = the ray.  Inputs and bounds of test_gpu_parity.py::test_composite_max_samples_and_empty
+# ---------------------------------------------------------------------------------------------------------------------------------------
+RAY = 4          # of 9
+
+
+def _composite_inputs(M, seed=5):
+    rng = np.random.default_rng(seed)
+    rs = rng.normal(size=(1, 9, M, 22)).astype(np.float32)
+    rs[..., -1] *= 30
+    rs[0, :, 5, -1] = -5.0                                        # relu clamps sample 5 of every ray: an exactly-zero weight
+    z = np.sort(rng.uniform(0.88, 1.12, (1, 9, M, 1)).astype(np.float32), axis=2)
+    noise = rng.normal(size=(1, 9, M, 1)).astype(np.float32)
+    return rs, z, noise
+
+
+COMPOSITE_CASES = {
+    # id: (clamp, noise_std, composite kwargs, (array, sample, channel), value)
+    "relu-density-nan": ("relu", 0.0, {}, ("rs", "mid", -1), "nan"),
+    "relu-density-pinf": ("relu", 0.0, {}, ("rs", "mid", -1), "pinf"),
+    "relu-density-ninf": ("relu", 0.0, {}, ("rs", "mid", -1), "ninf"),
+    "softplus-density-nan": ("softplus", 0.0, {}, ("rs", "mid", -1), "nan"),
+    "softplus-density-pinf": ("softplus", 0.0, {}, ("rs", "mid", -1), "pinf"),
+    "softplus-density-ninf": ("softplus", 0.0, {}, ("rs", "mid", -1), "ninf"),
+    "relu-last_back-density-nan": ("relu", 0.0, dict(last_back=True), ("rs", "mid", -1), "nan"),
+    "relu-white_back-density-nan": ("relu", 0.0, dict(white_back=True), ("rs", "mid", -1), "nan"),
+    "relu-fill-density-nan": ("relu", 0.0, dict(fill_mode="seg_padding_background", fill_color="grey"), ("rs", "mid", -1), "nan"),
+    "relu-fill-density-pinf": ("relu", 0.0, dict(fill_mode="seg_padding_background", fill_color="grey"), ("rs", "mid", -1), "pinf"),
+    "relu-colour-nan-at-zero-weight": ("relu", 0.0, {}, ("rs", 5, 3), "nan"),
+    "relu-colour-pinf-at-zero-weight": ("relu", 0.0, {}, ("rs", 5, 3), "pinf"),
+    "relu-noise-nan": ("relu", 0.5, {}, ("noise", "mid", 0), "nan"),
+    "softplus-noise-nan-last_back": ("softplus", 0.5, dict(last_back=True), ("noise", "mid", 0), "nan"),
+    "relu-noise-pinf": ("relu", 0.5, {}, ("noise", "mid", 0), "pinf"),
+    "relu-depth-nan": ("relu", 0.0, {}, ("z", "mid", 0), "nan"),
+    "relu-depth-pinf-last": ("relu", 0.0, {}, ("z", "last", 0), "pinf"),
+}
+
+
+@pytest.mark.parametrize("M", [12, 200])
+@pytest.mark.parametrize("case", list(COMPOSITE_CASES))
+def test_composite_nonfinite(case, M):
+    """relu-density-nan is the in-file demonstration: before the clamp of fenerf_composite_ray.h handed a NaN on (fmaxf(NaN, 0) = 0) the
+    native ray came out finite -- `'rgb', 'swallowed', 21, 'of', 21` (profiles/nonfinite_parent_relu_case.log); now all 21 channels
+    are NaN -- where F.relu makes the reference's pixel NaN."""
+    clamp, noise_std, kw, (what, k, ch), v = COMPOSITE_CASES[case]
+    rs, z, noise = _composite_inputs(M)
+    k = {"mid": (2 * M) // 3, "last": M - 1}.get(k, k)        # M = 200: in the third 64-sample slot, behind two carried products
+    clean_in = dict(rs=rs.copy(), z=z.copy(), noise=noise.copy())
+    {"rs": rs, "z": z, "noise": noise}[what][0, RAY, k, ch] = VALUES[v]
+    opts = _lib.composite_opts(clamp, noise_std, **kw)
+    run = lambda a: [N_(t) for t in native.composite(T(a["rs"]), T(a["z"][..., 0]), T(a["noise"][..., 0]) if noise_std else None, opts)]
+    clean = run(clean_in)
+    got = run(dict(rs=rs, z=z, noise=noise))
+    with quiet():
+        r_rgb, r_depth, r_w = O.fancy_integration(rs, z, noise=noise if noise_std else None, noise_std=noise_std, clamp_mode=clamp, **kw)
+        r_ws = np.sum(_weights_before_last_back(rs, z, noise if noise_std else None, noise_std, clamp), -1)
+    D = np.zeros((1, 9), bool); D[0, RAY] = True
+    nan = v == "nan"
+    tag = f"composite[{case}-M{M}]"
+    check(tag, "rgb", got[0], r_rgb, D[..., None], 2e-5, nan, clean[0])
+    check(tag, "depth", got[1], r_depth[..., 0], D, 2e-5, nan, clean[1])
+    check(tag, "weights", got[2], r_w[..., 0], D[..., None], 1e-5, nan, clean[2])
+    check(tag, "weights_sum", got[3], r_ws, D, 1e-5, nan, clean[3])
+    if nan and not (what == "rs" and ch != -1):
+        # a NaN density / noise / depth: a NaN pixel, never a plausible one (a fill mode prepends its background channel: 0, as the reference's)
+        assert np.isnan(got[0][0, RAY, -21:]).all() and np.isnan(got[3][0, RAY])
+
+
+def _weights_before_last_back(rs, z, noise, noise_std, clamp):
+    """weights_sum as the kernel returns it: taken before the last_back adjustment (volumetric_rendering.py:38-41)"""
+    return O.fancy_integration(rs, z, noise=noise, noise_std=noise_std, clamp_mode=clamp)[2][..., 0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# merge + composite (fenerf_merge_composite): the rank sort is a total order, NaN last.  Inputs of test_more_than_128_samples_per_pass
+# ---------------------------------------------------------------------------------------------------------------------------------------
+MERGE_CASES = {
+    # id: [(array, sample, value)]
+    "fine-depth-nan": [("zf", 3, "nan")],
+    "coarse-depth-nan": [("zc", 7, "nan")],
+    "two-nans-and-infs": [("zf", 1, "nan"), ("zc", 4, "nan"), ("zf", 5, "pinf"), ("zc", 0, "ninf")],
+    "all-fine-depths-nan": [("zf", slice(None), "nan")],
+    "fine-depth-pinf": [("zf", 0, "pinf")],
+    "fine-density-nan": [("fine", 6, "nan")],
+    "coarse-density-pinf": [("coarse", 2, "pinf")],
+}
+
+
+def _merge_inputs(N, seed):
+    rng = np.random.default_rng(seed)
+    fine = rng.normal(size=(9, N, 22)).astype(np.float32); coarse = rng.normal(size=(9, N, 22)).astype(np.float32)
+    fine[..., -1] *= 30; coarse[..., -1] *= 30
+    zc = np.sort(rng.uniform(0.88, 1.12, (9, N)).astype(np.float32), axis=1)
+    zf = np.sort(rng.uniform(0.88, 1.12, (9, N)).astype(np.float32), axis=1)
+    zf[:, 8] = zc[:, 7]                                              # a tie between the passes
+    return dict(fine=fine, coarse=coarse, zf=zf, zc=zc)
+
+
+@pytest.mark.parametrize("N", [12, 100])
+@pytest.mark.parametrize("case", list(MERGE_CASES))
+def test_merge_composite_nonfinite(case, N):
+    a = _merge_inputs(N, 100 + N)
+    clean_in = {k: v.copy() for k, v in a.items()}
+    for what, k, v in MERGE_CASES[case]:
+        if what in ("zf", "zc"):
+            a[what][RAY, k] = VALUES[v]
+        else:
+            a[what][RAY, k, -1] = VALUES[v]
+    opts = _lib.composite_opts("relu")
+    run = lambda x: [N_(t) for t in native.merge_composite(T(x["fine"]), T(x["coarse"]), T(x["zf"]), T(x["zc"]), None, opts)]
+    clean = run(clean_in)
+    got = run(a)
+    with quiet():
+        ao, az = O.merge_sorted(a["fine"][None], a["coarse"][None], a["zf"][None, ..., None], a["zc"][None, ..., None])
+        r_rgb, r_depth, r_w = O.fancy_integration(ao, az, clamp_mode="relu")
+    D = np.zeros(9, bool); D[RAY] = True
+    nan = all(v == "nan" for _, _, v in MERGE_CASES[case])
+    tag = f"merge[{case}-N{N}]"
+    # the sort is exact, for any depths: ascending, NaN after +Inf, ties and NaNs in input order (torch.sort, generators.py:510)
+    assert np.array_equal(got[4], az[0, ..., 0], equal_nan=True), (tag, "sorted depths", got[4][RAY], az[0, RAY, :, 0])
+    check(tag, "rgb", got[0], r_rgb[0], D[:, None], 2e-5, nan, clean[0])
+    check(tag, "depth", got[1], r_depth[0, ..., 0], D, 2e-5, nan, clean[1])
+    check(tag, "weights", got[2], r_w[0, ..., 0], D[:, None], 1e-5, nan, clean[2])
+    check(tag, "weights_sum", got[3], r_w[0, ..., 0].sum(-1), D, 1e-5, nan, clean[3])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# resample / sample_pdf (stand-alone; the fused copy runs inside the render below).  Inputs and bounds of test_more_than_128_samples_per_pass
+# ---------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", [12, 200])
+@pytest.mark.parametrize("what,v", [("weight", "nan"), ("weight", "pinf"), ("depth", "nan"), ("draw", "nan")])
+def test_resample_and_sample_pdf_nonfinite(what, v, N):
+    """A NaN coarse weight makes the whole cdf of the ray NaN: every fine depth of that ray is NaN, as in the reference (matched, not
+    redefined), and no other ray's.  A NaN draw or depth touches the samples it feeds."""
+    rng = np.random.default_rng(N)
+    BR = 9
+    z_c = np.sort(rng.uniform(0.88, 1.12, (BR, N)).astype(np.float32), axis=1)
+    w_c = rng.random((BR, N)).astype(np.float32) ** 4
+    u = rng.uniform(0.01, 1.0, (BR, N)).astype(np.float32)
+    bins = np.sort(rng.uniform(0.88, 1.12, (BR, N)).astype(np.float32), axis=1)
+    wk = rng.random((BR, N - 1)).astype(np.float32) ** 4
+    clean = N_(native.resample(T(z_c), T(w_c), T(u))), N_(native.sample_pdf(T(bins), T(wk), T(u)))
+    k = N // 2
+    if what == "weight":
+        w_c[RAY, k] = wk[RAY, k] = VALUES[v]
+    elif what == "depth":
+        z_c[RAY, k] = bins[RAY, k] = VALUES[v]
+    else:
+        u[RAY, k] = VALUES[v]
+    zf = N_(native.resample(T(z_c), T(w_c), T(u)))
+    s = N_(native.sample_pdf(T(bins), T(wk), T(u)))
+    with quiet():
+        r_zf = O.fine_z_from_coarse(w_c.reshape(1, BR, N, 1), z_c.reshape(1, BR, N, 1), u).reshape(BR, N)
+        r_s = O.sample_pdf(bins, wk, u)
+    D = np.zeros((BR, 1), bool); D[RAY] = True
+    tag = f"resample[{what}-{v}-N{N}]"
+    f1 = check(tag, "resample", zf, r_zf, D, 6e-5, v == "nan", clean[0])
+    f2 = check(tag, "sample_pdf", s, r_s, D, 6e-5, v == "nan", clean[1])
+    if what == "weight" and v == "nan":
+        assert f1["inside"] == N and f2["inside"] == N          # the reference's answer: the whole ray
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the hierarchical render, four launches and one (render_fusion("force")): D = the ray, through the coarse composite, the fused
+# resampling, the fine SIREN pass on NaN points (grid gather behind its bounds test) and the merge of NaN depths
+# ---------------------------------------------------------------------------------------------------------------------------------------
+RENDER_CASES = {
+    # id: (clamp, (array, index into the ray's samples), value)
+    "relu-coarse-noise-nan": ("relu", ("nc", 3), "nan"),
+    "softplus-coarse-noise-nan": ("softplus", ("nc", 3), "nan"),
+    "relu-final-noise-nan": ("relu", ("nf", 7), "nan"),
+    "relu-coarse-depth-nan": ("relu", ("z", 2), "nan"),
+    "relu-draw-nan": ("relu", ("u", 4), "nan"),
+    "relu-ray-origin-nan": ("relu", ("o", 1), "nan"),
+    "relu-coarse-noise-pinf": ("relu", ("nc", 3), "pinf"),
+    "relu-final-noise-ninf": ("relu", ("nf", 7), "ninf"),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _render_model(precision):
+    spec = proc.model_spec("texture", hidden_dim=32, grid_size=8, z_dim=8)
+    sd = proc.make_state_dict(spec, seed=6, sigma_gain=60.0, with_mapping=False)
+    return native.NativeModel(sd, spec, DEV, precision), spec, sd
+
+
+def _oracle_render(sd, spec, film, o, d, z, u, nc, nf, clamp, noise_std, **kw):
+    B, R, N = z.shape
+    args = (film["freq_geo"], film["phase_geo"], film["freq_app"], film["phase_app"])
+    dexp = np.broadcast_to(d[:, :, None, :], (B, R, N, 3)).reshape(B, -1, 3)
+    with quiet():
+        coarse = O.siren_forward(sd, spec, (o[:, :, None, :] + d[:, :, None, :] * z[..., None]).reshape(B, -1, 3), dexp, *args).reshape(B, R, N, -1)
+        _, _, cw = O.fancy_integration(coarse, z[..., None], noise=nc.reshape(B, R, N, 1), noise_std=noise_std, clamp_mode=clamp)
+        zf = O.fine_z_from_coarse(cw, z[..., None], u)
+        fine = O.siren_forward(sd, spec, (o[:, :, None, :] + d[:, :, None, :] * zf).reshape(B, -1, 3), dexp, *args).reshape(B, R, N, -1)
+        ao, az = O.merge_sorted(fine, coarse, zf, z[..., None])
+        return O.fancy_integration(ao, az, noise=nf.reshape(B, R, 2 * N, 1), noise_std=noise_std, clamp_mode=clamp, **kw)
+
+
+@pytest.mark.parametrize("route", ["four-launch", "one-launch"])
+@pytest.mark.parametrize("case", list(RENDER_CASES))
+def test_hierarchical_render_nonfinite(case, route):
+    """Shape and model of test_one_launch_render_equals_the_four_launch_render[tiny_texture_fill_noise]; the bound on untouched rays is the
+    1e-3 of the render-vs-oracle tests (test_more_than_128_samples_per_pass, smoke()) -- and they are bit for bit the clean render."""
+    clamp, (what, k), v = RENDER_CASES[case]
+    nat, spec, sd = _render_model("f16x3")
+    B, S_, N = 2, 8, 6
+    R = S_ * S_
+    film = proc.film_params(spec, B, seed=6)
+    tf = tuple(T(film[x]) for x in ("freq_geo", "phase_geo", "freq_app", "phase_app"))
+    torch.manual_seed(12)
+    o, d, z, _, _ = VR.sample_rays(B, N, DEV, 12, (S_, S_), 0.88, 1.12, 0.3, 0.155, np.pi / 2, np.pi / 2, "gaussian")
+    a = dict(o=N_(o), d=N_(d), z=N_(z), u=N_(torch.rand((B * R, N), device=DEV)), nc=N_(torch.randn((B * R, N), device=DEV)),
+             nf=N_(torch.randn((B * R, 2 * N), device=DEV)))
+    img, ray = 1, 21
+    opts = _lib.composite_opts(clamp, 0.3, last_back=True)
+
+    def run(x):
+        with native.render_fusion("force" if route == "one-launch" else "off"), native.phase_timing() as t:
+            out = nat.render(T(x["o"]), T(x["d"]), T(x["z"]), T(x["u"]), T(x["nc"]), T(x["nf"]), *tf, opts, hierarchical=True, want_weights=True,
+                             want_wsum=True)
+        assert ("render_fused" in t.calls) == (route == "one-launch"), t.calls
+        return [N_(t_) for t_ in out]
+    clean = run(a)
+    b = {k_: v_.copy() for k_, v_ in a.items()}
+    if what in ("o", "z"):
+        b[what][img, ray, k] = VALUES[v]
+    else:
+        b[what][img * R + ray, k] = VALUES[v]
+    got = run(b)
+    r_rgb, r_depth, r_w = _oracle_render(sd, spec, film, b["o"], b["d"], b["z"], b["u"], b["nc"], b["nf"], clamp, 0.3, last_back=True)
+    D = np.zeros((B, R), bool); D[img, ray] = True
+    nan = v == "nan"
+    tag = f"render[{case}-{route}]"
+    check(tag, "rgb", got[0], r_rgb, D[..., None], 1e-3, nan, clean[0])
+    check(tag, "depth", got[1], r_depth[..., 0], D, 1e-3, nan, clean[1])
+    # weights: only the mask (a resampled depth in a neighbouring bin reorders a finite ray's weights; the pixel bounds above hold anyway)
+    check(tag, "weights", got[2], r_w[..., 0], D[..., None], np.inf, nan, clean[2])
+    with quiet():       # weights_sum is taken before the last_back adjustment (volumetric_rendering.py:38-41)
+        r_ws = _oracle_render(sd, spec, film, b["o"], b["d"], b["z"], b["u"], b["nc"], b["nf"], clamp, 0.3)[2][..., 0].sum(-1)
+    check(tag, "weights_sum", got[3], r_ws, D, 1e-3, nan, clean[3])
+    if nan:
+        assert np.isnan(got[0][img, ray]).all(), (tag, "the rendered pixel of the injected ray is NaN in every channel, as the reference's")
+
+
+def test_ray_setup_nan_camera_angle():
+    """torch.clamp hands a NaN pitch on (volumetric_rendering.py:220-228), so the reference's camera origin and rays of that image are
+    NaN; fminf(fmaxf(NaN, lo), hi) made it lo -- a valid camera at the pole.  D = the image."""
+    B, S_, N = 2, 4, 6
+    rng = np.random.default_rng(2)
+    u = rng.random((B, S_ * S_, N)).astype(np.float32)
+    theta, phi = np.float32([1.3, 1.7]), np.float32([1.5, 1.6])
+    z_cam = -1.0 / np.tan(np.deg2rad(12.0) / 2)
+    run = lambda ph: [N_(t) for t in native.ray_setup(B, S_, N, z_cam, 0.88, 1.12, T(u), T(theta), T(ph))]
+    clean = run(phi)
+    assert torch.isnan(torch.clamp(torch.tensor(float("nan")), 1e-5, np.pi - 1e-5))          # the semantics asserted below
+    phi2 = phi.copy(); phi2[1] = np.nan
+    o, d, z, pitch, yaw = run(phi2)
+    for name, a, c in (("origins", o, clean[0]), ("dirs", d, clean[1])):
+        assert np.array_equal(a[0], c[0]) and np.isnan(a[1]).all(), name
+        note("ray_setup[phi-nan]", D=a[1].size, R=a[1].size, inside=int(np.isnan(a[1]).sum()), outside=0, extra=0)
+    assert np.array_equal(z, clean[2]) and np.isnan(pitch[1]).all() and np.array_equal(pitch[0], clean[3][0])      # depths do not depend on the pose
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# composite backward / merge-composite backward vs fp64 autograd (fenerf_oracle_grad), cast to fp32.  D = the ray's rows.
+# Inputs and bound of test_composite_backward_vs_autograd / test_merge_composite_backward_vs_autograd
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _grad_case(BR, N, C, seed, merge):
+    rng = np.random.default_rng(seed)
+    M = 2 * N if merge else N
+    rows = rng.normal(size=(BR, M, C)).astype(np.float32)
+    rows[..., -1] = rng.normal(size=(BR, M)).astype(np.float32) * 6 * (1 + (np.arange(BR) % 5))[:, None]
+    z = np.sort(rng.uniform(0.88, 1.12, (BR, M)).astype(np.float32), -1)
+    if merge:
+        z = rng.permuted(z, axis=-1)
+        z[:, :N] = np.sort(z[:, :N], -1); z[:, N:] = np.sort(z[:, N:], -1)
+    noise = rng.normal(size=(BR, M)).astype(np.float32)
+    g = rng.normal(size=(BR, C - 1)).astype(np.float32)
+    return rows, z, noise, g
+
+
+BACKWARD_CASES = {
+    # id: (array, index below the ray, value)
+    "upstream-nan": ("g", (3,), "nan"),
+    "upstream-pinf": ("g", (3,), "pinf"),
+    "density-nan": ("rows", ("mid", -1), "nan"),
+    "density-pinf": ("rows", ("mid", -1), "pinf"),
+    "colour-nan": ("rows", ("mid", 2), "nan"),
+    "noise-nan": ("noise", ("mid",), "nan"),
+    "depth-nan": ("z", ("mid",), "nan"),
+}
+
+
+def _f32_grad(t):
+    with quiet():
+        return t.grad.numpy().astype(np.float32)
+
+
+@pytest.mark.parametrize("clamp,last_back,white,noise_std", [("relu", False, False, 0.0), ("softplus", True, False, 0.5), ("relu", True, True, 0.3)])
+@pytest.mark.parametrize("N", [24, 150])
+@pytest.mark.parametrize("case", list(BACKWARD_CASES))
+def test_composite_backward_nonfinite(case, N, clamp, last_back, white, noise_std):
+    what, idx, v = BACKWARD_CASES[case]
+    if what == "noise" and noise_std == 0.0:
+        noise_std = 0.25          # a NaN times a zero noise_std is a NaN too, in both; use a case that is not degenerate
+    ray = 5
+    rows, z, noise, g = _grad_case(37, N, 22, 5 + N, False)
+    opts = _lib.composite_opts(clamp, last_back=last_back, white_back=white, noise_std=noise_std)
+    clean = N_(native.composite_backward(T(g), T(rows), T(z), opts, noise=T(noise)))
+    idx = tuple((2 * N) // 3 if i == "mid" else i for i in idx)
+    dict(g=g, rows=rows, noise=noise, z=z)[what][(ray,) + idx] = VALUES[v]
+    got = N_(native.composite_backward(T(g), T(rows), T(z), opts, noise=T(noise)))
+    t64 = lambda a: torch.tensor(a, dtype=torch.float64)
+    r = t64(rows).requires_grad_(True)
+    rgb, _, _ = OG.composite(r, t64(z), t64(noise), noise_std=noise_std, clamp_mode=clamp, last_back=last_back, white_back=white)
+    (rgb * t64(g)).sum().backward()
+    ref = _f32_grad(r)
+    scale = max(1.0, float(np.abs(ref[np.isfinite(ref)]).max()))
+    D = np.zeros((37, 1, 1), bool); D[ray] = True
+    check(f"composite_backward[{case}-N{N}-{clamp}-lb{int(last_back)}-wb{int(white)}-noise{noise_std}]", "d_rows", got, ref, D, 2e-5 * scale, v == "nan", clean)
+
+
+@pytest.mark.parametrize("N", [12, 100])
+@pytest.mark.parametrize("case", list(BACKWARD_CASES) + ["fine-depth-nan", "all-coarse-depths-nan"])
+def test_merge_composite_backward_nonfinite(case, N):
+    """The backward repeats the forward's rank sort and derives the rows it STORES to from it: with NaN depths the ranks must still be a
+    permutation (merge_rank, fenerf_composite_ray.h), so every gradient row of the ray is written exactly once and no other."""
+    ray = 5
+    rows, z, noise, g = _grad_case(29, N, 22, 40 + N, True)
+    opts = _lib.composite_opts("relu", noise_std=0.4)
+    run = lambda: [N_(t) for t in native.composite_backward(T(g), T(rows[:, :N]), T(z[:, :N]), opts, rows_b=T(rows[:, N:]), z_b=T(z[:, N:]),
+                                                            noise=T(noise))]
+    clean = run()
+    if case == "fine-depth-nan":
+        z[ray, 3], v = np.nan, "nan"
+    elif case == "all-coarse-depths-nan":
+        z[ray, N:], v = np.nan, "nan"
+    else:
+        what, idx, v = BACKWARD_CASES[case]
+        idx = tuple((2 * N) // 3 if i == "mid" else i for i in idx)
+        dict(g=g, rows=rows, noise=noise, z=z)[what][(ray,) + idx] = VALUES[v]
+    got = run()
+    t64 = lambda a: torch.tensor(a, dtype=torch.float64)
+    f, c = t64(rows[:, :N]).requires_grad_(True), t64(rows[:, N:]).requires_grad_(True)
+    rgb, _, _ = OG.merge_composite(f, c, t64(z[:, :N]), t64(z[:, N:]), t64(noise), noise_std=0.4, clamp_mode="relu")
+    (rgb * t64(g)).sum().backward()
+    rf, rc = _f32_grad(f), _f32_grad(c)
+    scale = max(1.0, float(np.abs(rf[np.isfinite(rf)]).max()), float(np.abs(rc[np.isfinite(rc)]).max()))
+    D = np.zeros((29, 1, 1), bool); D[ray] = True
+    tag = f"merge_composite_backward[{case}-N{N}]"
+    check(tag, "d_fine", got[0], rf, D, 2e-5 * scale, v == "nan", clean[0])
+    check(tag, "d_coarse", got[1], rc, D, 2e-5 * scale, v == "nan", clean[1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# SIREN forward, no grad: f32 / f16x3 / f16x3c2; texture + grid, baseline, spatial; an instantiated width and a padded one (100).
+# Shapes and bounds of test_siren_backward_vs_autograd's forward check (rgb / labels 1e-4, sigma 2e-4 x sigma_gain): B = 2, P ragged,
+# one injected point in the first 32-point tile (5) and one in the clamped tail tile (P - 3).
+# ---------------------------------------------------------------------------------------------------------------------------------------
+SIREN_MODELS = {"texture-32": ("texture", 32, 5, 75), "texture-100": ("texture", 100, 5, 75), "baseline-64": ("baseline", 64, 0, 70),
+                "spatial-32": ("spatial", 32, 0, 33), "spatial-72": ("spatial", 72, 0, 33)}
+SIREN_INJECTIONS = ["coord-nan", "dir-nan", "coord-pinf", "coord-ninf", "freq-nan", "freq-pinf", "phase-nan", "phase-app-nan",
+                    "trunk-weight-nan", "rgb-head-weight-nan", "voxel-nan"]
+
+
+def _siren_inputs(kind, H, grid, P, B=2):
+    spec = proc.model_spec(kind, hidden_dim=H, grid_size=grid, z_dim=8) if grid else proc.model_spec(kind, hidden_dim=H, z_dim=8)
+    sd = proc.make_state_dict(spec, seed=4, sigma_gain=30.0, with_mapping=False)
+    rng = np.random.default_rng(7)
+    pts = rng.uniform(-0.125, 0.125, (B, P, 3)).astype(np.float32)          # some points leave the grid box: zero padding
+    dirs = rng.normal(size=(B, P, 3)).astype(np.float32)
+    dirs /= np.linalg.norm(dirs, axis=-1, keepdims=True)
+    film = proc.film_params(spec, B, seed=4)
+    if kind == "spatial":
+        film["freq_app"] = proc.normal("film.freq_app", (B, H), 0.4, 4)
+        film["phase_app"] = proc.normal("film.phase_app", (B, H), 0.4, 4)
+    return spec, sd, pts, dirs, film
+
+
+def _oracle_siren(sd, spec, pts, dirs, film, dtype=np.float64):
+    if spec["kind"] == "spatial":
+        args = (np.concatenate([film["freq_geo"], film["freq_app"]], -1), np.concatenate([film["phase_geo"], film["phase_app"]], -1))
+    else:
+        args = (film["freq_geo"], film["phase_geo"], film["freq_app"], film["phase_app"])
+    with quiet():
+        return O.siren_forward(sd, spec, pts, dirs, *args, dtype=dtype)
+
+
+def _siren_bounds(spec, ref):
+    b = np.full(ref.shape, 1e-4)
+    b[..., -1] = 2e-4 * 30
+    return b
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3", "f16x3c2"])
+@pytest.mark.parametrize("model", list(SIREN_MODELS))
+def test_siren_forward_nonfinite(model, precision):
+    kind, H, grid, P = SIREN_MODELS[model]
+    spec, sd, pts, dirs, film = _siren_inputs(kind, H, grid, P)
+    B, Cc = 2, spec["output_dim"]
+    nat = native.NativeModel(sd, spec, DEV, precision)
+    fwd = lambda n, p, d, f: N_(n.siren_forward(T(p), T(d), *(T(f[k]) for k in ("freq_geo", "phase_geo", "freq_app", "phase_app"))))
+    clean = fwd(nat, pts, dirs, film)
+    ref0 = _oracle_siren(sd, spec, pts, dirs, film)
+    assert np.isfinite(clean).all() and (np.abs(clean - ref0) <= _siren_bounds(spec, ref0)).all()
+    rgb = slice(Cc - 4, Cc - 1)
+    for inj in SIREN_INJECTIONS:
+        if inj == "voxel-nan" and not grid:
+            continue
+        nan = not inj.endswith("inf")
+        v = VALUES[inj.rsplit("-", 1)[1]]
+        p2, d2, f2, sd2 = pts.copy(), dirs.copy(), {k: a.copy() for k, a in film.items()}, {k: a.copy() for k, a in sd.items()}
+        D = np.zeros((B, P, Cc), bool)
+        for pt in (5, P - 3):
+            if inj.startswith("coord"):
+                p2[1, pt, 1] = v; D[1, pt] = True
+            elif inj == "dir-nan":
+                d2[1, pt, 0] = v; D[1, pt] = True
+        if inj.startswith("freq"):
+            f2["freq_geo"][1, 2 * H + 3] = v; D[1] = True
+        elif inj == "phase-nan":
+            f2["phase_geo"][1, 5 * H + 1] = v; D[1] = True
+        elif inj == "phase-app-nan":
+            f2["phase_app"][1, 2] = v; D[1] = True
+        elif inj == "trunk-weight-nan":
+            sd2["network.3.layer.weight"][2, 5] = v; D[:] = True
+        elif inj == "rgb-head-weight-nan":
+            sd2["color_layer_linear.0.weight"][1, 4] = v; D[..., Cc - 3] = True
+        elif inj == "voxel-nan":
+            cs = E.corners(pts.reshape(-1, 3), (grid, grid, grid))
+            vox = int(next(idx[ok][0] for ok, idx, _ in cs if ok.any()))          # a voxel that some point touches
+            sd2["spatial_embeddings"].reshape(32, -1)[7, vox] = v                    # [1, C, D, H, W]: channel 7 of it
+            for ok, idx, _ in cs:                                                    # D: the rgb of every point with a corner on it
+                D.reshape(-1, Cc)[ok & (idx == vox), rgb] = True
+        tag = f"siren_forward[{model}-{precision}]|{inj}"
+        if inj in ("trunk-weight-nan", "rgb-head-weight-nan", "voxel-nan"):
+            ref = _oracle_siren(sd2, spec, pts, dirs, film)
+            nat_u = native.NativeModel(sd, spec, DEV, precision)
+            nat_u.update(sd2)                                       # the host packer
+            got = fwd(nat_u, pts, dirs, film)
+            nat_r = native.NativeModel(sd, spec, DEV, precision)    # ... and the device re-pack from resident parameters: the same result
+            nat_r.load_from_device({k: T(a) for k, a in sd2.items()})
+            got_r = fwd(nat_r, pts, dirs, film)
+            assert np.array_equal(np.isfinite(got_r), np.isfinite(got)), (tag, "host pack and device re-pack disagree on the mask")
+            fin = np.isfinite(got)       # test_device_side_repack_matches_host_pack's bound (the device folds the label head in fp32)
+            assert np.abs(got_r[fin] - got[fin]).max(initial=0.0) <= 1e-5 * max(1.0, float(np.abs(got[fin]).max(initial=0.0))), (tag, "host pack vs device re-pack")
+        else:
+            ref = _oracle_siren(sd, spec, p2, d2, f2)
+            got = fwd(nat, p2, d2, f2)
+        if inj in ("coord-pinf", "coord-ninf") and grid:
+            # the reference converts an Inf coordinate to a voxel index (undefined): no parity -- index safety, containment and a
+            # non-finite row of the point itself
+            assert np.isfinite(got[~D]).all() and np.array_equal(got[~D], clean[~D]) and not np.isfinite(got[D]).any(), tag
+            note(tag + " (no reference: R = D)", D=int(D.sum()), R=int(D.sum()), inside=int((~np.isfinite(got[D])).sum()), outside=0, extra=0)
+            continue
+        check(tag, "out", got, ref, D, _siren_bounds(spec, ref), nan, clean)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# SIREN backward through the autograd nodes (forward-save, chain, weight-gradient kernels) vs fp64 autograd cast to fp32: a non-finite
+# upstream gradient at one point of image 1, and a NaN made in the forward (NaN FiLM phase of image 1) and carried by the tape.
+# Shapes and the 2e-4 bound of test_siren_backward_vs_autograd.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _siren_module(kind, H, grid, precision, sigma_gain=30.0):
+    spec = proc.model_spec(kind, hidden_dim=H, grid_size=grid, z_dim=8)
+    sd = proc.make_state_dict(spec, seed=4, sigma_gain=sigma_gain, with_mapping=False)
+    if kind == "spatial":
+        mod = S.SPATIALSIRENBASELINE(hidden_dim=H, z_dim=8)
+    else:
+        cls = {"texture": S.TextureEmbeddingPiGAN128SEMANTICDISENTANGLE, "baseline": S.SIRENBASELINESEMANTICDISENTANGLE}[kind]
+        mod = cls(hidden_dim=H, z_geo_dim=8, z_app_dim=8, output_dim=22)
+    tsd = {k: torch.from_numpy(v) for k, v in sd.items()}
+    if "spatial_embeddings" in tsd:
+        mod.spatial_embeddings = torch.nn.Parameter(tsd["spatial_embeddings"].clone())
+    mod.load_state_dict(tsd, strict=False)
+    mod.precision = "f32" if precision == "f32" else "f16x3"
+    if precision in ("tape16", "amp", "amp16"):
+        mod.grad_precision = precision
+        if precision != "tape16":
+            mod.AMP_MIN_POINTS = 1
+    return mod.to(DEV), spec, sd
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3", "tape16", "amp", "amp16"])
+@pytest.mark.parametrize("kind,H,grid,P", [("texture", 32, 5, 75), ("baseline", 64, 0, 70), ("spatial", 32, 0, 33), ("texture", 100, 5, 75)])
+@pytest.mark.parametrize("inj", ["upstream-nan", "upstream-pinf", "phase-nan"])
+def test_siren_backward_nonfinite(inj, kind, H, grid, P, precision):
+    B = 2
+    mod, spec, sd = _siren_module(kind, H, grid, precision)
+    _, _, pts, dirs, film = _siren_inputs(kind, H, grid, P)
+    Cc = spec["output_dim"]
+    rng = np.random.default_rng(8)
+    g_out = rng.normal(size=(B, P, Cc)).astype(np.float32)
+    g_out[..., -1] *= 0.02
+    if inj == "upstream-nan":
+        g_out[1, 7, 0] = np.nan
+    elif inj == "upstream-pinf":
+        g_out[1, 7, Cc - 1] = np.inf
+    else:
+        film["phase_geo"][1, 5 * H + 1] = np.nan
+    film_t = {k: T(v).requires_grad_(True) for k, v in film.items()}
+    if kind == "spatial":
+        out = mod.forward_with_frequencies_phase_shifts(T(pts), torch.cat([film_t["freq_geo"], film_t["freq_app"]], -1),
+                                                        torch.cat([film_t["phase_geo"], film_t["phase_app"]], -1), T(dirs))
+    else:
+        out = mod.forward_with_frequencies_phase_shifts(T(pts), film_t["freq_geo"], film_t["freq_app"], film_t["phase_geo"], film_t["phase_app"], T(dirs))
+    (out * T(g_out)).sum().backward()
+    t64 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
+    sd64 = {k: t64(v).requires_grad_(True) for k, v in sd.items()}
+    film64 = {k: t64(v).requires_grad_(True) for k, v in film.items()}
+    ref = OG.siren_forward(sd64, spec, t64(pts), t64(dirs), film64["freq_geo"], film64["phase_geo"], film64["freq_app"], film64["phase_app"])
+    (ref * t64(g_out)).sum().backward()
+    tag = f"siren_backward[{inj}-{kind}-H{H}-{precision}]"
+    nan = inj != "upstream-pinf"
+
+    def bound(k, r):
+        """relative to the tensor's largest finite |gradient|: test_siren_backward_vs_autograd's 2e-4 (f32, f16x3, tape16); the AMP tiers'
+        own classes from test_siren_backward_at_scale_vs_fp64_autograd (6e-3 through the bf16 dump, 6e-5 / 2.5e-4 -> 2e-4 / 2.5e-4 else)"""
+        fin = np.isfinite(r)
+        dump = precision in ("amp", "amp16") and (k.endswith("layer.weight") or (precision == "amp16" and k.startswith("freq_")))
+        rel = 6e-3 if dump else (2.5e-4 if precision == "amp16" else 2e-4)
+        return rel * max(float(np.abs(r[fin]).max()) if fin.any() else 0.0, 1e-12)
+    # FiLM gradients: D = image 1; image 0 finite and within the bound
+    for k in film:
+        r = _f32_grad(film64[k])
+        D = np.zeros(r.shape, bool); D[1] = True
+        check(tag, "d_" + k, N_(film_t[k].grad), r, D, bound(k, r), nan)
+    # weight gradients sum over every point: D = everything.  Per tensor "has a non-finite element" as the reference; element-wise no
+    # swallowing and, for the NaN injections, the converse: finite and in bound wherever the reference is
+    named = dict(mod.named_parameters())
+    for k, v in sd64.items():
+        r = _f32_grad(v)
+        got = N_(named[k].grad)
+        assert (~np.isfinite(got)).any() == (~np.isfinite(r)).any(), (tag, k, "has a non-finite element", int((~np.isfinite(got)).sum()), int((~np.isfinite(r)).sum()))
+        check(tag, "d_" + k, got, r, np.ones(r.shape, bool), bound(k, r), nan)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The generator's render node (what g_loss.backward() runs): the render-backward ABI and the Python orchestration, chunked, sparse, with
+# the deterministic grid gradient -- a non-finite upstream gradient at one pixel of image 1, vs fp64 autograd of the restatement on the same
+# rays, depths and noise.  Shape, model and the 5e-4 bound of test_gpu_parity.py::test_generator_gradient_end_to_end.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+GEN_KW = dict(fov=12, ray_start=0.88, ray_end=1.12, h_stddev=0.3, v_stddev=0.155, h_mean=np.pi / 2, v_mean=np.pi / 2, hierarchical_sample=True,
+              sample_dist="gaussian", clamp_mode="relu")
+
+
+def _generator(precision, sigma_gain=150.0):
+    from fenerf_amd.generators import generators as G
+    mod, spec, sd = _siren_module("texture", 32, 5, precision, sigma_gain=sigma_gain)
+    gen = G.DoubleImplicitGenerator3d(functools.partial(S.TextureEmbeddingPiGAN128SEMANTICDISENTANGLE, hidden_dim=32), 8, 8, 22)
+    gen.siren = mod
+    gen = gen.to(DEV)
+    gen.device = torch.device(DEV); gen.siren.device = gen.device
+    return gen, mod, spec, sd
+
+
+@pytest.mark.parametrize("inj", ["upstream-nan", "upstream-pinf"])
+@pytest.mark.parametrize("route", ["abi", "python", "chunked", "sparse", "deterministic", "sparse-deterministic", "tape16-abi"])
+def test_generator_backward_nonfinite(route, inj, monkeypatch):
+    from fenerf_amd.generators import autograd as GA
+    from fenerf_amd.siren import autograd as SA
+    gen, mod, spec, sd = _generator("tape16" if route.startswith("tape16") else "f16x3")
+    if route == "python":
+        monkeypatch.setattr(GA, "USE_RENDER_ABI", False)
+    if route == "chunked":
+        monkeypatch.setattr(SA, "BACKWARD_CHUNK_POINTS", 256)          # 2 x 36 x 12 x 2 = 1,728 points: seven chunks
+    mod.sparse_backward = "sparse" in route
+    mod.deterministic_backward = True if "deterministic" in route else None
+    B, S_, N = 2, 6, 12
+    R = S_ * S_
+    film = proc.film_params(spec, B, seed=4)
+    film_t = {k: T(v).requires_grad_(True) for k, v in film.items()}
+    kw = dict(GEN_KW, img_size=S_, num_steps=N, nerf_noise=0.2, last_back=False)
+    torch.manual_seed(11)
+    px, _ = gen.forward_with_frequencies(film_t["freq_geo"], film_t["freq_app"], film_t["phase_geo"], film_t["phase_app"], **kw)
+    w = torch.randn(px.shape, device=DEV, generator=torch.Generator(device=DEV).manual_seed(5))
+    w[1, 19, 2, 4] = VALUES[inj.rsplit("-", 1)[1]]          # an rgb channel: the feature grid feeds the colour branch only
+    (px * w).sum().backward()
+    GA.SparseHierarchicalRenderFunction.verify()           # the sparse node's deferred overflow flag: must not have fired
+    # the constants of the step (rays, depths, resampled depths, noise: no_grad in the reference too) replayed from the same seed
+    torch.manual_seed(11)
+    origins, dirs, z_vals, _, _ = VR.sample_rays(B, N, gen.device, kw["fov"], (S_, S_), kw["ray_start"], kw["ray_end"], kw["h_stddev"],
+                                                 kw["v_stddev"], kw["h_mean"], kw["v_mean"], kw["sample_dist"], draws=gen.draws)
+    noise_c = gen.draws.randn((B, R, N, 1), gen.device); u = gen.draws.rand((B * R, N), gen.device)
+    noise_f = gen.draws.randn((B, R, 2 * N, 1), gen.device)
+    z_c = z_vals.reshape(B, R, N)
+    nat = mod.native_differentiable(DEV)
+    with torch.no_grad():
+        pts_c = origins.unsqueeze(2) + dirs.unsqueeze(2) * z_c.unsqueeze(-1)
+        rd = dirs.unsqueeze(2).expand(-1, -1, N, -1).reshape(B, R * N, 3)
+        coarse = nat.siren_forward(pts_c.reshape(B, R * N, 3), rd, *(film_t[k] for k in ("freq_geo", "phase_geo", "freq_app", "phase_app")))
+        _, _, w_c, _ = native.composite(coarse.reshape(B * R, N, 22), z_c.reshape(B * R, N), noise_c.reshape(B * R, N),
+                                        _lib.composite_opts("relu", 0.2), want_wsum=False)
+        z_f = native.resample(z_c.reshape(B * R, N), w_c, u).reshape(B, R, N)
+        pts_f = origins.unsqueeze(2) + dirs.unsqueeze(2) * z_f.unsqueeze(-1)
+    t64 = lambda a: torch.as_tensor(N_(a) if torch.is_tensor(a) else np.asarray(a), dtype=torch.float64)
+    sd64 = {k: t64(v).requires_grad_(True) for k, v in sd.items()}
+    film64 = {k: t64(v).requires_grad_(True) for k, v in film.items()}
+    args = (film64["freq_geo"], film64["phase_geo"], film64["freq_app"], film64["phase_app"])
+    c64 = OG.siren_forward(sd64, spec, t64(pts_c.reshape(B, R * N, 3)), t64(rd), *args)
+    f64 = OG.siren_forward(sd64, spec, t64(pts_f.reshape(B, R * N, 3)), t64(rd), *args)
+    rgb, _, _ = OG.merge_composite(f64.reshape(B * R, N, 22), c64.reshape(B * R, N, 22), t64(z_f.reshape(B * R, N)), t64(z_c.reshape(B * R, N)),
+                                   t64(noise_f.reshape(B * R, 2 * N)), noise_std=0.2, clamp_mode="relu")
+    ref_px = rgb.reshape(B, S_, S_, 21).permute(0, 3, 1, 2) * 2 - 1
+    (ref_px * t64(w)).sum().backward()
+    assert np.abs(N_(px) - ref_px.detach().numpy()).max() <= 1e-3
+    tag = f"generator_backward[{route}-{inj}]"
+    nan = inj.endswith("nan")
+    rel = lambda r: 5e-4 * max(float(np.abs(r[np.isfinite(r)]).max()) if np.isfinite(r).any() else 0.0, 1e-12)
+    for k in film:                                                      # D = image 1; image 0's FiLM gradients finite and in bound
+        r = _f32_grad(film64[k])
+        D = np.zeros(r.shape, bool); D[1] = True
+        check(tag, "d_" + k, N_(film_t[k].grad), r, D, rel(r), nan)
+    named = dict(mod.named_parameters())
+    for k, v in sd64.items():                                           # sums over all points: D = everything
+        r, got = _f32_grad(v), N_(named[k].grad)
+        assert (~np.isfinite(got)).any() == (~np.isfinite(r)).any(), (tag, k, "has a non-finite element")
+        check(tag, "d_" + k, got, r, np.ones(r.shape, bool), rel(r), nan)
+        if k == "spatial_embeddings" and nan:                           # NaN at exactly the voxel-channels the ray's samples touch
+            assert np.array_equal(~np.isfinite(got), ~np.isfinite(r)) and np.isfinite(r).any() and not np.isfinite(r).all()
+
+
+@pytest.mark.parametrize("v", ["nan", "pinf"])
+def test_sparse_backward_bound_under_a_nonfinite_upstream_gradient(v):
+    """A non-finite upstream gradient on EVERY pixel of image 1 makes every sample row of that image non-zero (0 * NaN): far more rows
+    than the bound the forward took from the densities.  That must not raise the sparse node's overflow error (the reference's step
+    is non-finite and a GradScaler skips it); the rows that did not fit are made up for by NaN in every returned gradient."""
+    from fenerf_amd.generators import autograd as GA
+    gen, mod, spec, sd = _generator("f16x3")
+    mod.sparse_backward = True
+    film_t = {k: T(a).requires_grad_(True) for k, a in proc.film_params(spec, 2, seed=4).items()}
+    torch.manual_seed(11)
+    px, _ = gen.forward_with_frequencies(film_t["freq_geo"], film_t["freq_app"], film_t["phase_geo"], film_t["phase_app"],
+                                         **dict(GEN_KW, img_size=6, num_steps=12, nerf_noise=0.2, last_back=False))
+    w = torch.randn(px.shape, device=DEV, generator=torch.Generator(device=DEV).manual_seed(5))
+    w[1] = VALUES[v]
+    (px * w).sum().backward()
+    kept, total = GA.SparseHierarchicalRenderFunction.last_kept
+    groups = GA.SparseHierarchicalRenderFunction.last_groups
+    GA.SparseHierarchicalRenderFunction.verify()
+    slots = sum(len(g) * c for g, c in groups)
+    assert slots < total, "the case must be one where the bound is below the number of non-zero rows"
+    grads = [film_t[k].grad for k in film_t] + [p.grad for _, p in mod.named_parameters() if p.grad is not None]
+    assert len(grads) > 30 and all(not torch.isfinite(g).all() for g in grads)
+    note(f"sparse_bound[{v}]", D=sum(g.numel() for g in grads), R=0, inside=sum(int((~torch.isfinite(g)).sum()) for g in grads), outside=0, extra=0)
+    # ... and with a finite gradient the same node still works and its flag stays down
+    for p in list(film_t.values()) + list(mod.parameters()):
+        p.grad = None
+    torch.manual_seed(11)
+    px, _ = gen.forward_with_frequencies(film_t["freq_geo"], film_t["freq_app"], film_t["phase_geo"], film_t["phase_app"],
+                                         **dict(GEN_KW, img_size=6, num_steps=12, nerf_noise=0.2, last_back=False))
+    (px * torch.randn_like(px)).sum().backward()
+    GA.SparseHierarchicalRenderFunction.verify()
+    assert all(torch.isfinite(film_t[k].grad).all() for k in film_t)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# GradScaler end to end (train_double_latent_semantic.py:279, :408-420): the skipped-step path through the native autograd nodes.
+# The scale: the loss is sum(px * w), so the render node's upstream gradient is scale * w in fp32.  With scale = 2^127 (the largest
+# power of two a float holds) every |w| >= 2 gives +-Inf -- in the reference's fp32 restatement exactly as here -- so the first step
+# overflows by construction, whatever the model computes.  The scaler then halves until a step is finite, as in training (measured: 35
+# skipped steps, the first finite one at 2^92, every precision and route); every skipped step is checked.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sparse", [False, True, "auto"])
+@pytest.mark.parametrize("precision", ["f16x3", "amp", "amp16"])
+def test_gradscaler_skips_overflowed_steps_and_recovers(precision, sparse):
+    from fenerf_amd.generators import autograd as GA
+    torch.manual_seed(5)
+    gen, mod, spec, sd = _generator(precision)
+    mod.sparse_backward = sparse
+    kw = dict(GEN_KW, img_size=8, num_steps=12, nerf_noise=0.1)
+    z = torch.randn(2, 8, device=DEV)
+    w = torch.randn((2, 21, 8, 8), device=DEV)
+    assert int((w.abs() >= 2).sum()) > 0
+    opt = torch.optim.Adam(gen.parameters(), lr=1e-4)
+    scaler = torch.amp.GradScaler("cuda", init_scale=2.0 ** 127, growth_interval=10 ** 9)
+
+    def step(amp):
+        opt.zero_grad(set_to_none=True)
+        torch.manual_seed(11)
+        with torch.autocast("cuda", enabled=amp):
+            px, _ = gen(z, z, **kw)
+            loss = (px.float() * w).sum()
+        (scaler.scale(loss) if amp else loss).backward()
+        GA.SparseHierarchicalRenderFunction.verify()        # the sparse route's deferred overflow flag must not fire for rows it kept
+        return {n: p.grad for n, p in gen.named_parameters() if p.grad is not None}
+
+    g32 = {n: N_(g) for n, g in step(False).items()}
+    skipped = 0
+    while True:
+        grads = step(True)
+        scale = scaler.get_scale()
+        finite = all(bool(torch.isfinite(g).all()) for g in grads.values())
+        before = [p.detach().clone() for p in gen.parameters()]
+        if finite:
+            g16 = {n: N_(g) / scale for n, g in grads.items()}
+            break
+        scaler.step(opt)
+        scaler.update()
+        assert all(torch.equal(a, p.detach()) for a, p in zip(before, gen.parameters())), "a skipped step must leave every parameter bit-identical"
+        assert scaler.get_scale() == scale / 2, (scale, scaler.get_scale())
+        skipped += 1
+        assert skipped <= 150, "no finite step down to a scale of 2^-23"
+    assert skipped >= 1
+    # the first finite step: the unscaled step's gradients to the bound of test_generator_step_under_autocast_and_gradscaler
+    assert set(g32) == set(g16)
+    cos = {k: float((g16[k] * g32[k]).sum() / (np.linalg.norm(g16[k]) * np.linalg.norm(g32[k]) + 1e-30))
+           for k in g32 if "mapping_network" not in k and g32[k].size >= 1024}
+    print(f"[nonfinite] gradscaler[{precision}-sparse={sparse}]: {skipped} skipped steps from 2^127, first finite step at scale 2^{int(np.log2(scale))}, "
+          f"cosine(grad, unscaled fp32 grad) over render weights min {min(cos.values()):.3f}")
+    assert min(cos.values()) >= 0.7
+    scaler.step(opt)          # and that step is taken
+    scaler.update()
+    assert any(not torch.equal(a, p.detach()) for a, p in zip(before, gen.parameters()))
+
+
+def test_device_repack_keeps_an_all_ones_nan_weight_a_nan():
+    """fenerf_model_repack's bf16 halves (bf16_rne_bits): a NaN with an all-ones mantissa used to round to -0 in both halves of the backward
+    stream.  Every half of the exported backward stream that the weight feeds must be a NaN (the host packer: tests/test_nonfinite_cpu.py)."""
+    spec, sd, *_ = _siren_inputs("texture", 32, 5, 75)
+    nat = native.NativeModel(sd, spec, DEV, "f16x3", differentiable=True)
+    nat.load_from_device({k: T(a) for k, a in sd.items()})
+    clean = N_(nat.export_packed()[2]).view(np.uint16)
+    for bits in (0x7fffffff, 0xffffffff):
+        sd2 = {k: a.copy() for k, a in sd.items()}
+        sd2["network.3.layer.weight"].view(np.uint32)[2, 5] = bits
+        params = {k: torch.from_numpy(a).to(DEV) for k, a in sd2.items()}
+        assert int(params["network.3.layer.weight"].view(torch.int32)[2, 5]) == np.uint32(bits).astype(np.int32)      # the payload arrived
+        nat.load_from_device(params)
+        h = N_(nat.export_packed()[2]).view(np.uint16)
+        changed = np.flatnonzero(h != clean)
+        is_nan = ((h[changed] & 0x7f80) == 0x7f80) & ((h[changed] & 0x007f) != 0)
+        assert changed.size >= 2 and is_nan.all(), (hex(bits), changed.size, [hex(x) for x in h[changed][:8]])
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# mapping network (fenerf_mapping_forward / _backward) and the label head's backward (fenerf_label_head_backward) vs torch on the CPU.
+# Shapes and bounds of test_mapping_network_native_vs_torch (output 2e-6, gradients 1e-5, relative) / test_label_head_backward_native_vs_autograd (2e-6)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _rel_bound(rel, r):
+    fin = np.isfinite(r)
+    return rel * max(float(np.abs(r[fin]).max()) if fin.any() else 0.0, 1e-12)
+
+
+@pytest.mark.parametrize("inj", ["z-nan", "z-pinf", "upstream-nan", "upstream-pinf", "weight-nan"])
+@pytest.mark.parametrize("z_dim,hidden,out_dim,n_blocks,B", [(16, 256, 704, 3, 4), (7, 33, 10, 1, 3)])
+def test_mapping_network_nonfinite(z_dim, hidden, out_dim, n_blocks, B, inj):
+    import copy
+    torch.manual_seed(z_dim + out_dim + B)
+    net = S.CustomMappingNetwork(z_dim, hidden, out_dim, n_blocks=n_blocks)
+    z = torch.randn(B, z_dim)
+    w = torch.randn(B, out_dim)
+    v = VALUES[inj.rsplit("-", 1)[1]]
+    if inj.startswith("z"):
+        z[1, 3] = v
+    elif inj.startswith("upstream"):
+        w[1, 5] = v
+    else:
+        with torch.no_grad():
+            net.network[2].weight[4, 6] = v
+    ref_net = copy.deepcopy(net)
+    ref = ref_net.network(z)
+    (ref * w).sum().backward()
+    net = net.to(DEV)
+    zd = z.to(DEV)
+    assert net._native_ok(zd)
+    f, p = net(zd)
+    out = torch.cat([f, p], -1)
+    assert "_MappingFunction" in str(f.grad_fn), "the native route ran"
+    (out * w.to(DEV)).sum().backward()
+    tag = f"mapping[{inj}-{z_dim}x{hidden}x{out_dim}-B{B}]"
+    nan = inj.endswith("nan")
+    D = np.zeros((B, out_dim), bool)
+    if inj.startswith("z"):
+        D[1] = True
+    elif inj == "weight-nan":
+        D[:] = True
+    check(tag, "out", N_(out), N_(ref), D, _rel_bound(2e-6, N_(ref)), nan)
+    for (n, q), (_, rq) in zip(net.named_parameters(), ref_net.named_parameters()):
+        got, r = N_(q.grad), N_(rq.grad)
+        assert (~np.isfinite(got)).any() == (~np.isfinite(r)).any(), (tag, n, "has a non-finite element", int((~np.isfinite(got)).sum()), int((~np.isfinite(r)).sum()))
+        check(tag, "d_" + n, got, r, np.ones(r.shape, bool), _rel_bound(1e-5, r), nan)
+
+
+@pytest.mark.parametrize("inj", ["upstream-nan", "upstream-pinf", "weight-nan", "bias-upstream-nan"])
+@pytest.mark.parametrize("n_layers,H,n_lab", [(3, 32, 18), (2, 100, 1)])
+def test_label_head_backward_nonfinite(n_layers, H, n_lab, inj):
+    from fenerf_amd.siren import autograd as SA
+    g = torch.Generator(device="cpu").manual_seed(n_layers * 1000 + H + n_lab)
+    dims = [H] * n_layers + [n_lab]
+    params = [(torch.randn(dims[i + 1] if i == n_layers - 1 else H, H, generator=g).mul_(H ** -0.5), torch.randn(dims[i + 1] if i == n_layers - 1 else H, generator=g).mul_(0.3))
+              for i in range(n_layers)]
+    gA, gc = torch.randn(n_lab, H, generator=g), torch.randn(n_lab, generator=g)
+    v = VALUES[inj.rsplit("-", 1)[1]]
+    if inj.startswith("upstream"):
+        gA[0, 5] = v
+    elif inj == "weight-nan":
+        params[0][0][3, 4] = v
+    else:
+        gc[0] = v
+    got = native.label_head_backward([(W.to(DEV), b.to(DEV)) for W, b in params], gA.to(DEV), gc.to(DEV))
+    p64 = [(W.double().requires_grad_(True), b.double().requires_grad_(True)) for W, b in params]
+    A, c = SA._fold_label_head(p64)
+    ((A * gA.double()).sum() + (c * gc.double()).sum()).backward()
+    tag = f"label_head_backward[{inj}-{n_layers}x{H}x{n_lab}]"
+    for i, ((dW, db), (W64, b64)) in enumerate(zip(got, p64)):
+        for name, a, r64 in ((f"dW{i}", dW, W64), (f"db{i}", db, b64)):
+            with quiet():
+                r = r64.grad.numpy().astype(np.float32)
+            a = N_(a)
+            assert (~np.isfinite(a)).any() == (~np.isfinite(r)).any(), (tag, name, "has a non-finite element", int((~np.isfinite(a)).sum()), int((~np.isfinite(r)).sum()))
+            check(tag, name, a, r, np.ones(r.shape, bool), _rel_bound(2e-6, r), inj.endswith("nan"))

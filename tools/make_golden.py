@@ -6,6 +6,7 @@ inputs (procedural-weight seeds, film params, every random draw the reference ma
 recorded in call order) and the reference's outputs, per stage and end to end.
 
     python tools/make_golden.py            # writes tests/golden/
+    python tools/make_golden.py DIR nonfinite      # only the nonfinite_* fixtures, into DIR
 """
 import functools
 import os
@@ -961,7 +962,160 @@ def run_curriculums(refs, name="curriculums"):
     print(f"{name}: {len(out)} curriculum dicts")
 
 
-def main(out_dir=None):
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# non-finite inputs: what the reference's own functions return when ONE value of otherwise ordinary inputs is NaN / +Inf / -Inf
+# ---------------------------------------------------------------------------------------------------------------------------------------
+NONFINITE = {"nan": np.nan, "pinf": np.inf, "ninf": -np.inf}
+
+
+def _fixed_draw(name, value):
+    """context: torch.<name>(...) returns `value` (the reference draws its noise / its u inside the function under test)"""
+    class _Ctx:
+        def __enter__(self):
+            self.orig = getattr(torch, name)
+            setattr(torch, name, lambda *a, **k: value.clone())
+
+        def __exit__(self, *exc):
+            setattr(torch, name, self.orig)
+    return _Ctx()
+
+
+def nonfinite_composite_inputs(seed=11, R=6, M=12, C=22):
+    rng = np.random.default_rng(seed)
+    rs = rng.normal(size=(1, R, M, C)).astype(np.float32)
+    rs[..., -1] *= 30
+    rs[0, :, 4, -1] = -5.0                         # sample 4 of every ray: clamped density, an exactly-zero relu weight
+    z = np.sort(rng.uniform(0.88, 1.12, (1, R, M, 1)).astype(np.float32), axis=2)
+    noise = rng.normal(size=(1, R, M, 1)).astype(np.float32)
+    return rs, z, noise
+
+
+def nonfinite_composite_cases():
+    """(id, fancy_integration kwargs, what to overwrite: (array, index, value name)) -- ray 1 takes every injection"""
+    cases = []
+    for clamp in ("relu", "softplus"):
+        for v in ("nan", "pinf", "ninf"):
+            cases.append((f"{clamp}-density-{v}", dict(clamp_mode=clamp, noise_std=0.0), ("rs", (0, 1, 2, -1), v)))
+    cases += [("relu-last_back-density-nan", dict(clamp_mode="relu", noise_std=0.0, last_back=True), ("rs", (0, 1, 2, -1), "nan")),
+              ("relu-white_back-density-nan", dict(clamp_mode="relu", noise_std=0.0, white_back=True), ("rs", (0, 1, 2, -1), "nan")),
+              ("relu-fill-density-nan", dict(clamp_mode="relu", noise_std=0.0, fill_mode="seg_padding_background", fill_color="grey"),
+               ("rs", (0, 1, 2, -1), "nan")),
+              ("relu-colour-nan-at-zero-weight", dict(clamp_mode="relu", noise_std=0.0), ("rs", (0, 1, 4, 3), "nan")),
+              ("relu-colour-pinf-at-zero-weight", dict(clamp_mode="relu", noise_std=0.0), ("rs", (0, 1, 4, 3), "pinf")),
+              ("relu-noise-nan", dict(clamp_mode="relu", noise_std=0.5), ("noise", (0, 1, 2, 0), "nan")),
+              ("softplus-noise-nan", dict(clamp_mode="softplus", noise_std=0.5, last_back=True), ("noise", (0, 1, 2, 0), "nan")),
+              ("relu-depth-nan", dict(clamp_mode="relu", noise_std=0.0), ("z", (0, 1, 6, 0), "nan")),
+              ("relu-depth-pinf-last", dict(clamp_mode="relu", noise_std=0.0), ("z", (0, 1, 11, 0), "pinf"))]
+    return cases
+
+
+def run_nonfinite(refs):
+    """tests/golden/nonfinite_*.npz: the reference's fancy_integration, sample_pdf, its sort-and-gather merge (generators.py:508-512:
+    torch.cat / torch.sort / torch.gather, called here as the generator calls them) and the three SIREN families' forward and autograd,
+    each with one non-finite value injected.  tests/test_nonfinite_cpu.py holds the oracles to these."""
+    siren_mod, gens, vr, cur = refs
+    out = {}
+    cases = nonfinite_composite_cases()
+    out["base_rs"], out["base_z"], out["base_noise"] = nonfinite_composite_inputs()
+    for i, (cid, kw, (what, idx, v)) in enumerate(cases):
+        rs, z, noise = nonfinite_composite_inputs()
+        {"rs": rs, "z": z, "noise": noise}[what][idx] = NONFINITE[v]
+        with _fixed_draw("randn", torch.from_numpy(noise)):
+            r = vr.fancy_integration(torch.from_numpy(rs.copy()), torch.from_numpy(z.copy()), device="cpu", **kw)
+        out[f"c{i}_id"], out[f"c{i}_kw"] = cid, repr(kw)
+        out[f"c{i}_inj"] = repr((what, idx, v))                  # the case's inputs: base_* with this one element overwritten
+        out[f"c{i}_rgb"], out[f"c{i}_depth"], out[f"c{i}_third"] = (np_(t).copy() for t in r)
+    out["n_cases"] = len(cases)
+    # the merge: fine | coarse depths with a NaN, two NaNs, +Inf and -Inf, and ties across the passes
+    rng = np.random.default_rng(12)
+    R, N, C = 5, 6, 22
+    merges = []
+    for j, inj in enumerate([[("zf", 2, "nan")], [("zc", 3, "nan")], [("zf", 1, "nan"), ("zc", 4, "nan"), ("zf", 5, "pinf"), ("zc", 0, "ninf")],
+                             [("zf", 0, "pinf")]]):
+        fine = rng.normal(size=(1, R, N, C)).astype(np.float32); coarse = rng.normal(size=(1, R, N, C)).astype(np.float32)
+        fine[..., -1] *= 30; coarse[..., -1] *= 30
+        zc = np.sort(rng.uniform(0.88, 1.12, (1, R, N, 1)).astype(np.float32), axis=2)
+        zf = np.sort(rng.uniform(0.88, 1.12, (1, R, N, 1)).astype(np.float32), axis=2)
+        zf[0, :, 3] = zc[0, :, 2]                                                     # a tie between the passes: fine first
+        for what, k, v in inj:
+            {"zf": zf, "zc": zc}[what][0, 1, k, 0] = NONFINITE[v]
+        all_out = torch.cat([torch.from_numpy(fine), torch.from_numpy(coarse)], dim=-2)
+        all_z = torch.cat([torch.from_numpy(zf), torch.from_numpy(zc)], dim=-2)
+        _, indices = torch.sort(all_z, dim=-2)
+        all_z = torch.gather(all_z, -2, indices)
+        all_out = torch.gather(all_out, -2, indices.expand(-1, -1, -1, C))
+        r = vr.fancy_integration(all_out, all_z, device="cpu", clamp_mode="relu", noise_std=0.0)
+        out[f"m{j}_fine"], out[f"m{j}_coarse"], out[f"m{j}_zf"], out[f"m{j}_zc"] = fine, coarse, zf, zc
+        out[f"m{j}_indices"], out[f"m{j}_all_z"] = np_(indices), np_(all_z)
+        out[f"m{j}_rgb"], out[f"m{j}_depth"], out[f"m{j}_third"] = (np_(t).copy() for t in r)
+        merges.append(j)
+    out["n_merges"] = len(merges)
+    # sample_pdf with a non-finite weight in ray 1
+    g = torch.Generator().manual_seed(6)
+    for j, v in enumerate(["nan", "pinf"]):
+        bins = torch.sort(torch.rand(4, 11, generator=g) * 0.24 + 0.88, dim=-1)[0]
+        w = torch.rand(4, 10, generator=g) ** 4 + 1e-5
+        w[1, 4] = NONFINITE[v]
+        u = torch.rand(4, 12, generator=g)
+        with _fixed_draw("rand", u):
+            s = vr.sample_pdf(bins, w, 12, det=False)
+        out[f"p{j}_bins"], out[f"p{j}_weights"], out[f"p{j}_u"], out[f"p{j}_samples"] = np_(bins), np_(w), np_(u), np_(s)
+    out["n_pdf"] = 2
+    path = os.path.join(OUT, "nonfinite_composite.npz")
+    np.savez_compressed(path, **out)
+    print(f"nonfinite_composite: {len(cases)} composite, {len(merges)} merge, 2 sample_pdf cases -> {os.path.getsize(path) / 1024:.0f} KiB")
+
+    # the SIREN families: forward and the module's own autograd (loss = sum(out * w)), B = 2, image 1 / point 7 take the injection
+    B, P = 2, 20
+    for kind, seed in (("texture", 3), ("baseline", 5), ("spatial", 8)):
+        spec = proc.model_spec(kind, hidden_dim=16, grid_size=4, z_dim=16) if kind == "texture" else proc.model_spec(kind, hidden_dim=16, z_dim=16)
+        H = spec["hidden_dim"]
+        rng = np.random.default_rng(200 + seed)
+        pts0 = rng.uniform(-0.11, 0.11, (B, P, 3)).astype(np.float32)
+        dirs0 = rng.normal(size=(B, P, 3)).astype(np.float32)
+        dirs0 /= np.linalg.norm(dirs0, axis=-1, keepdims=True)
+        w0 = rng.normal(size=(B, P, spec["output_dim"])).astype(np.float32)
+        w0[..., -1] *= 0.02
+        film0 = proc.film_params(spec, B, seed=seed)
+        injections = [("coord-nan", "points", (1, 7, 1), "nan"), ("dir-nan", "dirs", (1, 7, 0), "nan"),
+                      ("freq-nan", "freq_geo", (1, 2 * H + 3), "nan"), ("freq-pinf", "freq_geo", (1, 2 * H + 3), "pinf"),
+                      ("phase-nan", "phase_geo", (1, 5 * H + 1), "nan"), ("phase-app-nan", "phase_app", (1, 2), "nan"),
+                      ("grad-nan", "loss_w", (1, 7, 0), "nan"), ("grad-pinf", "loss_w", (1, 7, spec["output_dim"] - 1), "pinf")]
+        if not spec["grid_ch"]:       # with a feature grid the reference turns an Inf coordinate into a voxel index: undefined behaviour (float -> int of Inf): nothing to record
+            injections += [("coord-pinf", "points", (1, 7, 1), "pinf"), ("coord-ninf", "points", (1, 7, 2), "ninf")]
+        out = dict(meta_seed=seed, meta_sigma_gain=30.0, n_cases=len(injections), base_points=pts0, base_dirs=dirs0, base_loss_w=w0)
+        out.update({"base_" + k: a for k, a in film0.items()})
+        for k, v in spec.items():
+            out["spec_" + k] = v
+        gmod, sd = build_ref_generator(refs, spec, seed, 30.0)
+        out["meta_weights_checksum"] = proc.checksum(sd)
+        for i, (cid, what, idx, v) in enumerate(injections):
+            arrs = dict(points=pts0.copy(), dirs=dirs0.copy(), loss_w=w0.copy(), **{k: a.copy() for k, a in film0.items()})
+            arrs[what][idx] = NONFINITE[v]
+            gmod.siren.zero_grad()
+            tf = {k: torch.from_numpy(arrs[k]).requires_grad_(True) for k in film0}
+            pts, dirs = torch.from_numpy(arrs["points"]), torch.from_numpy(arrs["dirs"])
+            if kind == "spatial":
+                o = gmod.siren.forward_with_frequencies_phase_shifts(pts, torch.cat([tf["freq_geo"], tf["freq_app"]], -1),
+                                                                     torch.cat([tf["phase_geo"], tf["phase_app"]], -1), ray_directions=dirs)
+            else:
+                o = gmod.siren.forward_with_frequencies_phase_shifts(pts, tf["freq_geo"], tf["freq_app"], tf["phase_geo"], tf["phase_app"],
+                                                                     ray_directions=dirs)
+            (o * torch.from_numpy(arrs["loss_w"])).sum().backward()
+            out[f"c{i}_id"], out[f"c{i}_inj"] = cid, repr((what, idx, v))      # the case's inputs: base_* with this one element overwritten
+            out[f"c{i}_out"] = np_(o)
+            for k in film0:
+                out[f"c{i}_grad_film_{k}"] = np_(tf[k].grad)
+            if cid in ("phase-nan", "grad-nan", "grad-pinf"):      # weight gradients: of the cases the backward tests are about
+                for k, prm in gmod.siren.named_parameters():
+                    if k in sd and prm.grad is not None:        # the mapping networks take no part in a with-frequencies forward
+                        out[f"c{i}_grad_{k}"] = np_(prm.grad)
+        path = os.path.join(OUT, f"nonfinite_siren_{kind}.npz")
+        np.savez_compressed(path, **out)
+        print(f"nonfinite_siren_{kind}: {len(injections)} injections -> {os.path.getsize(path) / 1024:.0f} KiB")
+
+
+def main(out_dir=None, only=None):
     """Regenerates every fixture into `out_dir` (default tests/golden).  Run into a scratch directory and compared with the committed
     files, it checks the recipe against the reference."""
     global OUT
@@ -970,6 +1124,9 @@ def main(out_dir=None):
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
     refs = ref_import.import_reference()
+    if only == "nonfinite":
+        return run_nonfinite(refs)
+    run_nonfinite(refs)
     run_curriculums(refs)
     relu = dict(clamp_mode="relu", nerf_noise=0.0)
 
@@ -1055,4 +1212,4 @@ def main(out_dir=None):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else None)
+    main(sys.argv[1] if len(sys.argv) > 1 else None, sys.argv[2] if len(sys.argv) > 2 else None)   # [out_dir [recipe]]
