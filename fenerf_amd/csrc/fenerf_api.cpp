@@ -18,12 +18,16 @@ namespace fenerf {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
 
-static int fail(int code, const std::string& msg) {
+int fail(int code, const std::string& msg) {
   set_error(msg);
   return code;
 }
-static int hip_fail(hipError_t e, const char* what) {
+int hip_fail(hipError_t e, const char* what) {
   return fail(FENERF_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+int check_launch(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? FENERF_OK : hip_fail(e, what);
 }
 #define HIP_TRY(expr)                                   \
   do {                                                  \

@@ -234,9 +234,7 @@ int launch_composite_backward(const CompositeParams& p, bool merge, void* stream
   if (p.BR <= 0) return FENERF_OK;
   if (merge) FENERF_BY_RAY_SAMPLES(p.M, composite_backward_kernel, true, p.BR, stream, p);
   else FENERF_BY_RAY_SAMPLES(p.M, composite_backward_kernel, false, p.BR, stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("composite_backward launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
+  return check_launch("composite_backward launch");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -376,22 +374,14 @@ int launch_ray_setup(int B, int S, int N, float z_cam, float ray_start, float ra
   if (total <= 0) return FENERF_OK;
   hipLaunchKernelGGL(ray_setup_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, S, N, z_cam,
                      ray_start, ray_end, u_jitter, theta, phi, origins, dirs, z, pitch, yaw);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("ray_setup launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
-}
-
-static int hip_fail2(hipError_t e, const char* what) {
-  set_error(std::string(what) + ": " + hipGetErrorString(e));
-  return FENERF_E_HIP;
+  return check_launch("ray_setup launch");
 }
 
 int launch_composite(const CompositeParams& p, bool merge, void* stream) {
   if (p.BR <= 0) return FENERF_OK;
   if (merge) FENERF_BY_RAY_SAMPLES(p.M, composite_kernel, true, p.BR, stream, p);   // same results for any MAXM: fenerf_composite_ray.h
   else FENERF_BY_RAY_SAMPLES(p.M, composite_kernel, false, p.BR, stream, p);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail2(e, "composite launch");
+  return check_launch("composite launch");
 }
 
 int launch_resample(long long BR, int N, const float* z, const float* w, const float* u, float* zf, void* stream) {
@@ -401,8 +391,7 @@ int launch_resample(long long BR, int N, const float* z, const float* w, const f
   if (N > 256) hipLaunchKernelGGL((resample_kernel<false, 8>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, BR, N - 2, N, z, w, u, zf);
   else if (N > 128) hipLaunchKernelGGL((resample_kernel<false, 4>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, BR, N - 2, N, z, w, u, zf);
   else hipLaunchKernelGGL((resample_kernel<false, 2>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, BR, N - 2, N, z, w, u, zf);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail2(e, "resample launch");
+  return check_launch("resample launch");
 }
 
 int launch_sample_pdf(long long BR, int K, int NS, const float* bins, const float* w, const float* u, float* out, void* stream) {
@@ -412,8 +401,7 @@ int launch_sample_pdf(long long BR, int K, int NS, const float* bins, const floa
   if (K > 255 || NS > 256) hipLaunchKernelGGL((resample_kernel<true, 8>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, BR, K, NS, bins, w, u, out);
   else if (K > 127 || NS > 128) hipLaunchKernelGGL((resample_kernel<true, 4>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, BR, K, NS, bins, w, u, out);
   else hipLaunchKernelGGL((resample_kernel<true, 2>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, BR, K, NS, bins, w, u, out);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail2(e, "sample_pdf launch");
+  return check_launch("sample_pdf launch");
 }
 
 }  // namespace fenerf

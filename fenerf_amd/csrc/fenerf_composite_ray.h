@@ -9,18 +9,13 @@
 #include <hip/hip_runtime.h>
 
 #include "fenerf_internal.h"
+#include "fenerf_lane.h"
 
 namespace fenerf {
 
 // MAXM (template parameter: 128 in the fused render launch, 128 ... 1024 in the stand-alone kernels): samples per ray handled by one wave;
 // SLOTS = MAXM / 64 samples per lane: slot s of lane l is sample 64 s + l (slots past M are skipped, and a skipped slot contributes exact
 // zeros: the result does not depend on MAXM).  The launchers pick the smallest that fits (LDS and registers).
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // inclusive scans across the 64 lanes
 __device__ __forceinline__ float wave_scan_mul(float v, int lane) {

@@ -13,6 +13,7 @@
 // (fenerf_amd/grid_det_emulation.py).
 #include <hip/hip_runtime.h>
 
+#include "fenerf_grid.h"
 #include "fenerf_internal.h"
 
 #pragma clang fp contract(off)
@@ -52,16 +53,9 @@ __global__ __launch_bounds__(256) void det_max_kernel(long long n, const float* 
   }
 }
 
-// the 8 trilinear corners of a point (sample_from_3dgrid: zeros padding, align_corners=True), as grid_backward_kernel computes them
-struct Corners { float ix, iy, iz, x0, y0, z0; };
-__device__ __forceinline__ Corners corners_of(const float* p, float box_scale, int gd, int gh, int gw) {
-  Corners c;
-  const float qx = p[0] * box_scale, qy = p[1] * box_scale, qz = p[2] * box_scale;
-  c.ix = ((qx + 1.f) / 2.f) * (float)(gw - 1);
-  c.iy = ((qy + 1.f) / 2.f) * (float)(gh - 1);
-  c.iz = ((qz + 1.f) / 2.f) * (float)(gd - 1);
-  c.x0 = floorf(c.ix); c.y0 = floorf(c.iy); c.z0 = floorf(c.iz);
-  return c;
+// the grid cell of a point: UniformBoxWarp, then fenerf_grid.h
+__device__ __forceinline__ GridCell cell_of(const float* p, float box_scale, int gd, int gh, int gw) {
+  return grid_cell(p[0] * box_scale, p[1] * box_scale, p[2] * box_scale, gd, gh, gw);
 }
 
 // one thread per (row, channel): the 32 lanes of a row add into one voxel's 256-B line of int64 sums per corner
@@ -74,22 +68,14 @@ __global__ __launch_bounds__(256) void det_scatter_kernel(long long rows, const 
     if (g == 0.f || !finite_bits(__float_as_uint(g))) continue;      // zero rows add nothing; non-finite values: pass 4
     const long long pt = i >> 5;
     const int ch = (int)(i & 31);
-    const Corners k = corners_of(points + pt * 3, box_scale, gd, gh, gw);
+    const GridCell k = cell_of(points + pt * 3, box_scale, gd, gh, gw);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      const int cz = c >> 2, cy = (c >> 1) & 1, cx = c & 1;
-      const float xi = k.x0 + cx, yi = k.y0 + cy, zi = k.z0 + cz;
-      const float wx = cx ? (k.ix - k.x0) : (k.x0 + 1.f - k.ix);
-      const float wy = cy ? (k.iy - k.y0) : (k.y0 + 1.f - k.iy);
-      const float wz = cz ? (k.iz - k.z0) : (k.z0 + 1.f - k.iz);
-      const bool ok = xi >= 0.f && xi <= (float)(gw - 1) && yi >= 0.f && yi <= (float)(gh - 1) && zi >= 0.f && zi <= (float)(gd - 1);
-      if (ok) {
-        const float v = g * (wx * wy * wz);
+      const GridCorner n = grid_corner(k, c);
+      if (n.ok) {
+        const float v = g * (n.wx * n.wy * n.wz);
         const long long q = (long long)rint((double)v * scale);
-        if (q != 0) {
-          const long long vox = ((long long)(int)zi * gh + (int)yi) * gw + (int)xi;
-          atomicAdd(acc + vox * 32 + ch, (unsigned long long)q);     // two's complement: the signed sum
-        }
+        if (q != 0) atomicAdd(acc + grid_voxel(k, n) * 32 + ch, (unsigned long long)q);     // two's complement: the signed sum
       }
     }
   }
@@ -132,24 +118,17 @@ __global__ __launch_bounds__(256) void det_nonfinite_kernel(long long rows, cons
     if (finite_bits(__float_as_uint(d_e[i]))) continue;
     const long long pt = i >> 5;
     const int ch = (int)(i & 31);
-    const Corners k = corners_of(points + pt * 3, box_scale, gd, gh, gw);
+    const GridCell k = cell_of(points + pt * 3, box_scale, gd, gh, gw);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      const float xi = k.x0 + (c & 1), yi = k.y0 + ((c >> 1) & 1), zi = k.z0 + (c >> 2);
-      const bool ok = xi >= 0.f && xi <= (float)(gw - 1) && yi >= 0.f && yi <= (float)(gh - 1) && zi >= 0.f && zi <= (float)(gd - 1);
-      if (ok) {
-        const long long vox = ((long long)(int)zi * gh + (int)yi) * gw + (int)xi;
+      const GridCorner n = grid_corner(k, c);
+      if (n.ok) {
+        const long long vox = grid_voxel(k, n);
         out[TO_NCDHW ? (long long)ch * vox_n + vox : vox * 32 + ch] = __builtin_nanf("");
       }
     }
   }
 }
-
-int hip_fail_d(hipError_t e, const char* what) {
-  set_error(std::string(what) + ": " + hipGetErrorString(e));
-  return FENERF_E_HIP;
-}
-
 }  // namespace
 
 size_t grid_det_workspace_bytes(const FenerfModel* m) {
@@ -162,7 +141,7 @@ int launch_grid_backward_det(const FenerfModel* m, long long rows, long long den
   hipStream_t st = (hipStream_t)stream;
   const size_t ws = grid_det_workspace_bytes(m);
   hipError_t e = hipMemsetAsync(workspace, 0, ws, st);
-  if (e != hipSuccess) return hip_fail_d(e, "grid_backward_det: workspace clear");
+  if (e != hipSuccess) return hip_fail(e, "grid_backward_det: workspace clear");
   int h = 0;
   while (h < 63 && (1LL << h) < dense_rows) ++h;
   DetHeader* hdr = (DetHeader*)workspace;
@@ -184,8 +163,7 @@ int launch_grid_backward_det(const FenerfModel* m, long long rows, long long den
     if (to_ncdhw) hipLaunchKernelGGL(det_nonfinite_kernel<true>, dim3(blocks), dim3(256), 0, st, rows, points, d_e, m->box_scale, m->gd, m->gh, m->gw, hdr, out);
     else hipLaunchKernelGGL(det_nonfinite_kernel<false>, dim3(blocks), dim3(256), 0, st, rows, points, d_e, m->box_scale, m->gd, m->gh, m->gw, hdr, out);
   }
-  e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail_d(e, "grid_backward_det launch");
+  return check_launch("grid_backward_det launch");
 }
 
 }  // namespace fenerf

@@ -1,5 +1,7 @@
 // Internal declarations shared by the host API, the packer and the kernel launchers.
 #pragma once
+#include <hip/hip_runtime_api.h>
+
 #include <cstddef>
 #include <cstdint>
 #include <map>
@@ -13,6 +15,9 @@
 namespace fenerf {
 
 void set_error(const std::string& msg);
+int fail(int code, const std::string& msg);          // set_error(msg); returns code
+int hip_fail(hipError_t e, const char* what);        // set_error("<what>: <HIP's error string>"); returns FENERF_E_HIP
+int check_launch(const char* what);                  // behind a kernel launch: FENERF_OK, or hip_fail(hipGetLastError(), what)
 // Opt-in to > 64 KiB of dynamic LDS for kernel `kfn`.  hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE attribute:
 // what has been granted is remembered per (kernel, current device) under a lock, so a process that renders on several GPUs or
 // from several host threads always launches with the opt-in in place (include/fenerf.h: thread-safe per handle).

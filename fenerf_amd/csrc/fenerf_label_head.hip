@@ -13,6 +13,7 @@
 #include <string>
 
 #include "fenerf_internal.h"
+#include "fenerf_lane.h"
 
 namespace fenerf {
 namespace {
@@ -31,12 +32,6 @@ struct LabelHeadJob {
   float* S1;         // [nl][H]   W_2 W_1                  (three layers)
   float* q2;         // [H]       W_1 b_0 + b_1            (three layers)
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // out[r][j] = sum_k A[r][k] * w_j[k] (+ gc[r] * q[j]),  w_j[k] = W[j][k] (row j: ROW) or W[k][j] (column j)
 template <bool ROW>
@@ -116,9 +111,6 @@ __global__ __launch_bounds__(64) void label_head_stage2_kernel(LabelHeadJob J) {
     outer(J.S1, J.gA, J.gc, nullptr, J.H, J.nl, j, J.dW[0], J.db[0]);
   }
 }
-
-int lh_fail(int code, const std::string& msg) { set_error(msg); return code; }
-
 }  // namespace
 }  // namespace fenerf
 
@@ -128,14 +120,14 @@ extern "C" size_t fenerf_label_head_workspace_floats(int H) { return H > 0 ? (si
 
 extern "C" int fenerf_label_head_backward(int n_layers, int H, int n_lab, const float* const* W, const float* const* b, const float* g_head_w,
                                           const float* g_head_b, float* const* dW, float* const* db, float* workspace, void* stream) {
-  if (n_layers < 1 || n_layers > FENERF_MAX_LABEL_LAYERS) return lh_fail(FENERF_E_INVALID, "fenerf_label_head_backward: n_layers must be 1..3");
-  if (H < 1 || n_lab < 1 || n_lab > LH_MAX_ROWS) return lh_fail(FENERF_E_INVALID, "fenerf_label_head_backward: need H >= 1 and 1 <= n_lab <= 32");
+  if (n_layers < 1 || n_layers > FENERF_MAX_LABEL_LAYERS) return fail(FENERF_E_INVALID, "fenerf_label_head_backward: n_layers must be 1..3");
+  if (H < 1 || n_lab < 1 || n_lab > LH_MAX_ROWS) return fail(FENERF_E_INVALID, "fenerf_label_head_backward: need H >= 1 and 1 <= n_lab <= 32");
   if (!W || !b || !g_head_w || !g_head_b || !dW || !db || (n_layers == 3 && !workspace))
-    return lh_fail(FENERF_E_INVALID, "fenerf_label_head_backward: NULL pointer");
+    return fail(FENERF_E_INVALID, "fenerf_label_head_backward: NULL pointer");
   LabelHeadJob J{};
   J.n = n_layers; J.H = H; J.nl = n_lab; J.gA = g_head_w; J.gc = g_head_b;
   for (int i = 0; i < n_layers; ++i) {
-    if (!W[i] || !b[i] || !dW[i] || !db[i]) return lh_fail(FENERF_E_INVALID, "fenerf_label_head_backward: a layer's pointer is NULL");
+    if (!W[i] || !b[i] || !dW[i] || !db[i]) return fail(FENERF_E_INVALID, "fenerf_label_head_backward: a layer's pointer is NULL");
     J.W[i] = W[i]; J.b[i] = b[i]; J.dW[i] = dW[i]; J.db[i] = db[i];
   }
   hipStream_t st = (hipStream_t)stream;
@@ -143,13 +135,12 @@ extern "C" int fenerf_label_head_backward(int n_layers, int H, int n_lab, const 
   if (n_layers == 1) {      // the fold IS the layer
     hipError_t e = hipMemcpyAsync(dW[0], g_head_w, sizeof(float) * (size_t)n_lab * H, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(db[0], g_head_b, sizeof(float) * (size_t)n_lab, hipMemcpyDeviceToDevice, st);
-    return e == hipSuccess ? FENERF_OK : lh_fail(FENERF_E_HIP, std::string("label head backward copy: ") + hipGetErrorString(e));
+    return e == hipSuccess ? FENERF_OK : hip_fail(e, "label head backward copy");
   }
   if (n_layers == 3) {
     J.U1 = workspace; J.S1 = workspace + (size_t)LH_MAX_ROWS * H; J.q2 = workspace + (size_t)2 * LH_MAX_ROWS * H;
   }
   hipLaunchKernelGGL(label_head_stage1_kernel, dim3(H, n_layers), dim3(64), 0, st, J);
   if (n_layers == 3) hipLaunchKernelGGL(label_head_stage2_kernel, dim3(H, 3), dim3(64), 0, st, J);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : lh_fail(FENERF_E_HIP, std::string("label head backward launch: ") + hipGetErrorString(e));
+  return check_launch("label head backward launch");
 }

@@ -21,6 +21,7 @@
 #include <string>
 
 #include "fenerf_internal.h"
+#include "fenerf_lane.h"
 
 namespace fenerf {
 
@@ -47,11 +48,6 @@ struct MapParams {
   float* delta;                 // [n_layers - 1][B][hidden] dL/d(pre-activation) of the trunk layers
 };
 
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ float lrelu(float v) { return v > 0.f ? v : v * LRELU_SLOPE; }
 
 // The weights are cold every time (13 ms of other kernels' traffic since their last use), and a layer cannot start before the layer in
@@ -124,7 +120,7 @@ __device__ __forceinline__ void matvec_rows(const float* __restrict__ W, const f
     float res = 0.f;
 #pragma unroll
     for (int k = 0; k < RS; ++k) {
-      const float v = wave_sum_f(acc[k]);
+      const float v = wave_sum(acc[k]);
       if (lane == k) res = v;
     }
     if (lane < RS && r + lane < r1) store(r + lane, res + bl);
@@ -258,21 +254,16 @@ __global__ __launch_bounds__(256) void mapping_wgrad_kernel(MapParams P) {
   }
 }
 
-int map_fail(int code, const std::string& msg) {
-  set_error(msg);
-  return code;
-}
-
 int fill(MapParams& P, const FenerfMappingNet* net, int B) {
-  if (!net) return map_fail(FENERF_E_INVALID, "mapping network description is NULL");
-  if (net->n_layers < 2 || net->n_layers > MAP_MAX_LAYERS) return map_fail(FENERF_E_INVALID, "mapping network: n_layers must be in [2, FENERF_MAP_MAX_LAYERS]");
-  if (B <= 0 || net->z_dim <= 0 || net->hidden <= 0 || net->out_dim <= 0) return map_fail(FENERF_E_INVALID, "mapping network: B, z_dim, hidden, out_dim must be > 0");
-  if (net->hidden > 1024 || net->z_dim > 4096) return map_fail(FENERF_E_UNSUPPORTED, "mapping network: hidden <= 1024 and z_dim <= 4096");
+  if (!net) return fail(FENERF_E_INVALID, "mapping network description is NULL");
+  if (net->n_layers < 2 || net->n_layers > MAP_MAX_LAYERS) return fail(FENERF_E_INVALID, "mapping network: n_layers must be in [2, FENERF_MAP_MAX_LAYERS]");
+  if (B <= 0 || net->z_dim <= 0 || net->hidden <= 0 || net->out_dim <= 0) return fail(FENERF_E_INVALID, "mapping network: B, z_dim, hidden, out_dim must be > 0");
+  if (net->hidden > 1024 || net->z_dim > 4096) return fail(FENERF_E_UNSUPPORTED, "mapping network: hidden <= 1024 and z_dim <= 4096");
   memset(&P, 0, sizeof(P));
   P.n_layers = net->n_layers; P.B = B; P.z_dim = net->z_dim; P.hidden = net->hidden; P.out_dim = net->out_dim;
   P.S = net->out_dim >= 2048 ? 16 : (net->out_dim >= 512 ? 8 : 1);
   for (int l = 0; l < net->n_layers; ++l) {
-    if (!net->W[l] || !net->b[l]) return map_fail(FENERF_E_INVALID, "mapping network: weight / bias pointer is NULL");
+    if (!net->W[l] || !net->b[l]) return fail(FENERF_E_INVALID, "mapping network: weight / bias pointer is NULL");
     P.W[l] = net->W[l]; P.b[l] = net->b[l];
   }
   return FENERF_OK;
@@ -293,13 +284,12 @@ extern "C" int fenerf_mapping_forward(const FenerfMappingNet* net, int B, const 
   MapParams P;
   int rc = fill(P, net, B);
   if (rc) return rc;
-  if (!z || !acts || !out) return map_fail(FENERF_E_INVALID, "fenerf_mapping_forward: NULL pointer");
+  if (!z || !acts || !out) return fail(FENERF_E_INVALID, "fenerf_mapping_forward: NULL pointer");
   P.z = z; P.acts = acts; P.out = out;
   const int wmax = ((P.z_dim > P.hidden ? P.z_dim : P.hidden) + 3) & ~3;     // as the kernel rounds it: two buffers of whole float4s
   PhaseScope ph(PH_OTHER, stream);
   hipLaunchKernelGGL(mapping_forward_kernel, dim3(B, P.S), dim3(MAP_THREADS), 2 * wmax * sizeof(float), (hipStream_t)stream, P);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : map_fail(FENERF_E_HIP, std::string("mapping forward launch: ") + hipGetErrorString(e));
+  return check_launch("mapping forward launch");
 }
 
 extern "C" int fenerf_mapping_backward(const FenerfMappingNet* net, int B, const float* z, const float* acts, const float* d_out,
@@ -307,9 +297,9 @@ extern "C" int fenerf_mapping_backward(const FenerfMappingNet* net, int B, const
   MapParams P;
   int rc = fill(P, net, B);
   if (rc) return rc;
-  if (!z || !acts || !d_out || !dW || !db || !workspace) return map_fail(FENERF_E_INVALID, "fenerf_mapping_backward: NULL pointer");
+  if (!z || !acts || !d_out || !dW || !db || !workspace) return fail(FENERF_E_INVALID, "fenerf_mapping_backward: NULL pointer");
   for (int l = 0; l < P.n_layers; ++l) {
-    if (!dW[l] || !db[l]) return map_fail(FENERF_E_INVALID, "fenerf_mapping_backward: gradient pointer is NULL");
+    if (!dW[l] || !db[l]) return fail(FENERF_E_INVALID, "fenerf_mapping_backward: gradient pointer is NULL");
     P.dW[l] = dW[l]; P.db[l] = db[l];
   }
   P.z = z; P.acts = const_cast<float*>(acts); P.d_out = d_out;
@@ -323,6 +313,5 @@ extern "C" int fenerf_mapping_backward(const FenerfMappingNet* net, int B, const
   int gx = (int)((biggest + 255) / 256);
   if (gx > 4096) gx = 4096;
   hipLaunchKernelGGL(mapping_wgrad_kernel, dim3(gx, P.n_layers), dim3(256), 0, st, P);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : map_fail(FENERF_E_HIP, std::string("mapping backward launch: ") + hipGetErrorString(e));
+  return check_launch("mapping backward launch");
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "fenerf_lane.h"
 #include "fenerf_layout.h"
 #include "fenerf_trig.h"
 
@@ -108,8 +109,7 @@ __device__ __forceinline__ void film_store(const f32x16& acc, const FilmNB& fm, 
 struct LaneBits { bool b0, b1, b2, b3; };   // lane & 1, 2, 4, 8
 __device__ __forceinline__ LaneBits lane_bits(int lane) { return LaneBits{(lane & 1) != 0, (lane & 2) != 0, (lane & 4) != 0, (lane & 8) != 0}; }
 
-__device__ __forceinline__ float lane_xor1(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true)); }   // quad_perm:[1,0,3,2]
-__device__ __forceinline__ float lane_xor2(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true)); }   // quad_perm:[2,3,0,1]
+// lane_xor1 / lane_xor2: fenerf_lane.h
 __device__ __forceinline__ float lane_xor4(float x) {   // row_shl:4 into banks 0, 2; row_shr:4 into banks 1, 3
   const int xi = __builtin_bit_cast(int, x);
   int t = __builtin_amdgcn_update_dpp(0, xi, 0x104, 0xf, 0x5, true);

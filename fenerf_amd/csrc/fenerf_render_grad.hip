@@ -34,9 +34,7 @@ int launch_render_points(int B, int R, int N, long long Pp, const float* origins
                          void* stream) {
   const long long total = (long long)B * Pp;
   hipLaunchKernelGGL(render_points_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, origins, dirs, z, pts, rd, R, N, Pp, total);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("render points launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
+  return check_launch("render points launch");
 }
 
 // rows [nb][Pp][C] -> [nb][P][C] (or back, zero-filling the pad rows): the composite kernels work on unpadded rays
@@ -51,9 +49,7 @@ __global__ void pad_rows_kernel(const float* src, float* dst, long long P, long 
 int launch_pad_rows(const float* src, float* dst, long long nb, long long P, long long Pp, int C, bool to_padded, void* stream) {
   const long long total = nb * (to_padded ? Pp : P) * C;
   hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, dst, P, Pp, C, total, to_padded ? 1 : 0);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("pad rows launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
+  return check_launch("pad rows launch");
 }
 
 // dst_k += src_k for up to MULTI_ADD_MAX tensors in one launch (blockIdx.y = tensor): the sum of a later backward chunk's gradients into
@@ -73,9 +69,7 @@ int launch_multi_add(const MultiAdd& J, void* stream) {
   if (bx > 1024) bx = 1024;
   if (bx < 1) bx = 1;
   hipLaunchKernelGGL(multi_add_kernel, dim3((unsigned)bx, (unsigned)J.count), dim3(256), 0, (hipStream_t)stream, J);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("multi add launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
+  return check_launch("multi add launch");
 }
 
 // out[b][i] = a[b][i] + a[B + b][i]: the two passes of a hierarchical render share an image's FiLM parameters (four tensors, one launch)
@@ -89,9 +83,7 @@ int launch_film_fold(const FilmFold& J, void* stream) {
   long long nmax = 0;
   for (int k = 0; k < 4; ++k) nmax = (long long)J.B * J.row[k] > nmax ? (long long)J.B * J.row[k] : nmax;
   hipLaunchKernelGGL(film_fold_kernel, dim3((unsigned)((nmax + 255) / 256), 4), dim3(256), 0, (hipStream_t)stream, J);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("film fold launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
+  return check_launch("film fold launch");
 }
 
 // ---- selection step of the exact-sparsity backward (fenerf_sparse_select; generators/autograd.py SparseHierarchicalRenderFunction) ----
@@ -229,9 +221,7 @@ int launch_sparse_select(int B, int R, int N, int C, long long cap, const float*
   hipLaunchKernelGGL(sparse_scan_kernel, dim3((unsigned)B), dim3(1024), 0, (hipStream_t)stream, block_counts, (int)nblk, cap, counts, B);
   hipLaunchKernelGGL(sparse_gather_kernel, grid, dim3(256), 0, (hipStream_t)stream, d_coarse, d_fine, z_coarse, z_fine, origins, dirs, images, R, N, C,
                      cap, masks, block_counts, pts, rd, d_sel, counts);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("sparse select launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
+  return check_launch("sparse select launch");
 }
 
 }  // namespace fenerf

@@ -146,9 +146,7 @@ int launch_repack(FenerfModel* m, const float* flat, const FenerfRepackMaps* r, 
       hipLaunchKernelGGL(repack_gather_bf16_kernel, dim3(grid_for((long long)r->n_bwd_b16)), dim3(256), 0, st, flat, scale_bwd, r->scale_id, r->bwd_b16,
                          (long long)r->n_bwd_b16, reinterpret_cast<uint16_t*>(m->d_bwd_stream + r->n_bwd_f32));
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("repack launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
+  return check_launch("repack launch");
 }
 
 }  // namespace fenerf

@@ -25,6 +25,7 @@
 
 #include "fenerf_film.h"
 #include "fenerf_internal.h"
+#include "fenerf_launch.h"
 #include "fenerf_layout.h"
 #include "fenerf_mfma32.h"
 #include "fenerf_nt.h"
@@ -128,6 +129,7 @@ __global__ __launch_bounds__(256, 1) void siren_kernel(SirenParams P, int n_geo,
 #pragma unroll
     for (int i = 0; i < 16; ++i) e[i] = 0.f;
     if (GRID) {
+      // the corner walk of fenerf_grid.h (the definition this must match), in place: any inlined form moves this kernel's prologue
       const float ix = ((qx + 1.f) / 2.f) * (float)(P.gw - 1);
       const float iy = ((qy + 1.f) / 2.f) * (float)(P.gh - 1);
       const float iz = ((qz + 1.f) / 2.f) * (float)(P.gd - 1);
@@ -326,11 +328,6 @@ __global__ __launch_bounds__(256) void grid_transpose_kernel(const float* src, f
   }
 }
 
-static int hip_fail(hipError_t e, const char* what) {
-  set_error(std::string(what) + ": " + hipGetErrorString(e));
-  return FENERF_E_HIP;
-}
-
 int launch_film_prep(const FenerfModel* m, long long B, const float* fg, const float* pg, const float* fa, const float* pa,
                      float* fp, float* pp, void* stream, bool for_f32_kernel, bool twice) {
   const long long total = (long long)B * m->L * m->H;
@@ -340,23 +337,20 @@ int launch_film_prep(const FenerfModel* m, long long B, const float* fg, const f
   hipLaunchKernelGGL(film_prep_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, B, m->H, m->n_geo, m->n_color, fg,
                      pg, fa, pa, cst + CONST_FILM_BIAS, f16 ? m->d_consts + CONST_FILM_BIAS + (size_t)m->L * m->H : nullptr, fp, pp,
                      twice ? total : 0LL);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail(e, "film_prep launch");
+  return check_launch("film_prep launch");
 }
 
 int launch_grid_relayout(const float* src, float* dst, int C, int D, int Hh, int W, void* stream) {
   const long long vox = (long long)D * Hh * W;
   if (C != 32) { set_error("feature grid must have 32 channels"); return FENERF_E_UNSUPPORTED; }
   hipLaunchKernelGGL(grid_transpose_kernel<true>, dim3((unsigned)((vox + 63) / 64)), dim3(256), 0, (hipStream_t)stream, src, dst, vox);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail(e, "grid_relayout launch");
+  return check_launch("grid_relayout launch");
 }
 
 int launch_grid_unlayout(const float* src_cl, float* dst_ncdhw, int D, int Hh, int W, void* stream) {
   const long long vox = (long long)D * Hh * W;
   hipLaunchKernelGGL(grid_transpose_kernel<false>, dim3((unsigned)((vox + 63) / 64)), dim3(256), 0, (hipStream_t)stream, src_cl, dst_ncdhw, vox);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail(e, "grid_unlayout launch");
+  return check_launch("grid_unlayout launch");
 }
 
 template <int H, bool GRID, bool SAVE>
@@ -365,20 +359,9 @@ static int launch_siren_t(const FenerfModel* m, const SirenParams& p, void* stre
   const size_t lds = (size_t)4 * ((H / 8) * 64 + stage_f4) * sizeof(float4);
   auto kfn = siren_kernel<H, GRID, SAVE>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
-  const long long ntiles = (p.P + 31) / 32;
-  long long blocks = (ntiles + 3) / 4;
-  if (blocks > m->num_cus) blocks = m->num_cus;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail(e, "siren launch");
-}
-
-template <int H>
-static int launch_siren_h(const FenerfModel* m, const SirenParams& p, void* stream) {
-  const bool g = m->grid_ch != 0;
-  if (p.tape) return g ? launch_siren_t<H, true, true>(m, p, stream) : launch_siren_t<H, false, true>(m, p, stream);
-  return g ? launch_siren_t<H, true, false>(m, p, stream) : launch_siren_t<H, false, false>(m, p, stream);
+  const unsigned blocks = persistent_blocks((p.P + 31) / 32, 4, m->num_cus);    // a 32-point tile per wave
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C);
+  return check_launch("siren launch");
 }
 
 int launch_siren(const FenerfModel* m, const SirenParams& p, void* stream) {
@@ -389,16 +372,11 @@ int launch_siren(const FenerfModel* m, const SirenParams& p, void* stream) {
 
 int launch_siren_f32(const FenerfModel* m, const SirenParams& p, void* stream) {
   if (p.P <= 0) return FENERF_OK;
-  switch (m->H) {
-    case 32: return launch_siren_h<32>(m, p, stream);
-    case 64: return launch_siren_h<64>(m, p, stream);
-    case 96: return launch_siren_h<96>(m, p, stream);
-    case 128: return launch_siren_h<128>(m, p, stream);
-    case 192: return launch_siren_h<192>(m, p, stream);
-    case 256: return launch_siren_h<256>(m, p, stream);
-  }
-  set_error("unsupported hidden_dim");
-  return FENERF_E_UNSUPPORTED;
+  return dispatch_width(m->H, m->grid_ch != 0, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value;
+    constexpr bool GRID = decltype(g)::value;
+    return p.tape ? launch_siren_t<H, GRID, true>(m, p, stream) : launch_siren_t<H, GRID, false>(m, p, stream);
+  });
 }
 
 }  // namespace fenerf

@@ -15,13 +15,14 @@
 
 #include <type_traits>
 
+#include "fenerf_grid.h"
 #include "fenerf_internal.h"
+#include "fenerf_launch.h"
 #include "fenerf_layout.h"
 #include "fenerf_mfma32.h"
 #include "fenerf_nt.h"
 
 namespace fenerf {
-
 
 struct TapeNB { float a[16]; };
 // pre-FiLM accumulators of n-block nb for this lane from the forward's register dump (fenerf_layout.h "Tape"):
@@ -263,29 +264,13 @@ __global__ void grid_backward_kernel(long long P, const float* points, float box
     const int ch = (int)(i & 31);
     const float g = d_e[i];
     const float qx = points[pt * 3 + 0] * box_scale, qy = points[pt * 3 + 1] * box_scale, qz = points[pt * 3 + 2] * box_scale;
-    const float ix = ((qx + 1.f) / 2.f) * (float)(gw - 1);
-    const float iy = ((qy + 1.f) / 2.f) * (float)(gh - 1);
-    const float iz = ((qz + 1.f) / 2.f) * (float)(gd - 1);
-    const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
+    const GridCell k = grid_cell(qx, qy, qz, gd, gh, gw);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      const int cz = c >> 2, cy = (c >> 1) & 1, cx = c & 1;
-      const float xi = x0 + cx, yi = y0 + cy, zi = z0 + cz;
-      const float wx = cx ? (ix - x0) : (x0 + 1.f - ix);
-      const float wy = cy ? (iy - y0) : (y0 + 1.f - iy);
-      const float wz = cz ? (iz - z0) : (z0 + 1.f - iz);
-      const bool ok = xi >= 0.f && xi <= (float)(gw - 1) && yi >= 0.f && yi <= (float)(gh - 1) && zi >= 0.f && zi <= (float)(gd - 1);
-      if (ok) {
-        const long long vox = ((long long)(int)zi * gh + (int)yi) * gw + (int)xi;
-        unsafeAtomicAdd(d_grid_cl + vox * 32 + ch, g * (wx * wy * wz));
-      }
+      const GridCorner n = grid_corner(k, c);
+      if (n.ok) unsafeAtomicAdd(d_grid_cl + grid_voxel(k, n) * 32 + ch, g * (n.wx * n.wy * n.wz));
     }
   }
-}
-
-static int hip_fail_b(hipError_t e, const char* what) {
-  set_error(std::string(what) + ": " + hipGetErrorString(e));
-  return FENERF_E_HIP;
 }
 
 int launch_grid_backward(const FenerfModel* m, long long P, const float* points, const float* d_e, float* d_grid_cl, void* stream) {
@@ -294,8 +279,7 @@ int launch_grid_backward(const FenerfModel* m, long long P, const float* points,
   if (blocks > 65536) blocks = 65536;
   hipLaunchKernelGGL(grid_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, P, points, m->box_scale, d_e,
                      d_grid_cl, m->gd, m->gh, m->gw);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail_b(e, "grid_backward launch");
+  return check_launch("grid_backward launch");
 }
 
 template <int H, bool GRID>
@@ -303,28 +287,14 @@ static int launch_bwd_t(const FenerfModel* m, const SirenBwdParams& p, void* str
   const size_t lds = (size_t)4 * ((H / 8) * 64) * sizeof(float4);
   auto kfn = siren_bwd_kernel<H, GRID>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
-  const long long ntiles = (p.P + 31) / 32;
-  long long blocks = (ntiles + 3) / 4;
-  if (blocks > launch_cus(m)) blocks = launch_cus(m);
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail_b(e, "siren backward launch");
+  const unsigned blocks = persistent_blocks((p.P + 31) / 32, 4, launch_cus(m));    // a 32-point tile per wave
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C);
+  return check_launch("siren backward launch");
 }
 
 int launch_siren_backward(const FenerfModel* m, const SirenBwdParams& p, void* stream) {
   if (p.P <= 0) return FENERF_OK;
-  const bool g = m->grid_ch != 0;
-  switch (m->H) {
-    case 32: return g ? launch_bwd_t<32, true>(m, p, stream) : launch_bwd_t<32, false>(m, p, stream);
-    case 64: return g ? launch_bwd_t<64, true>(m, p, stream) : launch_bwd_t<64, false>(m, p, stream);
-    case 96: return g ? launch_bwd_t<96, true>(m, p, stream) : launch_bwd_t<96, false>(m, p, stream);
-    case 128: return g ? launch_bwd_t<128, true>(m, p, stream) : launch_bwd_t<128, false>(m, p, stream);
-    case 192: return g ? launch_bwd_t<192, true>(m, p, stream) : launch_bwd_t<192, false>(m, p, stream);
-    case 256: return g ? launch_bwd_t<256, true>(m, p, stream) : launch_bwd_t<256, false>(m, p, stream);
-  }
-  set_error("unsupported hidden_dim");
-  return FENERF_E_UNSUPPORTED;
+  return dispatch_width(m->H, m->grid_ch != 0, [&](auto h, auto g) { return launch_bwd_t<decltype(h)::value, decltype(g)::value>(m, p, stream); });
 }
 
 }  // namespace fenerf

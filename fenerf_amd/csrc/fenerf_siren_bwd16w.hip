@@ -45,13 +45,13 @@
 #include <string>
 #include <type_traits>
 
+#include "fenerf_grid.h"
 #include "fenerf_internal.h"
+#include "fenerf_launch.h"
 #include "fenerf_layout.h"
 #include "fenerf_trig.h"
+#include "fenerf_wave16.h"
 
-#ifndef FENERF_WAVE_HALF_COPIES
-#define FENERF_WAVE_HALF_COPIES 1     // 0: the wave half as a run-time flag inside the stream loop (rounds 3-5); A/B builds only
-#endif
 // Timing ablations of the stage bodies (tools/exp/chain_ablations.sh; WRONG results): 1 = no FiLM sums (the B items: row butterfly, LDS
 // hand-over, combine), 2 = no d(theta) stores, 4 = tape DMA from one L2-resident block instead of the tile's (same instruction, same queue)
 #ifndef FENERF_CHAIN_SETPRIO
@@ -67,22 +67,16 @@
 namespace fenerf {
 namespace bw16 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace wave16;
+
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 #define MFMA16B(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
-#define MFMA32W(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-constexpr int CH = FENERF_CH;        // entries (KiB) per chunk = one A operand per wave
-constexpr int DPF = FENERF_DPF;      // chunks in flight ahead of the chunk being consumed
-constexpr int NSLOT = FENERF_NSLOT;  // LDS ring slots
-constexpr int NWAVE = 8;
-static_assert(CH == NWAVE, "one 1-KiB A operand per wave and chunk");
 static_assert(CH == FENERF_PF16, "bodies of the backward stream are whole chunks");
-static_assert(NSLOT == 8 && NSLOT >= DPF + 2, "slot arithmetic below is & 7; a slot is refilled two barriers after its last reads");
+static_assert(NSLOT == 8, "slot arithmetic below is & 7");
 
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -92,37 +86,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-__device__ __forceinline__ int opaque(int v) {   // fenerf_siren_f16w.hip: keeps lane-derived address arithmetic local
-  asm volatile("" : "+v"(v));
-  return v;
-}
-// a wave-uniform pointer the compiler computed with vector instructions (64-bit multiplies) -> SGPRs, for the "s" operands below
-template <class T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-#define LDS_FENCE() asm volatile("" ::: "memory")
-
-// LDS-DMA of one KiB: lane i's 16 bytes at g_uniform + voff  ->  lds_uniform + 16 i
-__device__ __forceinline__ void glds_1k_s(const void* g_uniform, unsigned voff, unsigned lds_uniform) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %1"
-      :
-      : "v"(voff), "s"(g_uniform), "s"(lds_uniform)
-      : "memory");
-}
+// glds_1k_s (fenerf_wave16.h) with the nt cache policy: the tape DMAs
 __device__ __forceinline__ void glds_1k_s_nt(const void* g_uniform, unsigned voff, unsigned lds_uniform) {
   asm volatile(
       "s_mov_b32 m0, %2\n\t"
@@ -132,17 +96,7 @@ __device__ __forceinline__ void glds_1k_s_nt(const void* g_uniform, unsigned vof
       : "v"(voff), "s"(g_uniform), "s"(lds_uniform)
       : "memory");
 }
-// fire-and-forget stores, uniform base + 32-bit lane offset.  The s_nop is the hazard slot the compiler would insert behind a
-// store of more than 8 bytes whose data registers the next VALU instruction overwrites -- it does not look inside an asm.
-#ifndef FENERF_ST_POLICY
-#define FENERF_ST_POLICY "nt"      // cache policy of the fire-and-forget tape / d(theta) stores (A/B builds: profiles/r06_store_policy_ab.txt)
-#endif
-__device__ __forceinline__ void st_f4_nt(const void* g_uniform, unsigned voff, const f32x4& v) {
-  asm volatile("global_store_dwordx4 %0, %1, %2 " FENERF_ST_POLICY "\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(g_uniform) : "memory");
-}
-__device__ __forceinline__ void st_u4_nt(const void* g_uniform, unsigned voff, const u32x4& v) {
-  asm volatile("global_store_dwordx4 %0, %1, %2 " FENERF_ST_POLICY "\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(g_uniform) : "memory");
-}
+// the 8-byte fire-and-forget store of the FiLM sums (no hazard slot needed up to 8 bytes), default cache policy
 __device__ __forceinline__ void st_f2(const void* g_uniform, unsigned voff, const f32x2& v) {
   asm volatile("global_store_dwordx2 %0, %1, %2" : : "v"(voff), "v"(v), "s"(g_uniform) : "memory");
 }
@@ -199,24 +153,15 @@ struct WStream {
 
 __device__ __forceinline__ void ws_issue(WStream& w, int slot) {
   const unsigned m0 = w.ring_lds + (unsigned)slot * (CH * 1024);
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %1"
-      :
-      : "v"(w.voff), "s"(w.g_next), "s"(m0)
-      : "memory");
+  glds_1k_s(reinterpret_cast<const void*>(w.g_next), w.voff, m0);
   const unsigned long long nx = w.g_next + CH * 1024;
   w.g_next = nx == w.g_end ? w.g_begin : nx;      // the stream restarts for the next tile
 }
 
-// A operands of one k32-step (both row tiles): ring slot layout = operand index (spl * 2 + rt) * 2 + hl, 1 KiB each
-struct AK { float4 hi[2], lo[2]; };
 __device__ __forceinline__ AK ws_read(const WStream& w, int slot, int spl) {
   AK a;
-  const float4* p = reinterpret_cast<const float4*>(w.ring_lane + slot * (CH * 1024) + spl * 4096);
-  a.lo[0] = p[1 * 64]; a.lo[1] = p[3 * 64];
-  a.hi[0] = p[0 * 64]; a.hi[1] = p[2 * 64];
+  ring_read_lo(a, w.ring_lane, slot, spl);
+  ring_read_hi(a, w.ring_lane, slot, spl);
   return a;
 }
 
@@ -233,8 +178,6 @@ __device__ __forceinline__ void kstep_mfma(f32x4 (&acc)[2], const AK& a, const b
   acc[1] = MFMA16B(as_bf16x8(a.hi[1]), bh, acc[1]);
 }
 
-__device__ __forceinline__ float lane_xor1(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true)); }   // quad_perm:[1,0,3,2]
-__device__ __forceinline__ float lane_xor2(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true)); }   // quad_perm:[2,3,0,1]
 __device__ __forceinline__ float lane_ror4(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x124, 0xf, 0xf, true)); }  // row_ror:4
 __device__ __forceinline__ float lane_ror8(float x) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xf, 0xf, true)); }  // row_ror:8
 
@@ -329,7 +272,7 @@ __device__ __forceinline__ EpiOut epi_compute(const f32x4& acc, const EpiIn& q, 
     const f32x2 rr = {rem[2 * j], rem[2 * j + 1]};
     l2[j] = __builtin_bit_cast(unsigned, __builtin_convertvector(rr, bf16x2));
   }
-  // pinned here: without a use in this block the compiler sinks the epilogue behind the stage (fenerf_siren_f16w.hip)
+  // pinned here: without a use in this block the compiler sinks the epilogue behind the stage, keeping every n-block's values alive
   asm volatile("" : "+v"(h2[0]), "+v"(h2[1]), "+v"(l2[0]), "+v"(l2[1]));
   yh[2 * rt] = h2[0]; yh[2 * rt + 1] = h2[1];
   yl[2 * rt] = l2[0]; yl[2 * rt + 1] = l2[1];
@@ -369,7 +312,7 @@ __global__ __launch_bounds__(512, 2) void siren_bwd16w_kernel(SirenBwdParams P, 
   wait_vmcnt<0>();
   __syncthreads();
 
-  // ---- the DMA's re-tiling permutation (fenerf_siren_f16w.hip header): this wave fetches operand (spl, rt, hl) of every chunk
+  // ---- the DMA's re-tiling permutation (derived in the header of fenerf_siren_f16w.hip): this wave fetches operand (spl, rt, hl) of every chunk
   WStream ws;
   {
     const int spl = wave >> 2, rt = (wave >> 1) & 1, hl = wave & 1;
@@ -645,25 +588,15 @@ __global__ __launch_bounds__(512, 2) void siren_bwd16w_kernel(SirenBwdParams P, 
       const int lq = opaque(lane);
       const float* eblk = reinterpret_cast<const float*>(ext_wave);
       const int ch = lq & 31;
-      const float gwf = (float)(P.gw - 1), ghf = (float)(P.gh - 1), gdf = (float)(P.gd - 1);
       for (int it = 0; it < count && scat_next < 8; ++it, ++scat_next) {
         const int pi = 2 * scat_next + (lq >> 5);
         const float gv = eblk[pi * 32 + ch];
         const float qx = pts_wave[pi * 3 + 0] * P.box_scale, qy = pts_wave[pi * 3 + 1] * P.box_scale, qz = pts_wave[pi * 3 + 2] * P.box_scale;
-        const float ix = ((qx + 1.f) / 2.f) * gwf, iy = ((qy + 1.f) / 2.f) * ghf, iz = ((qz + 1.f) / 2.f) * gdf;
-        const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
+        const GridCell k = grid_cell(qx, qy, qz, P.gd, P.gh, P.gw);
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-          const int cz = c >> 2, cy = (c >> 1) & 1, cx = c & 1;
-          const float xi = x0 + cx, yi = y0 + cy, zi = z0 + cz;
-          const float wx = cx ? (ix - x0) : (x0 + 1.f - ix);
-          const float wy = cy ? (iy - y0) : (y0 + 1.f - iy);
-          const float wz = cz ? (iz - z0) : (z0 + 1.f - iz);
-          const bool ok = xi >= 0.f && xi <= gwf && yi >= 0.f && yi <= ghf && zi >= 0.f && zi <= gdf;
-          if (ok) {
-            const long long vox = ((long long)(int)zi * P.gh + (int)yi) * P.gw + (int)xi;
-            unsafeAtomicAdd(P.d_grid_cl + vox * 32 + ch, gv * (wx * wy * wz));
-          }
+          const GridCorner cn = grid_corner(k, c);
+          if (cn.ok) unsafeAtomicAdd(P.d_grid_cl + grid_voxel(k, cn) * 32 + ch, gv * (cn.wx * cn.wy * cn.wz));
         }
       }
     };
@@ -881,11 +814,6 @@ __global__ __launch_bounds__(512, 2) void siren_bwd16w_kernel(SirenBwdParams P, 
   __builtin_amdgcn_s_barrier();
 }
 
-static int hip_fail16w(hipError_t e, const char* what) {
-  set_error(std::string(what) + ": " + hipGetErrorString(e));
-  return FENERF_E_HIP;
-}
-
 template <int H, bool GRID, bool WGS, bool BD>
 static int launch_w(const FenerfModel* m, const SirenBwdParams& p, void* stream) {
   constexpr int TAPE = FENERF_BW16_T16;
@@ -894,13 +822,9 @@ static int launch_w(const FenerfModel* m, const SirenBwdParams& p, void* stream)
                      (size_t)NWAVE * 2048 + (WGS ? (size_t)3 * NWAVE * 32 * 8 : 0) + (size_t)NWAVE * 48 * 4;   // ring + FiLM buffers + tape staging + rgb head^T + head B operands + FiLM-sum buffers + tile points
   auto kfn = siren_bwd16w_kernel<H, GRID, WGS, BD, TAPE>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
-  const long long ntiles = (p.P + 15) / 16;
-  long long blocks = (ntiles + NWAVE - 1) / NWAVE;
-  if (blocks > launch_cus(m)) blocks = launch_cus(m);
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(512), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail16w(e, "siren bf16 backward (16-point waves) launch");
+  const unsigned blocks = persistent_blocks((p.P + 15) / 16, NWAVE, launch_cus(m));    // a 16-point tile per wave
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C);
+  return check_launch("siren bf16 backward (16-point waves) launch");
 }
 template <int H, bool GRID>
 static int launch_t(const FenerfModel* m, const SirenBwdParams& p, void* stream) {
@@ -954,17 +878,7 @@ int launch_siren_backward16w(const FenerfModel* m, const SirenBwdParams& p, void
   if (p.tape_format == FENERF_TAPE_F32_W && p.d_t) return launch_siren_backward16w_w(m, p, stream);     // (FiLM-only launches need the second sum)
 #endif
   if (p.P <= 0) return FENERF_OK;
-  const bool g = m->grid_ch != 0;
-  switch (m->H) {
-    case 32: return g ? bw16::launch_t<32, true>(m, p, stream) : bw16::launch_t<32, false>(m, p, stream);
-    case 64: return g ? bw16::launch_t<64, true>(m, p, stream) : bw16::launch_t<64, false>(m, p, stream);
-    case 96: return g ? bw16::launch_t<96, true>(m, p, stream) : bw16::launch_t<96, false>(m, p, stream);
-    case 128: return g ? bw16::launch_t<128, true>(m, p, stream) : bw16::launch_t<128, false>(m, p, stream);
-    case 192: return g ? bw16::launch_t<192, true>(m, p, stream) : bw16::launch_t<192, false>(m, p, stream);
-    case 256: return g ? bw16::launch_t<256, true>(m, p, stream) : bw16::launch_t<256, false>(m, p, stream);
-  }
-  set_error("unsupported hidden_dim");
-  return FENERF_E_UNSUPPORTED;
+  return dispatch_width(m->H, m->grid_ch != 0, [&](auto h, auto g) { return bw16::launch_t<decltype(h)::value, decltype(g)::value>(m, p, stream); });
 }
 
 }  // namespace fenerf

@@ -47,85 +47,27 @@
 #include "fenerf_composite_ray.h"
 #include "fenerf_film.h"
 #include "fenerf_internal.h"
+#include "fenerf_launch.h"
 #include "fenerf_layout.h"
 #include "fenerf_trig.h"
-
+#include "fenerf_wave16.h"
 
 namespace fenerf {
 namespace w16 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace wave16;
+
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef _Float16 half2 __attribute__((ext_vector_type(2)));
 
 #define MFMA16W(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
-#define MFMA32W(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-constexpr int CH = FENERF_CH;        // old entries (KiB) per chunk = one A operand per wave
-constexpr int DPF = FENERF_DPF;      // chunks in flight ahead of the chunk being consumed
-constexpr int NSLOT = FENERF_NSLOT;  // LDS ring slots; every stage is a whole number of ring revolutions (packer)
-constexpr int NWAVE = 8;
-static_assert(CH == NWAVE, "one 1-KiB A operand per wave and chunk");
-static_assert(NSLOT >= DPF + 2, "a slot is refilled two barriers after its last reader issued its reads");
 
 __device__ __forceinline__ half8 as_half8(const float4& v) { return __builtin_bit_cast(half8, v); }
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-// LDS-DMA of one KiB: lane i's 16 bytes at g_lane  ->  lds_uniform + 16 i.  Inline asm on purpose: with the builtin hipcc
-// tracks the DMA as a pending LDS write and drains the queue (vmcnt(0)) before every ring read.
-__device__ __forceinline__ void glds_1k(const char* g_lane, unsigned lds_uniform) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, off"
-      :
-      : "v"(g_lane), "s"(lds_uniform)
-      : "memory");
-}
-// saddr form: lane i's 16 bytes at g_uniform + voff  ->  lds_uniform + 16 i  (one VGPR of address instead of two)
-__device__ __forceinline__ void glds_1k_s(const void* g_uniform, unsigned voff, unsigned lds_uniform) {
-  asm volatile(
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %0, %1"
-      :
-      : "v"(voff), "s"(g_uniform), "s"(lds_uniform)
-      : "memory");
-}
-// An opaque copy of a lane-derived value.  LICM hoists lane-only address arithmetic out of the tile loop, where it stays live
-// through every layer (58 such registers at first count) until the allocator spills it INTO the stream loop -- and scratch
-// traffic there would break the counted vmcnt waits.  Deriving addresses from a fresh opaque copy at each use site keeps
-// them local.
-__device__ __forceinline__ int opaque(int v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-#define WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-// a wave-uniform pointer the compiler computed with vector instructions (64-bit multiplies) -> SGPRs, for "s" asm operands
-template <class T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {
-  const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
-}
 // Differentiable mode (forward-save): the raw accumulators of every FiLM layer leave as the tape (fenerf_layout.h "Tape": register
 // dumps of 32-point tiles; wave w of the workgroup owns half (w & 1) of tile32 = tile16 >> 1).  One fire-and-forget 1-KiB wave
-// store per (n-block, row tile): stores are not loads -- they only make the counted vmcnt waits stricter.  asm: uniform base
-// in SGPRs + one VGPR of lane offset; the s_nop is the hazard slot behind a > 8-byte store whose data registers are
-// overwritten next (the compiler does not look inside an asm).
+// store per (n-block, row tile) (st_f4_nt / st_u4_nt, fenerf_wave16.h).
 template <int MODE> struct TapeW { const char* base; };   // (tile32, layer) block of the tape (uniform), or unused
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#ifndef FENERF_ST_POLICY
-#define FENERF_ST_POLICY "nt"      // cache policy of the fire-and-forget tape / d(theta) stores (A/B builds: profiles/r06_store_policy_ab.txt)
-#endif
-__device__ __forceinline__ void st_f4_nt(const void* g_uniform, unsigned voff, const f32x4& v) {
-  asm volatile("global_store_dwordx4 %0, %1, %2 " FENERF_ST_POLICY "\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(g_uniform) : "memory");
-}
-__device__ __forceinline__ void st_u4_nt(const void* g_uniform, unsigned voff, const u32x4& v) {
-  asm volatile("global_store_dwordx4 %0, %1, %2 " FENERF_ST_POLICY "\n\ts_nop 1" : : "v"(voff), "v"(v), "s"(g_uniform) : "memory");
-}
 // SAVE = 2: the four dwords (two 16-bit phases each) of an n-block that wait for the n-block's last epilogue piece: ONE 16-byte store
 // per lane and n-block, [nb][16-point tile][lane][slot 4 rt + r] (the bf16 dump's layout, dump16_feature)
 struct TapeQ { unsigned q[4]; };
@@ -139,10 +81,6 @@ __device__ __forceinline__ unsigned phase_u16(float theta) {
   const unsigned c = __builtin_bit_cast(unsigned, v + 8388608.f) & 0xffffu;                   // RNE to an integer in the mantissa
   return !(__builtin_fabsf(theta) < __builtin_inff()) ? TAPE16_NONFINITE : (c == TAPE16_NONFINITE ? (v < 65535.f ? 0xfffeu : 0u) : c);
 }
-#define LDS_FENCE() asm volatile("" ::: "memory")
-#ifndef FENERF_WAVE_HALF_COPIES
-#define FENERF_WAVE_HALF_COPIES 1     // 0: rounds 2-5 (the wave half is a run-time flag inside the stream loop); A/B builds only
-#endif
 #ifndef FENERF_EXP_DEPHASE
 #define FENERF_EXP_DEPHASE 0          // 1: experiment, measured and dropped in round 6 (+ 8 % cycles): see chunk_step
 #endif
@@ -158,33 +96,17 @@ struct WStream {
 
 __device__ __forceinline__ void ws_issue(WStream& w, int slot) {
   const unsigned m0 = w.ring_lds + (unsigned)slot * (CH * 1024);
-  if (!w.skip)
-    asm volatile(
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, %1"
-        :
-        : "v"(w.voff), "s"(w.g_next), "s"(m0)
-        : "memory");
+  if (!w.skip) glds_1k_s(reinterpret_cast<const void*>(w.g_next), w.voff, m0);
   w.g_next += CH * 1024;
 }
 
-// A operands of one k32-step (both row tiles): ring slot layout = operand index (spl * 2 + rt) * 2 + hl, 1 KiB each
-struct AK { float4 hi[2], lo[2]; };
-__device__ __forceinline__ void ws_read_lo(AK& a, const WStream& w, int slot, int spl) {
-  const float4* p = reinterpret_cast<const float4*>(w.ring_lane + slot * (CH * 1024) + spl * 4096);
-  a.lo[0] = p[1 * 64]; a.lo[1] = p[3 * 64];
-}
-__device__ __forceinline__ void ws_read_hi(AK& a, const WStream& w, int slot, int spl) {
-  const float4* p = reinterpret_cast<const float4*>(w.ring_lane + slot * (CH * 1024) + spl * 4096);
-  a.hi[0] = p[0 * 64]; a.hi[1] = p[2 * 64];
-}
+// A operands of one k32-step from the ring (LO = false: the weight lo halves are not read)
 template <bool LO = true>
 __device__ __forceinline__ AK ws_read(const WStream& w, int slot, int spl) {
   AK a;
-  if (LO) ws_read_lo(a, w, slot, spl);
+  if (LO) ring_read_lo(a, w.ring_lane, slot, spl);
   else { a.lo[0] = make_float4(0.f, 0.f, 0.f, 0.f); a.lo[1] = a.lo[0]; }
-  ws_read_hi(a, w, slot, spl);
+  ring_read_hi(a, w.ring_lane, slot, spl);
   return a;
 }
 
@@ -202,7 +124,7 @@ __device__ __forceinline__ void ws_step(WStream& w, int i, bool early) {
   // costs 8 % of the kernel at full clock, profiles/r02_siren16w_experiments.md.)
   const bool sync = (i & 1) == 0;
   if (sync) {
-    WAIT_VMCNT(DPF - 3);
+    wait_vmcnt<DPF - 3>();
     __builtin_amdgcn_s_barrier();
   }
   LDS_FENCE();
@@ -426,7 +348,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     const unsigned* src = reinterpret_cast<const unsigned*>(threadIdx.x < 256 ? &F.coarse : &F.final_);
     if (t < NW) reinterpret_cast<unsigned*>(ray_par + (threadIdx.x >> 8))[t] = src[t];
   }
-  WAIT_VMCNT(0);
+  wait_vmcnt<0>();
   __syncthreads();
 
   // ---- the DMA's re-tiling permutation (header): this wave fetches operand (spl, rt, hl) = wave bits of every chunk
@@ -469,7 +391,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
   // ---- prime the shared stream: chunks 0..D-1 in flight, first k32-step of chunk 0 in registers
 #pragma unroll
   for (int i = 0; i < DPF; ++i) ws_issue(ws, i);
-  WAIT_VMCNT(DPF - 1);
+  wait_vmcnt<DPF - 1>();
   __builtin_amdgcn_s_barrier();
   LDS_FENCE();
   // Static issue priority for the second-dispatched half: between the two waves of a SIMD the arbiter prefers the older one (waves 0-3),
@@ -480,7 +402,6 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
   APipe a_cur;
   a_cur.c = ws_read<LOR>(ws, 0, 0);
   a_cur.n = ws_read<LOR>(ws, 0, 1);
-
 
   for (long long unit = o_begin + bi; unit < o_end; unit += blocks_in_x) {
   const int nsub = FUSED ? 2 * opg : 1;       // FUSED: the group's coarse octs, then its fine octs
@@ -548,6 +469,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     for (int i = 0; i < 8; ++i) e[i] = 0.f;
     if (GRID) {
       const int ch0 = 16 * (g & 1) + 8 * (g >> 1);
+      // the corner walk of fenerf_grid.h (the definition this must match), in place: any inlined form moves this kernel's prologue
       const float ix = ((qx + 1.f) / 2.f) * (float)(P.gw - 1);
       const float iy = ((qy + 1.f) / 2.f) * (float)(P.gh - 1);
       const float iz = ((qz + 1.f) / 2.f) * (float)(P.gd - 1);
@@ -600,7 +522,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       ext[0] = __builtin_bit_cast(float4, eh); ext[64] = __builtin_bit_cast(float4, el);
       ext[128] = __builtin_bit_cast(float4, dh); ext[192] = __builtin_bit_cast(float4, dl);
     }
-    WAIT_VMCNT(0);      // film 0/1 landed (own buffer, own reads: no barrier needed), point / grid loads done; once per tile
+    wait_vmcnt<0>();      // film 0/1 landed (own buffer, own reads: no barrier needed), point / grid loads done; once per tile
     LDS_FENCE();
 
     // f'' of FiLM layer `layer` at this lane group's first feature (p' follows FILM_F bytes behind); derived on the spot
@@ -634,7 +556,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       const TapeW<SAVE> tw = tape_of(l);
       half8 yh[KS], yl[KS];
       if (l + 1 < L) film_issue(l + 1);
-      if (SQ_CHUNKS < DPF + 2) WAIT_VMCNT(0);
+      if (SQ_CHUNKS < DPF + 2) wait_vmcnt<0>();
       if (l == n_geo) {
         // ---------------- colour layer 0: [x | grid feats | dir] -> H, then the label/sigma head on the same x -------
         const float4* ext = ext_wave + opaque(lane);
@@ -793,7 +715,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       for (int i = opaque(lane); i < 16 * C; i += 64)
         if (base + i < limit) out_dst[base + i] = stage[i];
     }
-    WAIT_VMCNT(0);   // stores may retire out of order with the DMA loads: keep them out of the counted waits
+    wait_vmcnt<0>();   // stores may retire out of order with the DMA loads: keep them out of the counted waits
     __builtin_amdgcn_wave_barrier();
     if constexpr (FUSED) {
       if (FENERF_EXP_RAY_PHASE > 0 && (sub == opg - 1 || sub == nsub - 1)) {
@@ -825,22 +747,17 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
           __builtin_amdgcn_s_barrier();
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         }
-        WAIT_VMCNT(0);      // nothing of the ray phase is in flight when the counted waits of the stream loop resume
+        wait_vmcnt<0>();      // nothing of the ray phase is in flight when the counted waits of the stream loop resume
       }
     }
   }
   }
-  WAIT_VMCNT(0);     // no LDS-DMA may land after the workgroup has released its LDS
+  wait_vmcnt<0>();     // no LDS-DMA may land after the workgroup has released its LDS
   __builtin_amdgcn_s_barrier();
   if (P.clk && threadIdx.x == 0) {   // ... and of its last
     P.clk[(size_t)blockIdx.x * 4 + 2] = __builtin_amdgcn_s_memtime();
     P.clk[(size_t)blockIdx.x * 4 + 3] = __builtin_amdgcn_s_memrealtime();
   }
-}
-
-static int hip_fail16w(hipError_t e, const char* what) {
-  set_error(std::string(what) + ": " + hipGetErrorString(e));
-  return FENERF_E_HIP;
 }
 
 static size_t lds_bytes_16w(const FenerfModel* m, int H) {
@@ -858,8 +775,7 @@ static int launch_fused_t(const FenerfModel* m, const SirenParams& p, const Fuse
   auto kfn = siren16w_kernel<H, GRID, 0, true>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
   hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(512), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C, F);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail16w(e, "fused render launch");
+  return check_launch("fused render launch");
 }
 
 template <int H, bool GRID, int SAVE, int TERMS2 = 0>
@@ -867,70 +783,24 @@ static int launch_t(const FenerfModel* m, const SirenParams& p, void* stream) {
   const size_t lds = lds_bytes_16w(m, H);
   auto kfn = siren16w_kernel<H, GRID, SAVE, false, TERMS2>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
-  const long long ntiles = (p.P + 15) / 16;
-  long long blocks = (ntiles + NWAVE - 1) / NWAVE;
-  if (blocks > m->num_cus) blocks = m->num_cus;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(512), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C, FuseArgs<false>{});
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hip_fail16w(e, "siren16w launch");
+  const unsigned blocks = persistent_blocks((p.P + 15) / 16, NWAVE, m->num_cus);    // a 16-point tile per wave
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C, FuseArgs<false>{});
+  return check_launch("siren16w launch");
 }
 
 }  // namespace w16
 
 // One launch over points whose tiles do not straddle images.
 static int launch_siren16w_one(const FenerfModel* m, const SirenParams& q, void* stream) {
-  const bool g = m->grid_ch != 0;
-  if (q.tape && q.tape_format == FENERF_TAPE_U16) {   // forward-save with the 16-bit tape (round 5)
-    switch (m->H) {
-      case 32: return g ? w16::launch_t<32, true, 2>(m, q, stream) : w16::launch_t<32, false, 2>(m, q, stream);
-      case 64: return g ? w16::launch_t<64, true, 2>(m, q, stream) : w16::launch_t<64, false, 2>(m, q, stream);
-      case 96: return g ? w16::launch_t<96, true, 2>(m, q, stream) : w16::launch_t<96, false, 2>(m, q, stream);
-      case 128: return g ? w16::launch_t<128, true, 2>(m, q, stream) : w16::launch_t<128, false, 2>(m, q, stream);
-      case 192: return g ? w16::launch_t<192, true, 2>(m, q, stream) : w16::launch_t<192, false, 2>(m, q, stream);
-      case 256: return g ? w16::launch_t<256, true, 2>(m, q, stream) : w16::launch_t<256, false, 2>(m, q, stream);
-    }
-  }
-  if (q.tape) {   // forward-save: the same kernel also dumps the tape (and the sampled grid features)
-    switch (m->H) {
-      case 32: return g ? w16::launch_t<32, true, 1>(m, q, stream) : w16::launch_t<32, false, 1>(m, q, stream);
-      case 64: return g ? w16::launch_t<64, true, 1>(m, q, stream) : w16::launch_t<64, false, 1>(m, q, stream);
-      case 96: return g ? w16::launch_t<96, true, 1>(m, q, stream) : w16::launch_t<96, false, 1>(m, q, stream);
-      case 128: return g ? w16::launch_t<128, true, 1>(m, q, stream) : w16::launch_t<128, false, 1>(m, q, stream);
-      case 192: return g ? w16::launch_t<192, true, 1>(m, q, stream) : w16::launch_t<192, false, 1>(m, q, stream);
-      case 256: return g ? w16::launch_t<256, true, 1>(m, q, stream) : w16::launch_t<256, false, 1>(m, q, stream);
-    }
-  }
-  if (m->forward_mode == FENERF_FORWARD_F16X2) {
-    switch (m->H) {
-      case 32: return g ? w16::launch_t<32, true, 0, 1>(m, q, stream) : w16::launch_t<32, false, 0, 1>(m, q, stream);
-      case 64: return g ? w16::launch_t<64, true, 0, 1>(m, q, stream) : w16::launch_t<64, false, 0, 1>(m, q, stream);
-      case 96: return g ? w16::launch_t<96, true, 0, 1>(m, q, stream) : w16::launch_t<96, false, 0, 1>(m, q, stream);
-      case 128: return g ? w16::launch_t<128, true, 0, 1>(m, q, stream) : w16::launch_t<128, false, 0, 1>(m, q, stream);
-      case 192: return g ? w16::launch_t<192, true, 0, 1>(m, q, stream) : w16::launch_t<192, false, 0, 1>(m, q, stream);
-      case 256: return g ? w16::launch_t<256, true, 0, 1>(m, q, stream) : w16::launch_t<256, false, 0, 1>(m, q, stream);
-    }
-  }
-  if (m->forward_mode == FENERF_FORWARD_F16X3_COLOR_X2) {
-    switch (m->H) {
-      case 32: return g ? w16::launch_t<32, true, 0, 2>(m, q, stream) : w16::launch_t<32, false, 0, 2>(m, q, stream);
-      case 64: return g ? w16::launch_t<64, true, 0, 2>(m, q, stream) : w16::launch_t<64, false, 0, 2>(m, q, stream);
-      case 96: return g ? w16::launch_t<96, true, 0, 2>(m, q, stream) : w16::launch_t<96, false, 0, 2>(m, q, stream);
-      case 128: return g ? w16::launch_t<128, true, 0, 2>(m, q, stream) : w16::launch_t<128, false, 0, 2>(m, q, stream);
-      case 192: return g ? w16::launch_t<192, true, 0, 2>(m, q, stream) : w16::launch_t<192, false, 0, 2>(m, q, stream);
-      case 256: return g ? w16::launch_t<256, true, 0, 2>(m, q, stream) : w16::launch_t<256, false, 0, 2>(m, q, stream);
-    }
-  }
-  switch (m->H) {
-    case 32: return g ? w16::launch_t<32, true, 0>(m, q, stream) : w16::launch_t<32, false, 0>(m, q, stream);
-    case 64: return g ? w16::launch_t<64, true, 0>(m, q, stream) : w16::launch_t<64, false, 0>(m, q, stream);
-    case 96: return g ? w16::launch_t<96, true, 0>(m, q, stream) : w16::launch_t<96, false, 0>(m, q, stream);
-    case 128: return g ? w16::launch_t<128, true, 0>(m, q, stream) : w16::launch_t<128, false, 0>(m, q, stream);
-    case 192: return g ? w16::launch_t<192, true, 0>(m, q, stream) : w16::launch_t<192, false, 0>(m, q, stream);
-    case 256: return g ? w16::launch_t<256, true, 0>(m, q, stream) : w16::launch_t<256, false, 0>(m, q, stream);
-  }
-  set_error("unsupported hidden_dim");
-  return FENERF_E_UNSUPPORTED;
+  return dispatch_width(m->H, m->grid_ch != 0, [&](auto h, auto g) {
+    constexpr int H = decltype(h)::value;
+    constexpr bool GRID = decltype(g)::value;
+    if (q.tape && q.tape_format == FENERF_TAPE_U16) return w16::launch_t<H, GRID, 2>(m, q, stream);   // forward-save with the 16-bit tape (round 5)
+    if (q.tape) return w16::launch_t<H, GRID, 1>(m, q, stream);   // forward-save: the same kernel also dumps the tape (and the sampled grid features)
+    if (m->forward_mode == FENERF_FORWARD_F16X2) return w16::launch_t<H, GRID, 0, 1>(m, q, stream);
+    if (m->forward_mode == FENERF_FORWARD_F16X3_COLOR_X2) return w16::launch_t<H, GRID, 0, 2>(m, q, stream);
+    return w16::launch_t<H, GRID, 0>(m, q, stream);
+  });
 }
 
 // Geometry of the one-launch render: G rays per group, octs per group, groups, workgroups; false when this (B, R, N) cannot run fused.
@@ -957,17 +827,9 @@ int launch_render16w_fused(const FenerfModel* m, const SirenParams& p, const Fus
   F.rays_per_group = plan.rays_per_group; F.octs_per_group = plan.octs_per_group; F.groups = plan.groups;
   F.total_rays = coarse.BR;
   F.z_fine = z_fine; F.out_fine = out_fine; F.coarse = coarse; F.final_ = final_;
-  const bool g = m->grid_ch != 0;
-  switch (m->H) {
-    case 32: return g ? w16::launch_fused_t<32, true>(m, p, F, plan.blocks, stream) : w16::launch_fused_t<32, false>(m, p, F, plan.blocks, stream);
-    case 64: return g ? w16::launch_fused_t<64, true>(m, p, F, plan.blocks, stream) : w16::launch_fused_t<64, false>(m, p, F, plan.blocks, stream);
-    case 96: return g ? w16::launch_fused_t<96, true>(m, p, F, plan.blocks, stream) : w16::launch_fused_t<96, false>(m, p, F, plan.blocks, stream);
-    case 128: return g ? w16::launch_fused_t<128, true>(m, p, F, plan.blocks, stream) : w16::launch_fused_t<128, false>(m, p, F, plan.blocks, stream);
-    case 192: return g ? w16::launch_fused_t<192, true>(m, p, F, plan.blocks, stream) : w16::launch_fused_t<192, false>(m, p, F, plan.blocks, stream);
-    case 256: return g ? w16::launch_fused_t<256, true>(m, p, F, plan.blocks, stream) : w16::launch_fused_t<256, false>(m, p, F, plan.blocks, stream);
-  }
-  set_error("unsupported hidden_dim");
-  return FENERF_E_UNSUPPORTED;
+  return dispatch_width(m->H, m->grid_ch != 0, [&](auto h, auto g) {
+    return w16::launch_fused_t<decltype(h)::value, decltype(g)::value>(m, p, F, plan.blocks, stream);
+  });
 }
 
 // FENERF_PREC_F16X3 models, forward and forward-save.  Tiles must not straddle images (FiLM parameters are fetched per wave, the

@@ -12,7 +12,9 @@
 // fp32 FMAs, launched only when a caller asked for these gradients.
 #include <hip/hip_runtime.h>
 
+#include "fenerf_grid.h"
 #include "fenerf_internal.h"
+#include "fenerf_launch.h"
 #include "fenerf_layout.h"
 #include "fenerf_nt.h"
 
@@ -139,21 +141,12 @@ __global__ __launch_bounds__(256) void siren_input_grad_kernel(InputGradParams P
       float gx = 0.f, gy = 0.f, gz = 0.f;
       if (GRID && P.d_points) {      // grid_sample's backward wrt the coordinates: d ix = sum_corners (+-1) wy wz <d features, grid[corner]>
         const float qx = P.points[pt * 3 + 0] * P.box_scale, qy = P.points[pt * 3 + 1] * P.box_scale, qz = P.points[pt * 3 + 2] * P.box_scale;
-        const float ix = ((qx + 1.f) / 2.f) * (float)(P.gw - 1);
-        const float iy = ((qy + 1.f) / 2.f) * (float)(P.gh - 1);
-        const float iz = ((qz + 1.f) / 2.f) * (float)(P.gd - 1);
-        const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
+        const GridCell cell = grid_cell(qx, qy, qz, P.gd, P.gh, P.gw);
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-          const int cz = c >> 2, cy = (c >> 1) & 1, cx = c & 1;
-          const float xi = x0 + cx, yi = y0 + cy, zi = z0 + cz;
-          const float wx = cx ? (ix - x0) : (x0 + 1.f - ix);
-          const float wy = cy ? (iy - y0) : (y0 + 1.f - iy);
-          const float wz = cz ? (iz - z0) : (z0 + 1.f - iz);
-          const bool ok = xi >= 0.f && xi <= (float)(P.gw - 1) && yi >= 0.f && yi <= (float)(P.gh - 1) && zi >= 0.f && zi <= (float)(P.gd - 1);
-          if (ok) {
-            const long long vox = ((long long)(int)zi * P.gh + (int)yi) * P.gw + (int)xi;
-            const float4* gv = reinterpret_cast<const float4*>(P.grid + vox * 32);
+          const GridCorner n = grid_corner(cell, c);
+          if (n.ok) {
+            const float4* gv = reinterpret_cast<const float4*>(P.grid + grid_voxel(cell, n) * 32);
             v2f s2 = v2f{0.f, 0.f};
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -162,9 +155,9 @@ __global__ __launch_bounds__(256) void siren_input_grad_kernel(InputGradParams P
               s2 = __builtin_elementwise_fma(ae[q][2 * k + 1], v2f{v.z, v.w}, s2);
             }
             const float s = s2.x + s2.y;
-            gx = fmaf(s, (cx ? 1.f : -1.f) * wy * wz, gx);
-            gy = fmaf(s, wx * (cy ? 1.f : -1.f) * wz, gy);
-            gz = fmaf(s, wx * wy * (cz ? 1.f : -1.f), gz);
+            gx = fmaf(s, (n.cx ? 1.f : -1.f) * n.wy * n.wz, gx);
+            gy = fmaf(s, n.wx * (n.cy ? 1.f : -1.f) * n.wz, gy);
+            gz = fmaf(s, n.wx * n.wy * (n.cz ? 1.f : -1.f), gz);
           }
         }
         gx *= 0.5f * (float)(P.gw - 1); gy *= 0.5f * (float)(P.gh - 1); gz *= 0.5f * (float)(P.gd - 1);
@@ -190,13 +183,9 @@ static int launch_ig(const FenerfModel* m, int B, long long P, const InputGradPa
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
   // a workgroup's four waves walk units of 2 NP tiles of ONE image; enough workgroups per image to fill the device three deep
   const long long units = (P / 32 + 2 * NP - 1) / (2 * NP);
-  long long bx = (units + 3) / 4, cap = (3LL * launch_cus(m) + B - 1) / B;
-  if (bx > cap) bx = cap;
-  if (bx < 1) bx = 1;
-  hipLaunchKernelGGL(kfn, dim3((unsigned)bx, (unsigned)B), dim3(256), lds, (hipStream_t)stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("input gradient launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
+  const unsigned bx = persistent_blocks(units, 4, (3LL * launch_cus(m) + B - 1) / B);
+  hipLaunchKernelGGL(kfn, dim3(bx, (unsigned)B), dim3(256), lds, (hipStream_t)stream, p);
+  return check_launch("input gradient launch");
 }
 
 int launch_siren_input_grads(const FenerfModel* m, int B, long long P, const float* points, const float* fp, const float* d_t, const float* w_geo0,

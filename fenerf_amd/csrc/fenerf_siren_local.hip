@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "fenerf_internal.h"
+#include "fenerf_launch.h"
 #include "fenerf_layout.h"
 #include "fenerf_mfma32.h"
 
@@ -277,32 +278,25 @@ static int launch_local_t(const FenerfLocalModel* m, const LocalParams& p, void*
   const size_t lds = (size_t)4 * ((LOCAL_MH / 8) * 64 + (32 * 4 + 3) / 4) * sizeof(float4);
   auto kfn = siren_local_kernel<H>;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
-  const long long ntiles = (p.P + 31) / 32;
-  long long blocks = (ntiles + 3) / 4;
-  if (blocks > m->num_cus) blocks = m->num_cus;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), lds, (hipStream_t)stream, p);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_error(std::string("siren_local launch: ") + hipGetErrorString(e)); return FENERF_E_HIP; }
-  return FENERF_OK;
+  const unsigned blocks = persistent_blocks((p.P + 31) / 32, 4, m->num_cus);    // a 32-point tile per wave
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(256), lds, (hipStream_t)stream, p);
+  return check_launch("siren_local launch");
 }
 
 }  // namespace fenerf
 
 using namespace fenerf;
 
-static int local_fail(int code, const std::string& msg) { set_error(msg); return code; }
-
 extern "C" int fenerf_local_model_create(const FenerfModelDesc* d, const FenerfLocalMapDesc* mp, FenerfLocalModel** out) {
-  if (!out) return local_fail(FENERF_E_INVALID, "out is NULL");
+  if (!out) return fail(FENERF_E_INVALID, "out is NULL");
   *out = nullptr;
   std::vector<float> blob, consts;
   std::string err;
   int rc = pack_local_weights(d, mp, blob, consts, err);
-  if (rc) return local_fail(rc, err);
+  if (rc) return fail(rc, err);
   if ((rc = check_trig_domain())) return rc;
   FenerfLocalModel* m = new (std::nothrow) FenerfLocalModel();
-  if (!m) return local_fail(FENERF_E_NOMEM, "out of host memory");
+  if (!m) return fail(FENERF_E_NOMEM, "out of host memory");
   m->H = d->hidden_dim; m->n_geo = d->n_geo; m->n_color = d->n_color; m->L = d->n_geo + d->n_color;
   m->box_scale = d->box_scale; m->d_stream = nullptr; m->d_consts = nullptr;
   int dev = 0;
@@ -315,7 +309,7 @@ extern "C" int fenerf_local_model_create(const FenerfModelDesc* d, const FenerfL
   if (e == hipSuccess) e = hipMemcpy(m->d_consts, consts.data(), consts.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     fenerf_local_model_destroy(m);
-    return local_fail(FENERF_E_HIP, std::string("fenerf_local_model_create: ") + hipGetErrorString(e));
+    return hip_fail(e, "fenerf_local_model_create");
   }
   *out = m;
   return FENERF_OK;
@@ -330,22 +324,14 @@ extern "C" void fenerf_local_model_destroy(FenerfLocalModel* m) {
 
 extern "C" int fenerf_siren_forward_local(const FenerfLocalModel* m, int64_t total_points, const float* points, const float* ray_dirs,
                                           const float* latents, float* out, void* stream) {
-  if (!m) return local_fail(FENERF_E_INVALID, "model is NULL");
-  if (total_points < 0) return local_fail(FENERF_E_INVALID, "total_points < 0");
+  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
+  if (total_points < 0) return fail(FENERF_E_INVALID, "total_points < 0");
   if (total_points == 0) return FENERF_OK;
-  if (!points || !latents || !out) return local_fail(FENERF_E_INVALID, "points / latents / out is NULL");
+  if (!points || !latents || !out) return fail(FENERF_E_INVALID, "points / latents / out is NULL");
   LocalParams p;
   p.stream = m->d_stream; p.consts = m->d_consts;
   p.points = points; p.dirs = ray_dirs; p.latents = latents; p.out = out;
   p.P = total_points; p.box_scale = m->box_scale; p.n_geo = m->n_geo; p.n_color = m->n_color;
   PhaseScope ph(PH_SIREN, stream);
-  switch (m->H) {
-    case 32: return launch_local_t<32>(m, p, stream);
-    case 64: return launch_local_t<64>(m, p, stream);
-    case 96: return launch_local_t<96>(m, p, stream);
-    case 128: return launch_local_t<128>(m, p, stream);
-    case 192: return launch_local_t<192>(m, p, stream);
-    case 256: return launch_local_t<256>(m, p, stream);
-  }
-  return local_fail(FENERF_E_UNSUPPORTED, "unsupported hidden_dim");
+  return dispatch_width(m->H, [&](auto h) { return launch_local_t<decltype(h)::value>(m, p, stream); });
 }

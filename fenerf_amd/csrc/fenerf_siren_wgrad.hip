@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "fenerf_internal.h"
+#include "fenerf_launch.h"
 #include "fenerf_layout.h"
 #include "fenerf_nt.h"
 #include "fenerf_mfma32.h"
@@ -473,13 +474,10 @@ __device__ __forceinline__ void stage_split4(unsigned short* row0_m, const float
 // costs (address + data transfer, 64 B/clk at best), and with 512 of them per tile and workgroup the LDS -- 1,536 cycles of fragment
 // reads + 2,048 of staging writes per tile against 3,072 cycles of MFMA work per SIMD -- was what bounded this kernel
 // (SQ_WAIT_INST_LDS 21 %, matrix pipe 59 % busy, profiles/r06_pmc_gstep_waits.txt).  Same bits in the same places as stage_split4.
-__device__ __forceinline__ float wg_lane_xor1(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true));   // quad_perm:[1,0,3,2]
-}
 __device__ __forceinline__ void stage_split4_pair(unsigned* row0 /* dword 0 of row `row` of the image */, int m, const float (&v)[4]) {
   const bool odd = (m & 1) != 0;
   const float s0 = odd ? v[0] : v[2], s1 = odd ? v[1] : v[3];        // what the partner lane's rows need from this point
-  const float r0 = wg_lane_xor1(s0), r1 = wg_lane_xor1(s1);           // the partner point's values of THIS lane's rows
+  const float r0 = lane_xor1(s0), r1 = lane_xor1(s1);                 // the partner point's values of THIS lane's rows
   const float o0 = odd ? v[2] : v[0], o1 = odd ? v[3] : v[1];        // this point's values of this lane's rows
   const float ev[2] = {odd ? r0 : o0, odd ? r1 : o1};                // even point (low half of the dword)
   const float od[2] = {odd ? o0 : r0, odd ? o1 : r1};                // odd point (high half)
@@ -1103,10 +1101,6 @@ __global__ __launch_bounds__(256) void pointwise_bias_reduce_kernel(FenerfSirenG
 }
 
 namespace {
-int hipfail(hipError_t e, const char* what) {
-  set_error(std::string(what) + ": " + hipGetErrorString(e));
-  return FENERF_E_HIP;
-}
 
 template <int H, int JOB>
 size_t wg_lds_bytes() {
@@ -1120,8 +1114,7 @@ int launch_job(const WgradParams& p, int nz, hipStream_t st) {
   const size_t lds = wg_lds_bytes<H, JOB>();
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
   hipLaunchKernelGGL(kfn, dim3(p.nchunk, p.B, nz), dim3(256), lds, st, p);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hipfail(e, "wgrad launch");
+  return check_launch("wgrad launch");
 }
 
 template <int H, bool T16>
@@ -1131,8 +1124,7 @@ int launch_sq_bf16(const WgradParams& p, int nz, hipStream_t st) {
   const size_t lds = (size_t)(4 * H * WG_LD + 2 * H) * sizeof(float);     // two [A | B] images + FiLM rows
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
   hipLaunchKernelGGL(kfn, dim3(p.nchunk, p.B, nz), dim3(NW * 64), lds, st, p);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hipfail(e, "wgrad bf16 launch");
+  return check_launch("wgrad bf16 launch");
 }
 
 template <int H>
@@ -1141,8 +1133,7 @@ int launch_sq_b16d(const WgradParams& p, int nz, hipStream_t st) {
   const size_t lds = (size_t)4 * H * WD_LD * sizeof(unsigned short);     // two [A | B] images
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
   hipLaunchKernelGGL(kfn, dim3(p.nchunk, p.B, nz), dim3(256), lds, st, p);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hipfail(e, "wgrad bf16-dump launch");
+  return check_launch("wgrad bf16-dump launch");
 }
 
 }  // namespace
@@ -1218,8 +1209,7 @@ static int param_grads_t(const FenerfModel* m, WgradParams p, const FenerfSirenG
     PhaseScope ph(PH_WGRAD_FILM, st);
     hipLaunchKernelGGL(pointwise_film_grads_kernel, dim3((unsigned)((long long)B * p.tiles_per_image), L), dim3(256), 0, st, p, g.d_freq_geo, g.d_phase_geo,
                        g.d_freq_app, g.d_phase_app);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hipfail(e, "per-point film gradients launch");
+    if ((rc = check_launch("per-point film gradients launch"))) return rc;
   } else
   {  // FiLM frequency / phase gradients and the FiLM-layer biases: gather the chain kernel's per-tile sums, reduce
     PhaseScope ph(PH_WGRAD_FILM, st);
@@ -1228,8 +1218,7 @@ static int param_grads_t(const FenerfModel* m, WgradParams p, const FenerfSirenG
     hipLaunchKernelGGL(film_gather_kernel, dim3(nf, B, L), dim3(256), 0, st, pf);
     hipLaunchKernelGGL(film_reduce_kernel, dim3((L * H + 255) / 256), dim3(256), 0, st, film, B, L, H, ng, nf, nf, nf, p.fp, p.inv, g.d_freq_geo,
                        g.d_phase_geo, g.d_freq_app, g.d_phase_app, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hipfail(e, "film sums launch");
+    if ((rc = check_launch("film sums launch"))) return rc;
   }
   if (film_only) return FENERF_OK;
   // ---- square products dtheta_l x_{l-1}^T, l = 1..L-1, one launch
@@ -1266,8 +1255,7 @@ static int param_grads_t(const FenerfModel* m, WgradParams p, const FenerfSirenG
     if (wg_lds_bytes<H, WG_L0>() > lds) lds = wg_lds_bytes<H, WG_L0>();
     if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds))) return rc;
     hipLaunchKernelGGL(kfn, dim3(nt, B, 4), dim3(256), lds, st, T);
-    hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) return hipfail(e2, "thin wgrad launch");
+    if ((rc = check_launch("thin wgrad launch"))) return rc;
   }
   ReduceSet J;
   memset(&J, 0, sizeof(J));
@@ -1290,8 +1278,7 @@ static int param_grads_t(const FenerfModel* m, WgradParams p, const FenerfSirenG
     hipLaunchKernelGGL(film_freq_thin_kernel, dim3(H, B), dim3(64), 0, st, g, *weights, p_l0, p_c0, nt, p.bias, H, ng, L - ng, G);
   if (p.film_per_point)
     hipLaunchKernelGGL(pointwise_bias_reduce_kernel, dim3((L * H + 255) / 256), dim3(256), 0, st, g, p.bias_partial, B, L, H, ng, nt, nc, p.bias_stride);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? FENERF_OK : hipfail(e, "wgrad reduce launch");
+  return check_launch("wgrad reduce launch");
 }
 
 int launch_param_grads(const FenerfModel* m, int B, long long P, const float* points, const float* dirs, const float* fp, const float* pp,
@@ -1321,16 +1308,7 @@ int launch_param_grads(const FenerfModel* m, int B, long long P, const float* po
   }
   p.nchunk = wgrad_nchunk(m, B, p.tiles_per_image);
   float* ws = (float*)workspace;
-  switch (m->H) {
-    case 32: return param_grads_t<32>(m, p, g, ws, film_only, (hipStream_t)stream, weights);
-    case 64: return param_grads_t<64>(m, p, g, ws, film_only, (hipStream_t)stream, weights);
-    case 96: return param_grads_t<96>(m, p, g, ws, film_only, (hipStream_t)stream, weights);
-    case 128: return param_grads_t<128>(m, p, g, ws, film_only, (hipStream_t)stream, weights);
-    case 192: return param_grads_t<192>(m, p, g, ws, film_only, (hipStream_t)stream, weights);
-    case 256: return param_grads_t<256>(m, p, g, ws, film_only, (hipStream_t)stream, weights);
-  }
-  set_error("unsupported hidden_dim");
-  return FENERF_E_UNSUPPORTED;
+  return dispatch_width(m->H, [&](auto h) { return param_grads_t<decltype(h)::value>(m, p, g, ws, film_only, (hipStream_t)stream, weights); });
 }
 
 }  // namespace fenerf

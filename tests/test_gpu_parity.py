@@ -84,7 +84,11 @@ def test_native_library_is_loaded():
 @pytest.mark.parametrize("precision", FORWARD_PRECISIONS)
 @pytest.mark.parametrize("name", ["tiny_texture_fwd", "tiny_baseline_fwd", "h256_texture_16x16_n12",
                                   "h256_texture_16x16_n24_trained", "h256_baseline_8x8_n12", "tiny_texture_fwd_trained",
-                                  "h96_texture_8x8_n12", "h192_baseline_8x8_n12"])       # H = 96 / 192 (round 5): widths that are not powers of two
+                                  "h96_texture_8x8_n12", "h192_baseline_8x8_n12",        # H = 96 / 192 (round 5): widths that are not powers of two
+                                  # the remaining (width, grid / no grid) cells of the launchers' width dispatch and a padded width (48 runs
+                                  # at 64), at 100 points of one image: the last tile is partial
+                                  "h64_texture_5x5_n4", "h64_baseline_5x5_n4", "h128_texture_5x5_n4", "h128_baseline_5x5_n4",
+                                  "h96_baseline_5x5_n4", "h192_texture_5x5_n4", "h48_texture_5x5_n4"])
 def test_siren_forward_vs_reference(name, precision):
     g = load_golden(name)
     nat, spec, sd = _native_for(name, precision)
@@ -891,7 +895,13 @@ def test_one_model_handle_from_two_threads_and_streams():
             assert all(torch.equal(r, ref) for r in results[tid]), (precision, tid)
 
 
-@pytest.mark.parametrize("case", ["tiny_texture_fill_noise", "baseline_lock_view", "h256_bench_shape", "h256_48p48", "cannot_fuse"])
+# the (width, grid / no grid) cells of the one-launch render's width dispatch that the cases above it do not reach, and 48 padded to 64
+WIDTH_CASES = [("texture", 64), ("texture", 96), ("texture", 128), ("texture", 192), ("texture", 48),
+               ("baseline", 32), ("baseline", 96), ("baseline", 128), ("baseline", 192), ("baseline", 256)]
+
+
+@pytest.mark.parametrize("case", ["tiny_texture_fill_noise", "baseline_lock_view", "h256_bench_shape", "h256_48p48", "cannot_fuse"] +
+                         [f"width_{H}_{kind}" for kind, H in WIDTH_CASES])
 def test_one_launch_render_equals_the_four_launch_render(case):
     """fenerf_render_forward on an f16x3 model runs generators.py:479-519 as ONE launch when the shape allows it (ray groups of whole
     128-point tile groups: coarse tiles -> weights + resampling -> fine tiles -> merge + composite inside the workgroup;
@@ -905,6 +915,7 @@ def test_one_launch_render_equals_the_four_launch_render(case):
         "h256_48p48": ("texture", 256, 96, 1, 64, 48, dict(last_back=True), False, False),
         "cannot_fuse": ("texture", 32, 8, 1, 10, 6, {}, False, False),          # 100 rays: not a multiple of the 64-ray group of N = 6
     }
+    cases.update({f"width_{H}_{kind}": (kind, H, 8 if kind == "texture" else 0, 1, 8, 6, {}, False, False) for kind, H in WIDTH_CASES})   # one 64-ray group
     kind, H, grid, B, S_, N, okw, with_noise, lock = cases[case]
     spec = proc.model_spec(kind, hidden_dim=H, grid_size=grid, z_dim=8) if grid else proc.model_spec(kind, hidden_dim=H, z_dim=8)
     sd = proc.make_state_dict(spec, seed=6, sigma_gain=60.0, with_mapping=False)
@@ -1529,7 +1540,10 @@ def _rel_err(got, ref):
                                              ("texture", 128, 4, 3, 130), ("texture", 256, 6, 2, 200),
                                              ("texture", 96, 5, 2, 75), ("baseline", 192, 0, 1, 64), ("spatial", 96, 0, 2, 33),      # round 5: H = 96 / 192
                                              # round 6: widths BETWEEN the instantiated ones run zero-padded at the next one (native.padded_hidden_dim)
-                                             ("texture", 100, 5, 2, 75), ("baseline", 40, 0, 1, 64), ("spatial", 72, 0, 2, 33), ("texture", 250, 4, 1, 96)])
+                                             ("texture", 100, 5, 2, 75), ("baseline", 40, 0, 1, 64), ("spatial", 72, 0, 2, 33), ("texture", 250, 4, 1, 96),
+                                             # the remaining (width, grid / no grid) cells of the launchers' width dispatch, and 48 padded to 64 with a grid
+                                             ("texture", 64, 5, 1, 100), ("texture", 192, 5, 1, 100), ("baseline", 128, 0, 1, 100), ("baseline", 256, 0, 1, 100),
+                                             ("texture", 48, 5, 1, 100)])
 def test_siren_backward_vs_autograd(kind, H, grid, B, P, precision):
     from oracle import fenerf_oracle_grad as OG
     mod, spec, sd = _siren_module(kind, H, grid, precision=precision)
@@ -2793,7 +2807,8 @@ def test_forward_save_and_chain_kernels_are_run_to_run_deterministic():
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-1000:]
 
 
-@pytest.mark.parametrize("H,B,P", [(256, 1, 4224), (256, 2, 2080), (64, 3, 1024)])
+@pytest.mark.parametrize("H,B,P", [(256, 1, 4224), (256, 2, 2080), (64, 3, 1024),
+                                   (32, 1, 96), (96, 1, 96), (128, 1, 96), (192, 1, 96)])      # the other widths of the fp32-tape chain, three 32-point tiles
 def test_inversion_chain_without_the_dump_equals_the_full_backward(H, B, P):
     """fenerf_siren_backward_film + fenerf_siren_film_grads (inversion: no d(theta) dump, no d(grid features)) against
     fenerf_siren_backward + fenerf_siren_param_grads with NULL weight pointers: the FiLM sums are produced by the same instructions and

@@ -1115,6 +1115,18 @@ def run_nonfinite(refs):
         print(f"nonfinite_siren_{kind}: {len(injections)} injections -> {os.path.getsize(path) / 1024:.0f} KiB")
 
 
+# One small forward fixture per (hidden width, with / without a feature grid) that no other fixture has -- and one width between the
+# instantiated ones (48 runs zero-padded at 64): 25 rays x 4 samples = 100 points of one image, so that the last tile is partial.
+WIDTH_CASES = [("texture", 64), ("baseline", 64), ("texture", 128), ("baseline", 128), ("baseline", 96), ("texture", 192), ("texture", 48)]
+
+
+def run_width_cases(refs):
+    for i, (kind, H) in enumerate(WIDTH_CASES):
+        spec = proc.model_spec(kind, hidden_dim=H, grid_size=8, z_dim=16) if kind == "texture" else proc.model_spec(kind, hidden_dim=H, z_dim=16)
+        run_film_case(refs, f"h{H}_{kind}_5x5_n4", spec, seed=30 + i, sigma_gain=300.0, B=1, S=5, N=4, hier=True,
+                      kwargs=dict(clamp_mode="relu", nerf_noise=0.0))
+
+
 def main(out_dir=None, only=None):
     """Regenerates every fixture into `out_dir` (default tests/golden).  Run into a scratch directory and compared with the committed
     files, it checks the recipe against the reference."""
@@ -1126,6 +1138,8 @@ def main(out_dir=None, only=None):
     refs = ref_import.import_reference()
     if only == "nonfinite":
         return run_nonfinite(refs)
+    if only == "widths":
+        return run_width_cases(refs)
     run_nonfinite(refs)
     run_curriculums(refs)
     relu = dict(clamp_mode="relu", nerf_noise=0.0)
@@ -1209,6 +1223,7 @@ def main(out_dir=None, only=None):
                   hier=True, kwargs=relu)
     run_inversion_case(refs, "tiny_texture_inversion", tiny8, "tiny_texture_trained_state", seed=1, n_iterations=30, n_mean_latents=500,
                        S=8, N=12)
+    run_width_cases(refs)
 
 
 if __name__ == "__main__":
