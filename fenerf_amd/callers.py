@@ -281,31 +281,46 @@ def inversion_trajectory(name, num_frames, fov):
     raise ValueError(f"unknown trajectory {name!r} (front | orbit | non_rotation | sphere | inverse_sphere | rotation_horizontal | zoom | rotation_linear)")
 
 
-def render_inversion_views(generator, meta, render_options, angles=(0.0,), max_batch_size=2400000, lock_view_dependence=False):
-    """staged_forward_with_frequencies of an inversion state at yaws pi/2 + angle (:419-431, :441-446) -> [(angle, frame [1,22,S,S])]"""
+def _inversion_pose(pose):
+    """(yaw, pitch) as floats, or None: the reference's frontal pi / 2"""
+    return None if pose is None else (float(pose[0]), float(pose[1]))
+
+
+def render_inversion_views(generator, meta, render_options, angles=(0.0,), max_batch_size=2400000, lock_view_dependence=False, pose=None):
+    """staged_forward_with_frequencies of an inversion state at yaws pi/2 + angle (:419-431, :441-446) -> [(angle, frame [1,22,S,S])].
+    pose: (yaw, pitch) to centre the angles on instead -- what inverse_render(optimize_pose=True) recovered."""
     import math
     film = film_from_inversion(meta)
+    pose = _inversion_pose(pose)
+    if pose is not None:
+        render_options = dict(render_options, v_mean=pose[1])
+    centre = math.pi / 2 if pose is None else pose[0]
     out = []
     with torch.no_grad():
         for angle in angles:
-            img, _, _ = generator.staged_forward_with_frequencies(*film, h_mean=math.pi / 2 + angle, max_batch_size=max_batch_size,
+            img, _, _ = generator.staged_forward_with_frequencies(*film, h_mean=centre + angle, max_batch_size=max_batch_size,
                                                                   lock_view_dependence=lock_view_dependence, **render_options)
             out.append((angle, img))
     return out
 
 
-def render_inversion_recon(generator, meta, render_options, trajectory, max_batch_size=2400000, lock_view_dependence=False):
+def render_inversion_recon(generator, meta, render_options, trajectory, max_batch_size=2400000, lock_view_dependence=False, pose=None):
     """The frames of run_render_recon_video (:462-501): per trajectory entry one staged render of the inverted identity at (pitch, yaw) --
     the trajectory's fov is NOT applied (the reference sets only h_mean / v_mean) -- as uint8 [S, 3 S, 3] RGB panels
-    [image | label colours | 0.5 / 0.5 blend] (the reference hands them to cv2 as BGR)."""
+    [image | label colours | 0.5 / 0.5 blend] (the reference hands them to cv2 as BGR).
+    pose: (yaw, pitch) the trajectory -- written around the frontal (pi / 2, pi / 2) -- is moved to: what inverse_render(optimize_pose=True)
+    recovered."""
+    import math
     from . import imageio_lite
     film = film_from_inversion(meta)
+    pose = _inversion_pose(pose)
+    d_yaw, d_pitch = (0.0, 0.0) if pose is None else (pose[0] - math.pi / 2, pose[1] - math.pi / 2)
     kw = dict(render_options)
     frames = []
     to_u8 = lambda t: imageio_lite.to_uint8_hwc(imageio_lite.make_grid(t, normalize=True))     # tensor_to_PIL (:114-119)
     with torch.no_grad():
         for _, pitch, yaw, _ in trajectory:
-            kw.update(h_mean=float(yaw), v_mean=float(pitch))
+            kw.update(h_mean=float(yaw) + d_yaw, v_mean=float(pitch) + d_pitch)
             frame, _, _ = generator.staged_forward_with_frequencies(*film, max_batch_size=max_batch_size, lock_view_dependence=lock_view_dependence, **kw)
             image, sem = to_u8(frame[:, -3:].cpu()), to_u8(mask2color(frame[:, :-3], generator.device))
             blend = image * 0.5 + sem * 0.5
@@ -315,7 +330,7 @@ def render_inversion_recon(generator, meta, render_options, trajectory, max_batc
 
 def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_psi=0.0, lambda_seg=1.0, lambda_img=1.0,
                    lambda_percept=0.0, lambda_norm=0.0, percept=None, z_dim=256, lr=1e-2, on_step=None, latent_noise=0.03,
-                   n_mean_latents=10000, record_offsets=False):
+                   n_mean_latents=10000, record_offsets=False, optimize_pose=False, lr_pose=None, init_pose=None):
     """GAN inversion in FiLM space (inverse_render_double_semantic.py:306-410): optimise additive offsets on the geometry /
     appearance frequencies and phase shifts with Adam (lr 1e-2, weight_decay 1e-4, StepLR(100, 0.75)) under annealed
     latent noise so that generator.forward_with_frequencies reproduces gt_image [1,3,S,S] and gt_seg [1,18,S,S] (both in
@@ -325,7 +340,11 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
     iteration) goes through generator.draws in the script's order: with the default source that is torch.randn / randn_like on the
     device, value for value the script's generator consumption; a test replays the draws the reference recorded.
     Returns a dict with the reference's checkpoint keys (w_*_frequencies, w_*_phase_shifts, w_*_offsets) + `losses`
-    (+ `offset_history`: the four offset tensors after every iteration, on the host, if record_offsets)."""
+    (+ `offset_history`: the four offset tensors after every iteration, on the host, if record_offsets) + `yaw` / `pitch`.
+    optimize_pose: the camera's yaw / pitch (options['h_mean'] / ['v_mean'], or init_pose = (yaw, pitch)) are optimised with the offsets --
+    what the reference leaves to an external pose estimate (its hand-over is commented out, :422-423, :440, :490-491): leaf parameters in
+    an Adam group of their own (lr_pose, default lr; no weight decay -- an angle has no reason to shrink towards 0), through the rays'
+    gradient of the differentiable render.  Off: every value and draw is what it was; `yaw` / `pitch` report the options' pose."""
     device = generator.device
     siren = generator.siren
     draws = generator.draws
@@ -349,6 +368,13 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
         opt_params = [o_af, o_ap]
     else:
         opt_params = [o_gf, o_gp, o_af, o_ap]
+    yaw, pitch = options.get("h_mean"), options.get("v_mean")
+    if optimize_pose:
+        leaf = lambda v: torch.as_tensor(v, dtype=torch.float32).detach().to(device).reshape(()).clone().requires_grad_()
+        yaw, pitch = leaf(yaw if init_pose is None else init_pose[0]), leaf(pitch if init_pose is None else init_pose[1])
+        options = dict(options, h_mean=yaw, v_mean=pitch)
+        opt_params = [dict(params=opt_params), dict(params=[yaw, pitch], lr=lr if lr_pose is None else lr_pose, weight_decay=0.0)]
+    pose_now = lambda: dict(yaw=yaw.detach().clone() if optimize_pose else yaw, pitch=pitch.detach().clone() if optimize_pose else pitch)
     optimizer = torch.optim.Adam(opt_params, lr=lr, weight_decay=1e-4)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, 100, gamma=0.75)
     mse = torch.nn.MSELoss(reduction="mean")
@@ -377,13 +403,14 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
         if on_step is not None:      # (i, loss, the reference's checkpoint dict at this iteration: what its in-loop preview renders use, :419-452)
             on_step(i, losses[-1], dict(w_geo_frequencies=w_gf, w_geo_phase_shifts=w_gp, w_app_frequencies=w_af, w_app_phase_shifts=w_ap,
                                         w_geo_frequency_offsets=o_gf.detach(), w_geo_phase_shift_offsets=o_gp.detach(),
-                                        w_app_frequency_offsets=o_af.detach(), w_app_phase_shift_offsets=o_ap.detach()))
+                                        w_app_frequency_offsets=o_af.detach(), w_app_phase_shift_offsets=o_ap.detach(), **pose_now()))
     if losses and on_step is None:
         losses = torch.stack(losses).cpu().tolist()
     extra = dict(offset_history=history) if record_offsets else {}
     return dict(**extra, w_geo_frequencies=w_gf, w_geo_phase_shifts=w_gp, w_app_frequencies=w_af, w_app_phase_shifts=w_ap,
                 w_geo_frequency_offsets=o_gf.detach(), w_geo_phase_shift_offsets=o_gp.detach(),
-                w_app_frequency_offsets=o_af.detach(), w_app_phase_shift_offsets=o_ap.detach(), losses=losses)
+                w_app_frequency_offsets=o_af.detach(), w_app_phase_shift_offsets=o_ap.detach(), losses=losses,
+                **{k: (None if v is None else float(v)) for k, v in pose_now().items()})
 
 
 def render_latent_interpolation(generator, z1_geo, z2_geo, z1_app, z2_app, options, n_frames=8, latent_type="both", psi=1.0,

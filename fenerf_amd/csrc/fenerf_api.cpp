@@ -1375,13 +1375,16 @@ long long backward_max_points(const FenerfModel* m, long long Pp, bool film16, l
 
 struct BackwardWs {
   size_t d_out2, d_fc, dump, dump_stride, d_grid_cl, d_e, det, wgrad, film2, scratch, total;      // dump_stride: bytes of one chunk's dump (split backward: several slots)
+  size_t d_pts2, d_rd2;                   // ray gradients (fenerf_render_backward_rays): per-sample d points / d view directions, [2B][Pp][3] each
   long long max_chunk_points, film_row;   // film_row = floats of one image's four FiLM gradient rows
   int max_nb;
 };
-BackwardWs backward_ws(const FenerfModel* m, int B, int R, int N, int film_only, long long chunk_points, long long film_budget, int dump_slots = 1) {
+// rays: 0 = no ray gradients, 1 = with per-sample view-direction gradients, 2 = the view is locked (d points only)
+BackwardWs backward_ws(const FenerfModel* m, int B, int R, int N, int film_only, long long chunk_points, long long film_budget, int dump_slots = 1,
+                       int rays = 0) {
   BackwardWs w;
   const long long P = (long long)R * N, Pp = (P + 31) / 32 * 32;
-  const bool film16 = film_only && m->precision == FENERF_PREC_F16X3;
+  const bool film16 = film_only && m->precision == FENERF_PREC_F16X3 && !rays;      // (the input gradients are read from the dump)
   const std::vector<Chunk> chunks = plan_chunks(2 * B, Pp, backward_max_points(m, Pp, film16, chunk_points, film_budget));
   w.max_chunk_points = 0; w.max_nb = 0;
   size_t wg = 0, sums = 0;
@@ -1413,6 +1416,9 @@ BackwardWs backward_ws(const FenerfModel* m, int B, int R, int N, int film_only,
   w.film2 = take((size_t)2 * B * w.film_row * sizeof(float));
   // a later chunk's gradients before they are added to the first one's: every weight tensor + the FiLM rows of the chunk's images
   w.scratch = take(chunks.size() > 1 ? ((size_t)(film_only ? 0 : grad_sizes(m).total) + (size_t)w.max_nb * w.film_row) * sizeof(float) : 0);
+  // (behind everything else: the layout of a backward without ray gradients is what it was)
+  w.d_pts2 = take(rays ? (size_t)2 * B * Pp * 3 * sizeof(float) : 0);
+  w.d_rd2 = take(rays == 1 ? (size_t)2 * B * Pp * 3 * sizeof(float) : 0);
   w.total = off;
   return w;
 }
@@ -1503,6 +1509,9 @@ extern "C" size_t fenerf_render_backward_workspace_bytes(const FenerfModel* m, i
   return backward_ws(m, B, R, N, film_only, chunk_points, film_sums_budget_bytes).total;
 }
 
+// what fenerf_render_backward_rays asks for beside fenerf_render_backward's gradients (stage 0 only)
+struct RayGrads { const float* w_geo0; const float* w_color0; int w_color0_ld; float* d_origins; float* d_dirs; };
+
 // stage 0: the whole backward in one call (fenerf_render_backward).  stage 1 / 2: the same launches cut in two (fenerf_render_backward_stage):
 // 1 = composite backward, chain AND weight gradients of every chunk but the last `keep_chunks`, the chains of those last chunks -- each
 // into its own dump slot -- and the finished grid gradient; 2 = the weight gradients of the last chunks, the sums, the FiLM fold.  Same
@@ -1511,7 +1520,7 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
                                 int tape_format, const float* z_coarse, const float* noise_final, const FenerfCompositeOpts* opts,
                                 const float* g_rgb, const FenerfSirenGrads* grads, float* d_grid_ncdhw, const FenerfSirenGrads* weights,
                                 int64_t chunk_points, int64_t film_sums_budget_bytes, void* workspace, size_t workspace_bytes,
-                                void* stream, int keep_chunks, int stage) {
+                                void* stream, int keep_chunks, int stage, const RayGrads* rays = nullptr) {
   if (!m) return fail(FENERF_E_INVALID, "model is NULL");
   if (!m->differentiable || !m->d_bwd_stream) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
   int rc = check_opts(opts);
@@ -1532,8 +1541,21 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
   if (!film_only && m->grid_ch && !d_grid_ncdhw && stage != 2) return fail(FENERF_E_INVALID, "d_grid_ncdhw is NULL");
   const RenderSave sv = render_save(m, B, R, N, tape_format, lock_view);
   if (save_bytes < sv.total) return fail(FENERF_E_INVALID, "save buffer too small (see fenerf_render_save_bytes)");
-  const BackwardWs wsz = backward_ws(m, B, R, N, film_only, chunk_points, film_sums_budget_bytes, stage == 0 ? 1 : keep_chunks);
-  if (workspace_bytes < wsz.total) return fail(FENERF_E_INVALID, "workspace too small (see fenerf_render_backward_workspace_bytes / _split_workspace_bytes)");
+  const int ray_mode = rays ? (lock_view ? 2 : 1) : 0;
+  const BackwardWs wsz = backward_ws(m, B, R, N, film_only, chunk_points, film_sums_budget_bytes, stage == 0 ? 1 : keep_chunks, ray_mode);
+  if (workspace_bytes < wsz.total)
+    return fail(FENERF_E_INVALID, rays ? "workspace too small (see fenerf_render_backward_rays_workspace_bytes)"
+                                       : "workspace too small (see fenerf_render_backward_workspace_bytes / _split_workspace_bytes)");
+  if (rays) {       // refusals before the first launch
+    const std::vector<Chunk> chunks = plan_chunks(2 * B, sv.Pp, backward_max_points(m, sv.Pp, false, chunk_points, 0));
+    if (m->grid_ch != 0 && m->grid_ch != 32) return fail(FENERF_E_UNSUPPORTED, "fenerf_render_backward_rays: feature grids of 32 channels only");
+    for (const Chunk& c : chunks) {
+      if (c.nb > 65535) return fail(FENERF_E_UNSUPPORTED, "fenerf_render_backward_rays: at most 65535 images per backward chunk (lower chunk_points)");
+      if (use_bf16_dump(m, (long long)c.nb * c.n))
+        return fail(FENERF_E_UNSUPPORTED, "fenerf_render_backward_rays: the input-gradient pass reads the fp32 d(theta) dump; a backward chunk of this "
+                                          "model writes the bf16 dump (wgrad_bf16_min_points: AMP-class gradients)");
+    }
+  }
   const char* sb = (const char*)save;
   char* wb = (char*)workspace;
   hipStream_t st = (hipStream_t)stream;
@@ -1568,8 +1590,11 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
     }
   }
   // ---- chunks of whole (pass, image) pairs -- or point ranges of one -- : chain, then the weight / FiLM gradients of the chunk
-  const bool film16 = film_only && m->precision == FENERF_PREC_F16X3;
+  // (with ray gradients a FiLM-only step takes the dumping chain too: the no-dump chain leaves nothing for the input-gradient pass to read)
+  const bool film16 = film_only && m->precision == FENERF_PREC_F16X3 && !rays;
   const std::vector<Chunk> chunks = plan_chunks(nB, Pp, backward_max_points(m, Pp, film16, chunk_points, film_sums_budget_bytes));
+  float* const d_pts2 = rays ? (float*)(wb + wsz.d_pts2) : nullptr;
+  float* const d_rd2 = (rays && !lock_view && rays->d_dirs) ? (float*)(wb + wsz.d_rd2) : nullptr;
   float* const dump0 = (float*)(wb + wsz.dump);
   const bool det = grid_det(m) && !film_only;          // d_e of every row (pass-major, [2B][Pp][32]), one order-independent reduction
   float* d_grid_cl = (m->grid_ch && !film_only && !det) ? (float*)(wb + wsz.d_grid_cl) : nullptr;
@@ -1625,6 +1650,12 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
     if (do_chain && m->grid_ch && !film_only && !det && !chain_scatters(m)) {
       PhaseScope ph(PH_GRID, stream);
       if ((rc = launch_grid_backward(m, npts, pts_c, d_e, d_grid_cl, stream))) return rc;
+    }
+    if (rays) {       // this chunk's rows of the per-sample d points / d view directions, from the dump its chain has just left
+      PhaseScope ph(PH_OTHER, stream);
+      if ((rc = launch_siren_input_grads(m, c.nb, c.n, pts_c, fp_c, dump, rays->w_geo0, rays->w_color0, rays->w_color0_ld, d_pts2 + (size_t)g0 * 3,
+                                         d_rd2 ? d_rd2 + (size_t)g0 * 3 : nullptr, stream)))
+        return rc;
     }
     if (!do_wgrad) continue;
     // where this chunk's gradients go: the first chunk writes the outputs, later ones a scratch set that is then added (chunk order:
@@ -1687,7 +1718,49 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
     const long long rows = (long long)nB * Pp;
     if ((rc = launch_grid_backward_det(m, rows, rows, pts2, d_e, d_grid_ncdhw, true, wb + wsz.det, stream))) return rc;
   }
+  if (rays) {       // every chunk has left its rows: one reduction over both passes' samples per ray
+    PhaseScope ph(PH_OTHER, stream);
+    if ((rc = launch_ray_grads(B, R, N, Pp, 2, d_pts2, d_rd2, z_coarse, zf, rays->d_origins, rays->d_dirs, stream))) return rc;
+  }
   return FENERF_OK;
+}
+
+// replaces: the `origins.grad` / `dirs.grad` torch autograd leaves behind transformed_points = origins + dirs * z and the expanded view
+// directions of a render (generators.py:468-476, :504) when the rays carry a graph -- the reference never asks (its rays are built under
+// torch.no_grad(), generators.py:465; the pose hand-over of its inversion is commented out, inverse_render_double_semantic.py:422-423)
+extern "C" int fenerf_ray_grads(int B, int R, int N, int passes, const float* d_points, const float* d_viewdirs, const float* z_coarse,
+                                const float* z_fine, float* d_origins, float* d_dirs, void* stream) {
+  if (B <= 0 || R <= 0 || N < 3 || N > FENERF_MAX_RAY_SAMPLES / 2) return fail(FENERF_E_INVALID, "need B, R > 0 and 3 <= num_steps <= 512 (FENERF_MAX_RAY_SAMPLES / 2)");
+  if (passes != 1 && passes != 2) return fail(FENERF_E_INVALID, "passes must be 1 (single pass) or 2 (coarse | fine)");
+  if (!d_points || !z_coarse) return fail(FENERF_E_INVALID, "d_points / z_coarse is NULL");
+  if ((passes == 2) != (z_fine != nullptr)) return fail(FENERF_E_INVALID, "z_fine is required with passes == 2 and must be NULL with passes == 1");
+  if (!d_origins && !d_dirs) return fail(FENERF_E_INVALID, "d_origins and d_dirs are both NULL");
+  const long long P = (long long)R * N, Pp = (P + 31) / 32 * 32;
+  PhaseScope ph(PH_OTHER, stream);
+  return launch_ray_grads(B, R, N, Pp, passes, d_points, d_viewdirs, z_coarse, z_fine, d_origins, d_dirs, stream);
+}
+
+extern "C" size_t fenerf_render_backward_rays_workspace_bytes(const FenerfModel* m, int B, int R, int N, int film_only, int lock_view,
+                                                              int64_t chunk_points, int64_t film_sums_budget_bytes) {
+  if (!m || B <= 0 || R <= 0 || N <= 0) return 0;
+  return backward_ws(m, B, R, N, film_only, chunk_points, film_sums_budget_bytes, 1, lock_view ? 2 : 1).total;
+}
+
+// replaces: loss.backward() through a render whose rays carry a graph (see fenerf_ray_grads) -- fenerf_render_backward plus, per backward
+// chunk, the input-gradient pass over the chunk's dump and, at the end, one reduction to per-ray gradients
+extern "C" int fenerf_render_backward_rays(const FenerfModel* m, int B, int R, int N, int lock_view, const void* save, size_t save_bytes,
+                                           int tape_format, const float* z_coarse, const float* noise_final, const FenerfCompositeOpts* opts,
+                                           const float* g_rgb, const FenerfSirenGrads* grads, float* d_grid_ncdhw, const FenerfSirenGrads* weights,
+                                           int64_t chunk_points, int64_t film_sums_budget_bytes, void* workspace, size_t workspace_bytes,
+                                           const float* w_geo0, const float* w_color0, int w_color0_ld, float* d_origins, float* d_dirs,
+                                           void* stream) {
+  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
+  if (!d_origins && !d_dirs) return fail(FENERF_E_INVALID, "d_origins and d_dirs are both NULL (fenerf_render_backward is the call without ray gradients)");
+  if (!w_geo0 || !w_color0) return fail(FENERF_E_INVALID, "w_geo0 / w_color0 is NULL");
+  if (w_color0_ld < 3 + m->grid_ch) return fail(FENERF_E_INVALID, "w_color0_ld < 3 + grid channels");
+  const RayGrads rays{w_geo0, w_color0, w_color0_ld, d_origins, d_dirs};
+  return render_backward_impl(m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
+                              chunk_points, film_sums_budget_bytes, workspace, workspace_bytes, stream, 1, 0, &rays);
 }
 
 extern "C" int fenerf_render_backward(const FenerfModel* m, int B, int R, int N, int lock_view, const void* save, size_t save_bytes,

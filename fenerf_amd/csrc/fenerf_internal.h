@@ -191,6 +191,10 @@ int launch_grid_backward_det(const FenerfModel* m, long long rows, long long den
 // fenerf_siren_inputgrad.hip: d points / d dirs from the fp32 d(theta) dump (layer 0 and colour layer 0) + grid_sample's coordinate gradient
 int launch_siren_input_grads(const FenerfModel* m, int B, long long P, const float* points, const float* fp, const float* d_t, const float* w_geo0,
                              const float* w_color0, int w_color0_ld, float* d_points, float* d_dirs, void* stream);
+// fenerf_ray_grad.hip: per-sample d points / d view directions [passes][B][Pp][3] (d_rd2 may be nullptr) -> d origins / d dirs [B][R][3]
+// (either may be nullptr) for constant depths z_coarse / z_fine [B*R][N] (z_fine: passes == 2 only)
+int launch_ray_grads(int B, int R, int N, long long Pp, int passes, const float* d_pts2, const float* d_rd2, const float* z_coarse,
+                     const float* z_fine, float* d_origins, float* d_dirs, void* stream);
 int launch_siren16w(const FenerfModel* m, const SirenParams& p, void* stream);   // f16x3 forward / forward-save, 16-point waves (fenerf_siren_f16w.hip)
 // fenerf_render_forward as ONE launch (fenerf_siren_f16w.hip, FUSED): ray groups of whole octs, see there
 struct FusedRenderPlan { int rays_per_group, octs_per_group, blocks; long long groups; };

@@ -161,6 +161,18 @@ def _python_composite_backward(nat, opts, dims, g_rgb, rd, film, out2, z_f, zc, 
     return d_out2, [torch.cat([t, t]) for t in film], torch.cat([rd, rd]) if rd.numel() else None
 
 
+def check_ray_grads_supported(module):
+    """Rays that require grad: refuse the gradient tiers whose backward chunks write the bf16 d(theta) dump (nothing for the input-gradient
+    pass to read) -- up front, in the forward."""
+    if getattr(module, "grad_precision", "f32") in ("amp", "amp16"):
+        raise NotImplementedError(f"fenerf_amd: gradients wrt the rays (camera pose) are not available with siren.grad_precision = "
+                                  f"{module.grad_precision!r}; use grad_precision 'f32' or 'tape16'")
+
+
+def rays_require_grad(origins, dirs):
+    return torch.is_grad_enabled() and (origins.requires_grad or dirs.requires_grad)
+
+
 class HierarchicalRenderFunction(torch.autograd.Function):
     """The whole differentiable hierarchical render of generators.py:479-519 as ONE autograd node: coarse SIREN pass ->
     (no-grad) coarse weights -> resampled depths -> fine SIREN pass -> merged composite.  Both passes write their tapes into
@@ -174,6 +186,11 @@ class HierarchicalRenderFunction(torch.autograd.Function):
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, module, opts, copts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, *params):
         film_only = not any(ctx.needs_input_grad[14:])
+        if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
+            # Rays that require grad (a camera pose under optimisation).  The backward reads the chunks' fp32 d(theta) dumps once more
+            # (fenerf_siren_input_grads); every tape format tape_format() picks below leaves one -- a FiLM-only step simply takes the
+            # dumping chain -- except the bf16 dumps of the AMP tiers.
+            check_ray_grads_supported(module)
         ctx.abi = USE_RENDER_ABI and not (_siren_autograd.OVERLAP_WGRAD)
         if not ctx.abi:
             return _hierarchical_forward(ctx, module, opts, copts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, params, film_only=film_only)
@@ -190,22 +207,36 @@ class HierarchicalRenderFunction(torch.autograd.Function):
             B, R, N = ctx.dims
             save, z_c, noise_f, *params = ctx.saved_tensors
             nat.set_grid_grad_mode(_siren_autograd.deterministic_grid(module))
+            ray_grads = None
+            if need[4] or need[5]:
+                w_geo, w_col = _siren_autograd.film_layer_weights(module, params)
+                ray_grads = (w_geo[0], w_col[0], need[4], need[5])
             r, g_grid = nat.render_backward(B, R, N, save, z_c, noise_f if noise_f.numel() else None, opts, g_rgb.contiguous().float(), film_only,
                                             lock_view=ctx.lock_view, tape_format=ctx.tape_format,
                                             weights=_siren_autograd.film_layer_weights(module, params) if ctx.tape_format else None,
-                                            chunk_points=_siren_autograd.BACKWARD_CHUNK_POINTS, film_sums_budget_bytes=_siren_autograd.FILM_SUMS_BUDGET_BYTES)
-            return (None,) * 10 + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, d_grid_ncdhw=g_grid)
+                                            chunk_points=_siren_autograd.BACKWARD_CHUNK_POINTS, film_sums_budget_bytes=_siren_autograd.FILM_SUMS_BUDGET_BYTES,
+                                            ray_grads=ray_grads)
+            return (None,) * 4 + (r.get("d_origins"), r.get("d_dirs")) + (None,) * 4 \
+                + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, d_grid_ncdhw=g_grid)
         B, R, N, P, Pp = ctx.dims
         pts2, rd, fg, pg, fa, pa, out2, tape2, tape_e2, z_f, zc, noise_f, *params = ctx.saved_tensors
         d_out2, film2, rd2 = _python_composite_backward(nat, opts, ctx.dims, g_rgb, rd, (fg, pg, fa, pa), out2, z_f, zc, noise_f)
         rows = _siren_autograd.begin_grid_gradient(module, nat, 2 * B * Pp, film_only)
+        input_grads = None
+        if need[4] or need[5]:      # per-sample d points / d view directions of both passes, chunk by chunk, then one reduction per ray
+            w_geo, w_col = _siren_autograd.film_layer_weights(module, params)
+            new = lambda: torch.empty((2 * B, Pp, 3), dtype=torch.float32, device=pts2.device)
+            input_grads = _siren_autograd.InputGrads(w_geo[0], w_col[0], new(), new() if (need[5] and rd2 is not None) else None)
         r, d_grid = _siren_autograd.chunked_backward(nat, 2 * B, Pp, film2, pts2, rd2, out2, d_out2, tape2,
                                                   tape_e2 if tape_e2.numel() else None, film_only, tape_format=ctx.tape_format,
                                                   weights=_siren_autograd.film_layer_weights(module, params) if ctx.tape_format else None,
-                                                  grid_rows=rows)
+                                                  input_grads=input_grads, grid_rows=rows)
         if rows is not None:
             d_grid = rows.reduce(nat)
-        return (None,) * 10 + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, B=B, d_grid_cl=d_grid)
+        d_o = d_d = None
+        if input_grads is not None:
+            d_o, d_d = native.ray_grads(input_grads.d_points, input_grads.d_dirs, zc.reshape(B, R, N), z_f, want_origins=need[4], want_dirs=need[5])
+        return (None,) * 4 + (d_o, d_d) + (None,) * 4 + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, B=B, d_grid_cl=d_grid)
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------

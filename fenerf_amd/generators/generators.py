@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from .. import _lib, native
 from ..siren import autograd as _siren_autograd
-from .autograd import (CompositeFunction, HierarchicalRenderFunction, ImageLayoutFunction, MergeCompositeFunction, SparseHierarchicalRenderFunction,
+from .autograd import (check_ray_grads_supported, rays_require_grad, CompositeFunction, HierarchicalRenderFunction, ImageLayoutFunction, MergeCompositeFunction, SparseHierarchicalRenderFunction,
                        SparseSinglePassRenderFunction, hierarchical_render_split, sparse_auto_choice)
 from . import volumetric_rendering as VR
 from .volumetric_rendering import _DEFAULT_DRAWS, sample_rays
@@ -130,9 +130,12 @@ class _Generator3dBase(nn.Module):
             t = wsum.unsqueeze(-1).expand_as(rgb)
         return rgb, depth, t, pitch, yaw
 
-    def _wants_grad(self, film):
+    def _wants_grad(self, film, *pose):
+        """pose: the call's h_mean / v_mean -- a tensor among them that requires grad (a camera pose under optimisation) makes the render
+        differentiable too"""
         return torch.is_grad_enabled() and (any(t.requires_grad for t in film) or
-                                            any(p.requires_grad for p in self.siren._render_params()))
+                                            any(p.requires_grad for p in self.siren._render_params()) or
+                                            any(isinstance(t, torch.Tensor) and t.requires_grad for t in pose))
 
     def _render_grad(self, film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
                      hierarchical_sample, sample_dist, lock_view_dependence, kwargs):
@@ -151,7 +154,7 @@ class _Generator3dBase(nn.Module):
         grad_points = kwargs.get("grad_points", R)
         if grad_points == R:
             rgb, depth = self._render_rays(film, origins, dirs, z_c, hierarchical_sample, lock_view_dependence, kwargs,
-                                           self._wants_grad(film))
+                                           self._wants_grad(film, origins, dirs))
             return rgb, depth, pitch, yaw
         # part_forward: randperm AFTER the camera draws, then the gradient part's draws, then the rest's (:880-900)
         assert R > grad_points
@@ -159,7 +162,7 @@ class _Generator3dBase(nn.Module):
         idx_g, idx_n = perm[:grad_points], perm[grad_points:]
         take = lambda t, idx: t[:, idx].contiguous()
         rgb_g, _ = self._render_rays(film, take(origins, idx_g), take(dirs, idx_g), take(z_c, idx_g), hierarchical_sample,
-                                     lock_view_dependence, kwargs, self._wants_grad(film))
+                                     lock_view_dependence, kwargs, self._wants_grad(film, origins, dirs))
         with torch.no_grad():
             rgb_n, _ = self._render_rays(film, take(origins, idx_n), take(dirs, idx_n), take(z_c, idx_n), hierarchical_sample,
                                          lock_view_dependence, kwargs, False)
@@ -198,10 +201,16 @@ class _Generator3dBase(nn.Module):
             return _siren_autograd.siren_apply(self.siren, pts.reshape(B, R * N, 3), rd, fg, pg, fa, pa)
 
         sparse = getattr(self.siren, "sparse_backward", False)
+        pose = rays_require_grad(origins, dirs)       # a camera pose under optimisation: only the dense one-node renders deliver d rays
         if sparse == "auto":
-            sparse = sparse_auto_choice(self.siren, B * R * N * (2 if hierarchical_sample else 1))
+            sparse = False if pose else sparse_auto_choice(self.siren, B * R * N * (2 if hierarchical_sample else 1))
         elif sparse not in (True, False):
             raise ValueError(f"siren.sparse_backward must be True, False or 'auto', got {sparse!r}")
+        if pose:
+            check_ray_grads_supported(self.siren)
+            if sparse:
+                raise NotImplementedError("fenerf_amd: the exact-sparsity backward delivers no gradients wrt the rays (camera pose); set "
+                                          "siren.sparse_backward = False or 'auto'")
         if not hierarchical_sample:
             if sparse:      # opt-in exact-sparsity backward (autograd.py), the render without importance resampling: the reference's inversion renders
                 return SparseSinglePassRenderFunction.apply(self.siren, opts, None, bool(lock_view_dependence), origins, dirs, z_c, None, None,
@@ -223,8 +232,12 @@ class _Generator3dBase(nn.Module):
             # what this one removes, and its backward is short
             return SparseHierarchicalRenderFunction.apply(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg,
                                                           fa, pa, *params)
-        if getattr(self.siren, "split_backward", False) and grid is not None and grid.requires_grad and \
-                any(p.requires_grad for p in params if p is not grid):
+        split = getattr(self.siren, "split_backward", False) and grid is not None and grid.requires_grad and \
+            any(p.requires_grad for p in params if p is not grid)
+        if split and pose:
+            raise NotImplementedError("fenerf_amd: the two-node (split_backward) render delivers no gradients wrt the rays (camera pose); set "
+                                      "siren.split_backward = False")
+        if split:
             # two autograd nodes: the grid gradient reaches DistributedDataParallel before the weight-gradient kernels run (autograd.py)
             return hierarchical_render_split(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg, fa, pa)
         return HierarchicalRenderFunction.apply(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg, fa, pa,
@@ -298,7 +311,7 @@ class DoubleImplicitGenerator3d(_Generator3dBase):
             # (camera at the mean pose, view dependence on); kept as is
             return self.part_forward(z_geo, z_app, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
                                      hierarchical_sample, sample_dist=None, lock_view_dependence=False, **kwargs)
-        if self._wants_grad((fg, pg, fa, pa)):
+        if self._wants_grad((fg, pg, fa, pa), h_mean, v_mean):
             pixels, depth, pitch, yaw = self._render_grad((fg, pg, fa, pa), img_size, fov, ray_start, ray_end, num_steps, h_stddev,
                                                           v_stddev, h_mean, v_mean, hierarchical_sample, sample_dist,
                                                           lock_view_dependence, kwargs)
@@ -409,7 +422,7 @@ class DoubleImplicitGenerator3d(_Generator3dBase):
         """-> (pixels [B, output_dim-1, S, S], poses)   (generators.py:735-797)."""
         batch_size = frequencies_app.shape[0]
         film = (frequencies_geo, phase_shifts_geo, frequencies_app, phase_shifts_app)
-        if self._wants_grad(film):
+        if self._wants_grad(film, h_mean, v_mean):
             pixels, depth, pitch, yaw = self._render_grad(film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
                                                           h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence,
                                                           kwargs)
@@ -474,7 +487,7 @@ class ImplicitGenerator3d(_Generator3dBase):
         batch_size = z.shape[0]
         frequencies, phase_shifts = self.siren.mapping_network(z)
         film = self._film(frequencies, phase_shifts)
-        if self._wants_grad(film):
+        if self._wants_grad(film, h_mean, v_mean):
             pixels, depth, pitch, yaw = self._render_grad(film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
                                                           h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence,
                                                           kwargs)
@@ -522,7 +535,7 @@ class ImplicitGenerator3d(_Generator3dBase):
         """(generators.py:353-431)"""
         batch_size = frequencies.shape[0]
         film = self._film(frequencies, phase_shifts)
-        if self._wants_grad(film):
+        if self._wants_grad(film, h_mean, v_mean):
             pixels, depth, pitch, yaw = self._render_grad(film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
                                                           h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence,
                                                           kwargs)

@@ -69,12 +69,12 @@ class RecordedDraws:
 _DEFAULT_DRAWS = TorchDraws()
 
 
-def _camera_ray_dirs(resolution, fov, device):
+def _camera_ray_dirs(resolution, fov, device, dtype=None):
     """Unit camera-space directions [R,3] of the W x H pixel grid: x in [-1,1] left->right, y in [1,-1] top->bottom,
     z = -1/tan(fov/2); ray index = row*W + col (volumetric_rendering.py:113-121)."""
     W, H = resolution
-    xs = torch.linspace(-1, 1, W, device=device)
-    ys = torch.linspace(1, -1, H, device=device)
+    xs = torch.linspace(-1, 1, W, device=device, dtype=dtype)
+    ys = torch.linspace(1, -1, H, device=device, dtype=dtype)
     x = xs.repeat(H)                       # col varies fastest
     y = ys.repeat_interleave(W)
     z = -torch.ones_like(x) / np.tan((2 * math.pi * fov / 360) / 2)
@@ -142,6 +142,12 @@ def sample_camera_positions(device, n=1, r=1, horizontal_stddev=1, vertical_stdd
     """Camera origins on a sphere of radius r; returns (origin [n,3], phi = pitch [n,1], theta = yaw [n,1])  (:179-228).
     phi is clamped to [1e-5, pi - 1e-5]; y is up: origin = r (sin phi cos theta, cos phi, sin phi sin theta)."""
     theta, phi = sample_camera_angles(device, n, horizontal_stddev, vertical_stddev, horizontal_mean, vertical_mean, mode, draws)
+    return camera_position(theta, phi, r)
+
+
+def camera_position(theta, phi, r=1):
+    """(theta, phi) [n,1] as sample_camera_angles returns them -> (origin [n,3], clamped phi = pitch, theta = yaw): the deterministic
+    part of sample_camera_positions (:220-228), differentiable in both angles (the clamp passes no gradient where it binds)."""
     phi = torch.clamp(phi, 1e-5, math.pi - 1e-5)
     origin = torch.cat([r * torch.sin(phi) * torch.cos(theta), r * torch.cos(phi), r * torch.sin(phi) * torch.sin(theta)], -1)
     return origin, phi, theta
@@ -184,6 +190,20 @@ def transform_sampled_points(points, z_vals, ray_directions, device, h_stddev=1,
     return world_points.reshape(n, num_rays, num_steps, 3), z_vals, world_dirs.reshape(n, num_rays, 3), world_origins, pitch, yaw
 
 
+def rays_from_angles(theta, phi, resolution, fov, device):
+    """The PyTorch formulation of the rays of a camera at (theta, phi) [n,1] on the unit sphere looking at the origin:
+    -> (origins [n,R,3], dirs [n,R,3], pitch, yaw).  The host-logic statement of fenerf_ray_setup's camera part, and -- being ordinary
+    torch ops -- the graph through which a pose that requires grad reaches the rays (sample_rays attaches it to the kernel's values)."""
+    W, H = resolution
+    n = theta.shape[0]
+    rays_d_cam = _camera_ray_dirs(resolution, fov, device, dtype=theta.dtype)                # [R,3]
+    camera_origin, pitch, yaw = camera_position(theta, phi)
+    rot = _lookat_rotation(normalize_vecs(-camera_origin))
+    dirs = torch.matmul(rays_d_cam.unsqueeze(0), rot.transpose(1, 2))                        # [n,R,3]
+    origins = camera_origin.unsqueeze(1).expand(n, W * H, 3).contiguous()
+    return origins, dirs.contiguous(), pitch, yaw
+
+
 def sample_rays(n, num_steps, device, fov, resolution, ray_start, ray_end, h_stddev, v_stddev, h_mean, v_mean, mode,
                 draws=_DEFAULT_DRAWS):
     """What the fused renderer needs from get_initial_rays_trig + transform_sampled_points, without materialising
@@ -196,19 +216,21 @@ def sample_rays(n, num_steps, device, fov, resolution, ray_start, ray_end, h_std
         u = draws.rand((n, W * H, num_steps, 1), device)
         theta, phi = sample_camera_angles(device, n, h_stddev, v_stddev, h_mean, v_mean, mode, draws=draws)
         z_cam = (-torch.ones(1) / np.tan((2 * math.pi * fov / 360) / 2)).item()   # as the reference's fp32 tensor op rounds it
-        return native.ray_setup(n, W, num_steps, z_cam, ray_start, ray_end, u, theta, phi)
-    rays_d_cam = _camera_ray_dirs(resolution, fov, device)                                   # [R,3]
+        origins, dirs, z_vals, pitch, yaw = native.ray_setup(n, W, num_steps, z_cam, ray_start, ray_end, u, theta.detach(), phi.detach())
+        if torch.is_grad_enabled() and (theta.requires_grad or phi.requires_grad):
+            # a pose that requires grad (h_mean / v_mean tensors): the values stay the kernel's -- x + (t - t.detach()) adds an exact zero --
+            # and the torch formulation's graph carries the gradient to the angles
+            tied = lambda x, t: x + (t - t.detach())
+            o_t, d_t, pitch_t, yaw_t = rays_from_angles(theta.to(device), phi.to(device), resolution, fov, device)
+            origins, dirs, pitch, yaw = tied(origins, o_t), tied(dirs, d_t), tied(pitch, pitch_t), tied(yaw, yaw_t)
+        return origins, dirs, z_vals, pitch, yaw
     z_lin = torch.linspace(ray_start, ray_end, num_steps, device=device)                      # [N]
     step = (z_lin[1] - z_lin[0]) if num_steps > 1 else torch.zeros((), device=device)
     u = draws.rand((n, W * H, num_steps, 1), device)
     z_vals = z_lin.reshape(1, 1, num_steps) + (u.squeeze(-1) - 0.5) * step                    # perturb_points
-    camera_origin, pitch, yaw = sample_camera_positions(n=n, r=1, horizontal_stddev=h_stddev, vertical_stddev=v_stddev,
-                                                        horizontal_mean=h_mean, vertical_mean=v_mean, device=device,
-                                                        mode=mode, draws=draws)
-    rot = _lookat_rotation(normalize_vecs(-camera_origin))
-    dirs = torch.matmul(rays_d_cam.unsqueeze(0), rot.transpose(1, 2))                        # [n,R,3]
-    origins = camera_origin.unsqueeze(1).expand(n, W * H, 3).contiguous()
-    return origins, dirs.contiguous(), z_vals.contiguous(), pitch, yaw
+    theta, phi = sample_camera_angles(device, n, h_stddev, v_stddev, h_mean, v_mean, mode, draws=draws)
+    origins, dirs, pitch, yaw = rays_from_angles(theta, phi, resolution, fov, device)
+    return origins, dirs, z_vals.contiguous(), pitch, yaw
 
 
 def fancy_integration(rgb_sigma, z_vals, device, noise_std=0.5, last_back=False, white_back=False, black_back=False,

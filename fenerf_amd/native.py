@@ -888,11 +888,26 @@ class NativeModel:
             keep.append(_f32(w.detach(), self.device)); wts.color_w[i] = keep[-1].data_ptr()
         return wts, keep
 
+    def _input_grad_weights(self, w_geo0, w_color0):
+        """layer 0's and colour layer 0's nn.Linear weights as fenerf_siren_input_grads / fenerf_render_backward_rays read them: fp32 on the
+        device, zero rows for the padded features of a padded width (their d theta is zero anyway)"""
+        w0, wc0 = _f32(w_geo0.detach(), self.device), _f32(w_color0.detach(), self.device)
+        if self.padded:
+            d = self.spec["hidden_dim"] - self.logical_H
+            w0, wc0 = torch.nn.functional.pad(w0, (0, 0, 0, d)), torch.nn.functional.pad(wc0, (0, 0, 0, d))
+        return w0, wc0
+
     def render_backward(self, B, R, N, save, z_coarse, noise_final, opts, g_rgb, film_only, lock_view=False, tape_format=0, weights=None,
-                        chunk_points=0, film_sums_budget_bytes=0):
+                        chunk_points=0, film_sums_budget_bytes=0, ray_grads=None):
         """fenerf_render_backward: every gradient of the render in ONE call -> (dict like siren_param_grads -- FiLM gradients [B, n*H], both
-        passes summed; weight / bias gradients unless film_only --, d_grid [1,32,D,H,W] or None)."""
+        passes summed; weight / bias gradients unless film_only --, d_grid [1,32,D,H,W] or None).
+        ray_grads: None, or (w_geo0, w_color0, want_origins, want_dirs) -- layer 0's [H,3] and colour layer 0's [H,3+G+H] nn.Linear weights
+        and which of the two ray gradients to deliver: fenerf_render_backward_rays, and the result dict gains d_origins / d_dirs [B,R,3]
+        (None for the one not asked for)."""
         dev = self.device
+        if ray_grads is not None:
+            return self._render_backward_rays(B, R, N, save, z_coarse, noise_final, opts, g_rgb, film_only, lock_view, tape_format, weights,
+                                              chunk_points, film_sums_budget_bytes, ray_grads)
         if self.spec["grid_ch"] and not film_only and self.grid_grad_mode == _lib.GRID_GRAD_ATOMIC:
             alert_not_deterministic("NativeModel.render_backward (atomic grid-gradient mode)")
         res, g, d_grid = self._render_grad_buffers(B, film_only)
@@ -906,6 +921,33 @@ class NativeModel:
                                                 C.byref(opts), _ptr(_f32(g_rgb, dev)), C.byref(g), _ptr(d_grid), C.byref(wts) if wts is not None else None,
                                                 int(chunk_points), int(film_sums_budget_bytes), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream()))
         return self._unpad_grads(res), d_grid
+
+    def _render_backward_rays(self, B, R, N, save, z_coarse, noise_final, opts, g_rgb, film_only, lock_view, tape_format, weights, chunk_points,
+                              film_sums_budget_bytes, ray_grads):
+        dev = self.device
+        w_geo0, w_color0, want_o, want_d = ray_grads
+        if not (want_o or want_d):
+            raise ValueError("ray_grads: neither d_origins nor d_dirs is asked for (pass ray_grads=None)")
+        if self.spec["grid_ch"] and not film_only and self.grid_grad_mode == _lib.GRID_GRAD_ATOMIC:
+            alert_not_deterministic("NativeModel.render_backward (atomic grid-gradient mode)")
+        res, g, d_grid = self._render_grad_buffers(B, film_only)
+        wts, keep = self._film_weight_struct(weights)
+        w0, wc0 = self._input_grad_weights(w_geo0, w_color0)
+        d_o = torch.empty((B, R, 3), dtype=torch.float32, device=dev) if want_o else None
+        d_d = torch.empty((B, R, 3), dtype=torch.float32, device=dev) if want_d else None
+        l = _lib.lib()
+        with torch.cuda.device(dev):
+            ws = self._workspace("render_bwd", l.fenerf_render_backward_rays_workspace_bytes(self._h, B, R, N, int(film_only), int(lock_view),
+                                                                                             int(chunk_points), int(film_sums_budget_bytes)))
+            _lib.check(l.fenerf_render_backward_rays(self._h, B, R, N, int(lock_view), C.c_void_p(save.data_ptr()), C.c_size_t(save.numel()),
+                                                     int(tape_format), _ptr(_f32(z_coarse, dev)),
+                                                     _ptr(_f32(noise_final, dev)) if noise_final is not None else None, C.byref(opts),
+                                                     _ptr(_f32(g_rgb, dev)), C.byref(g), _ptr(d_grid), C.byref(wts) if wts is not None else None,
+                                                     int(chunk_points), int(film_sums_budget_bytes), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
+                                                     _ptr(w0), _ptr(wc0), int(wc0.shape[1]), _ptr(d_o), _ptr(d_d), _stream()))
+        res = self._unpad_grads(res)
+        res["d_origins"], res["d_dirs"] = d_o, d_d
+        return res, d_grid
 
     def render_backward_stage(self, stage, keep_chunks, B, R, N, save, z_coarse, noise_final, opts, g_rgb, lock_view=False, tape_format=0,
                               weights=None, chunk_points=0, carry=None):
@@ -1266,6 +1308,28 @@ def sparse_select(d_coarse, d_fine, z_coarse, z_fine, origins, dirs, cap, want_d
         _lib.check(_lib.lib().fenerf_sparse_select(B, R, N, Cc, cap, _ptr(dc), _ptr(df), _ptr(zc), _ptr(zf), _ptr(o), _ptr(d),
                                                    C.c_void_p(images.data_ptr()) if images is not None else None, _ptr(pts), _ptr(rd), _ptr(d_sel), C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), nbytes, _stream()))
     return pts, rd, d_sel, counts
+
+
+def ray_grads(d_points, d_viewdirs, z_coarse, z_fine=None, want_origins=True, want_dirs=True):
+    """Per-sample gradients -> per-ray gradients (fenerf_ray_grads, include/fenerf.h): d_points / d_viewdirs [passes * B, Pp, 3] (pass-major;
+    Pp = R * N rounded up to whole 32-point tiles, the pad rows are never read; d_viewdirs None under a locked view) as siren_input_grads
+    leaves them, z_coarse [B, R, N] and, for a hierarchical render, z_fine [B, R, N] (any shape of B * R * N elements), all constants of
+    the graph.  -> (d_origins, d_dirs) [B, R, 3] (None for the one not asked for): sum_n d_points, and sum_n z * d_points + sum_n d_viewdirs,
+    over both passes, in a fixed order."""
+    B, R, N = z_coarse.shape
+    passes = 1 if z_fine is None else 2
+    Pp = (R * N + 31) // 32 * 32
+    dev = d_points.device
+    dp, zc = _f32(d_points, dev), _f32(z_coarse, dev)
+    dv = _f32(d_viewdirs, dev) if d_viewdirs is not None else None
+    zf = _f32(z_fine, dev) if z_fine is not None else None
+    if dp.numel() != passes * B * Pp * 3 or (dv is not None and dv.numel() != dp.numel()) or (zf is not None and zf.numel() != zc.numel()):
+        raise ValueError(f"ray_grads: d_points / d_viewdirs must hold [{passes} * {B}, {Pp}, 3] and z_fine as many depths as z_coarse")
+    d_o = torch.empty((B, R, 3), dtype=torch.float32, device=dev) if want_origins else None
+    d_d = torch.empty((B, R, 3), dtype=torch.float32, device=dev) if want_dirs else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_ray_grads(B, R, N, passes, _ptr(dp), _ptr(dv), _ptr(zc), _ptr(zf), _ptr(d_o), _ptr(d_d), _stream()))
+    return d_o, d_d
 
 
 def composite_backward(g_rgb, rows_a, z_a, opts, rows_b=None, z_b=None, noise=None, out_a=None, out_b=None):

@@ -623,6 +623,36 @@ int fenerf_siren_input_grads(const FenerfModel* m, int B, int64_t P, const float
                              const float* freq_app, const float* phase_app, const float* d_t, const float* w_geo0,
                              const float* w_color0, int w_color0_ld, float* d_points, float* d_dirs, void* film_ws, void* stream);
 
+/* Gradients wrt the RAYS of a render (camera-pose optimisation).  replaces: what torch autograd leaves in origins.grad / dirs.grad behind
+ * transformed_points = origins + dirs * z and the expanded per-sample view directions (generators.py:468-476, :504) when the rays carry a
+ * graph.  The reference never asks: it builds its rays under torch.no_grad() (generators.py:465) and the pose hand-over of its inversion
+ * script is commented out (inverse_render_double_semantic.py:422-423, :440, :490-491).  Sample depths -- the jittered coarse z and the
+ * resampled fine z -- are constants of the graph, as in the reference (generators.py:465, :483-503): this is the exact gradient of the
+ * function the forward computes FOR THE GIVEN DEPTHS; it does not include the resampling's own dependence on the rays.
+ *   fenerf_ray_grads: the reduction alone, for hosts that drive the stage-by-stage API.  d_points / d_viewdirs [passes][B][Pp][3]
+ *     (Pp = R * N rounded up to a multiple of 32; rows R*N .. Pp-1 of an image are never read; d_viewdirs may be NULL: locked view), as
+ *     fenerf_siren_input_grads leaves them; z_coarse [B*R][N]; z_fine [B*R][N] with passes == 2, NULL with passes == 1.
+ *         d_origins[b,r,:] = sum_pass sum_n d_points[pass,b,r*N+n,:]
+ *         d_dirs[b,r,:]    = sum_pass sum_n z[pass,b,r,n] * d_points[pass,b,r*N+n,:]  +  sum_pass sum_n d_viewdirs[pass,b,r*N+n,:]
+ *     [B][R][3] each, either may be NULL.  One ray's additions run coarse n ascending, then fine n ascending, as fp32 adds / FMAs, without
+ *     atomics: the same bits for every launch.  Non-finite per-sample values propagate into their ray's sums.
+ *   fenerf_render_backward_rays: fenerf_render_backward (same arguments, same gradients bit for bit on a weight-gradient step) that also
+ *     runs fenerf_siren_input_grads' pass over every backward chunk's dump and the reduction above: w_geo0 / w_color0 / w_color0_ld as for
+ *     fenerf_siren_input_grads; d_origins / d_dirs [B][R][3], at least one non-NULL (FENERF_E_INVALID otherwise).  With lock_view the
+ *     view-direction term is absent.  A FiLM-only step of a FENERF_PREC_F16X3 model takes the dumping chain here (the no-dump chain leaves
+ *     nothing to read), so its FiLM gradients are those of that chain.  FENERF_E_UNSUPPORTED for models whose backward chunks write the bf16
+ *     dump (wgrad_bf16_min_points: AMP-class gradients).  workspace: fenerf_render_backward_rays_workspace_bytes (two more [2B][Pp][3]
+ *     buffers, one with lock_view).  The two-stage form has no ray variant. */
+int fenerf_ray_grads(int B, int R, int N, int passes, const float* d_points, const float* d_viewdirs, const float* z_coarse,
+                     const float* z_fine, float* d_origins, float* d_dirs, void* stream);
+size_t fenerf_render_backward_rays_workspace_bytes(const FenerfModel* m, int B, int R, int N, int film_only, int lock_view,
+                                                   int64_t chunk_points, int64_t film_sums_budget_bytes);
+int fenerf_render_backward_rays(const FenerfModel* m, int B, int R, int N, int lock_view, const void* save, size_t save_bytes, int tape_format,
+                                const float* z_coarse, const float* noise_final, const FenerfCompositeOpts* opts, const float* g_rgb,
+                                const FenerfSirenGrads* grads, float* d_grid_ncdhw, const FenerfSirenGrads* weights, int64_t chunk_points,
+                                int64_t film_sums_budget_bytes, void* workspace, size_t workspace_bytes, const float* w_geo0,
+                                const float* w_color0, int w_color0_ld, float* d_origins, float* d_dirs, void* stream);
+
 /* replaces: what torch autograd derives for the final fancy_integration of a differentiable render
  * (generators.py:519 / :790; G-step and inversion): gradient wrt rgb_final g_rgb [BR, C-1] -> gradients wrt the SIREN
  * outputs.  merge = 0: rows_a [BR,N,C], z_a [BR,N] -> d_rows_a [BR,N,C].  merge = 1: fine rows_a / coarse rows_b with

@@ -4,7 +4,7 @@ launches per SIREN call recorded and replayed by autograd), in fp32 and under to
 reference's training loop (train_double_latent_semantic.py:279).  Measurement tool only -- imports the test oracle for
 the eager restatement.
 
-    python tools/bench_gstep.py [--B 4] [--size 64] [--steps 24] [--iters 5]
+    python tools/bench_gstep.py [--B 4] [--size 64] [--steps 24] [--iters 5] [--pose] [--single-pass]
 """
 import argparse
 import functools
@@ -47,6 +47,8 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--skip-eager", action="store_true")
     ap.add_argument("--grad-precision", choices=["f32", "tape16", "amp", "amp16"], default="f32", help="weight-gradient operands (siren.grad_precision)")
+    ap.add_argument("--pose", action="store_true", help="h_mean / v_mean as tensors that require grad: the step also delivers the camera-pose gradient")
+    ap.add_argument("--single-pass", action="store_true", help="hierarchical_sample=False (the inversion renders: N samples per ray, no resampling)")
     a = ap.parse_args()
     B, S_, N, H = a.B, a.size, a.steps, a.H
     spec = proc.model_spec("texture", hidden_dim=H, grid_size=a.grid, z_dim=8)
@@ -64,14 +66,21 @@ def main():
     film = proc.film_params(spec, B, seed=4)
     film_t = {k: torch.tensor(v, device=DEV).requires_grad_(True) for k, v in film.items()}
     kw = dict(img_size=S_, fov=12, ray_start=0.88, ray_end=1.12, num_steps=N, h_stddev=0.3, v_stddev=0.155, h_mean=np.pi / 2,
-              v_mean=np.pi / 2, hierarchical_sample=True, sample_dist="gaussian", clamp_mode="relu", nerf_noise=0.2, last_back=False)
+              v_mean=np.pi / 2, hierarchical_sample=not a.single_pass, sample_dist="gaussian", clamp_mode="relu", nerf_noise=0.2, last_back=False)
+    if a.pose:
+        kw.update(h_mean=torch.tensor(np.pi / 2, dtype=torch.float32, device=DEV, requires_grad=True),
+                  v_mean=torch.tensor(np.pi / 2, dtype=torch.float32, device=DEV, requires_grad=True))
     w = torch.randn((B, 21, S_, S_), device=DEV)
     params = [p for n, p in mod.named_parameters() if "mapping_network" not in n]
-    res = {"config": {"B": B, "img_size": S_, "num_steps": f"{N}+{N}", "H": H, "grid": a.grid, "points": B * S_ * S_ * 2 * N}}
+    passes = 1 if a.single_pass else 2
+    res = {"config": {"B": B, "img_size": S_, "num_steps": f"{N}+{N}" if passes == 2 else f"{N}", "H": H, "grid": a.grid, "points": B * S_ * S_ * passes * N,
+                      "pose": bool(a.pose)}}
 
     def native_step(repack):
         for p in params:
             p.grad = None
+        if a.pose:
+            kw["h_mean"].grad = kw["v_mean"].grad = None
         if repack:
             with torch.no_grad():
                 params[0].add_(0)        # bumps the version counter like optimizer.step(): weights are re-packed
@@ -95,6 +104,8 @@ def main():
         p.requires_grad_(True)
 
     if not a.skip_eager:
+        if a.pose or a.single_pass:
+            raise SystemExit("--pose / --single-pass time the native step only: add --skip-eager")
         sdt = {k: torch.tensor(v, device=DEV).requires_grad_(True) for k, v in sd.items()}
         film_e = {k: torch.tensor(v, device=DEV).requires_grad_(True) for k, v in film.items()}
         R = S_ * S_

@@ -77,6 +77,10 @@ def build_parser():
     parser.add_argument('--sparse_backward', choices=['off', 'on', 'auto'], default='off',
                         help="exact-sparsity backward of every iteration's render (DESIGN.md 4.5): same gradients to the order of the sums, "
                              "about half the time per iteration on a mostly empty density field; 'auto' picks per iteration")
+    parser.add_argument('--optimize_pose', action='store_true',
+                        help="optimise the camera's yaw / pitch with the FiLM offsets (the reference assumes a frontal, externally estimated pose); "
+                             "the recovered pose is saved with the checkpoint and centres the preview / recon renders")
+    parser.add_argument('--lr_pose', type=float, default=None, help='learning rate of the yaw / pitch parameter group (default: the offsets\' 1e-2)')
     return parser
 
 
@@ -103,26 +107,31 @@ def run_inverse_render(opt, generator, img_path, seg_path, percept=None):
         gt_seg_19 = torch.nn.functional.interpolate(gt_seg_19, size=(opt.preview_size, opt.preview_size), mode="nearest")
 
     def on_step(i, loss, meta):
+        pose = (meta['yaw'], meta['pitch']) if opt.optimize_pose else None
         if i % 200 == 0:
-            for angle, img in callers.render_inversion_views(generator, meta, render_options, PREVIEW_ANGLES, opt.max_batch_size, opt.lock_view_dependence):
+            for angle, img in callers.render_inversion_views(generator, meta, render_options, PREVIEW_ANGLES, opt.max_batch_size, opt.lock_view_dependence, pose=pose):
                 imageio_lite.save_image(img[:, -3:].cpu(), os.path.join(opt.save_dir, f"{i}_{angle}_img.jpg"), normalize=True)
                 imageio_lite.save_image(callers.mask2color(img[:, :-3]).cpu(), os.path.join(opt.save_dir, f"{i}_{angle}_seg.jpg"), normalize=True)
         if i % 20 == 0:
-            (_, img), = callers.render_inversion_views(generator, meta, render_options, (0,), opt.max_batch_size, opt.lock_view_dependence)
+            (_, img), = callers.render_inversion_views(generator, meta, render_options, (0,), opt.max_batch_size, opt.lock_view_dependence, pose=pose)
             gen_masks = callers.mask2labels(torch.argmax(img[:, :-3], dim=1).float()[0].cpu().numpy(), 19)
             mious.append(callers.mIOU(torch.Tensor(gen_masks[None]), gt_seg_19).item())
 
     z_dim = callers._latent_dims(generator)[0]
     res = callers.inverse_render(generator, gt_image, gt_seg_18, options, n_iterations=opt.iteration, init_psi=opt.init_psi,
                                  lambda_seg=opt.lambda_seg, lambda_img=opt.lambda_img, lambda_percept=opt.lambda_percept,
-                                 lambda_norm=opt.lambda_norm if opt.latent_normalize else 0.0, percept=percept, z_dim=z_dim, on_step=on_step)
+                                 lambda_norm=opt.lambda_norm if opt.latent_normalize else 0.0, percept=percept, z_dim=z_dim, on_step=on_step,
+                                 optimize_pose=opt.optimize_pose, lr_pose=opt.lr_pose)
     meta = {k: res[k] for k in ('w_geo_frequencies', 'w_geo_phase_shifts', 'w_geo_frequency_offsets', 'w_geo_phase_shift_offsets',
                                 'w_app_frequencies', 'w_app_phase_shifts', 'w_app_frequency_offsets', 'w_app_phase_shift_offsets')}
+    if opt.optimize_pose:
+        meta.update(yaw=res['yaw'], pitch=res['pitch'])
     checkpoint_path = os.path.join(opt.save_dir, f'freq_phase_offset_{opt.name}.pth')
     torch.save(meta, checkpoint_path)
     np.save(os.path.join(opt.save_dir, 'mious.npy'), mious)
     print(f"{os.path.basename(img_path)}: loss {res['losses'][0]:.5f} -> {res['losses'][-1]:.5f} in {opt.iteration} iterations"
-          + (f", frontal mIoU {mious[0]:.3f} -> {mious[-1]:.3f}" if mious else "") + f" -> {checkpoint_path}")
+          + (f", frontal mIoU {mious[0]:.3f} -> {mious[-1]:.3f}" if mious else "")
+          + (f", yaw {res['yaw']:.4f} pitch {res['pitch']:.4f}" if opt.optimize_pose else "") + f" -> {checkpoint_path}")
     return checkpoint_path
 
 
@@ -133,7 +142,8 @@ def run_render_recon_video(opt, generator, checkpoint_path):
     meta = torch.load(checkpoint_path, map_location=generator.device, weights_only=False)
     render_options = callers.inversion_render_options(opt.fov, opt.fill_color, opt.preview_size, opt.preview_steps)
     frames = callers.render_inversion_recon(generator, meta, render_options, callers.inversion_trajectory(opt.trajectory, opt.num_frames, opt.fov),
-                                            opt.max_batch_size, opt.lock_view_dependence)
+                                            opt.max_batch_size, opt.lock_view_dependence,
+                                            pose=(meta['yaw'], meta['pitch']) if 'yaw' in meta else None)
     out = os.path.join(opt.save_dir, f'reconstructed_debug_{opt.trajectory}_{opt.fill_color}.avi')
     writer = imageio_lite.AviWriter(out, fps=25)
     for f in frames:
