@@ -164,6 +164,10 @@ _SIGS = {
     "fenerf_render_backward_rays_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i, _i64, _i64]),
     "fenerf_render_backward_rays": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _i, _vp, _vp, C.POINTER(FenerfCompositeOpts), _vp, C.POINTER(FenerfSirenGrads), _vp,
                                          C.POINTER(FenerfSirenGrads), _i64, _i64, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp]),
+    # gradients of depth / weights / wsum beside rgb's: the composite backward's kernel variant, and the one-call render backward with it
+    "fenerf_composite_backward_outputs": (_i, [_i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(FenerfCompositeOpts)] + [_vp] * 7),
+    "fenerf_render_backward_outputs": (_i, [_vp, _i, _i, _i, _i, _vp, _sz, _i, _vp, _vp, C.POINTER(FenerfCompositeOpts), _vp, _vp, C.POINTER(FenerfSirenGrads),
+                                            _vp, C.POINTER(FenerfSirenGrads), _i64, _i64, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp]),
     "fenerf_sparse_select_workspace_bytes": (C.c_size_t, [_i, _i64]),
     "fenerf_sparse_select": (_i, [_i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fenerf_composite_backward": (_i, [_i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(FenerfCompositeOpts), _vp, _vp, _vp, _vp]),

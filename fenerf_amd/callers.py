@@ -330,7 +330,8 @@ def render_inversion_recon(generator, meta, render_options, trajectory, max_batc
 
 def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_psi=0.0, lambda_seg=1.0, lambda_img=1.0,
                    lambda_percept=0.0, lambda_norm=0.0, percept=None, z_dim=256, lr=1e-2, on_step=None, latent_noise=0.03,
-                   n_mean_latents=10000, record_offsets=False, optimize_pose=False, lr_pose=None, init_pose=None):
+                   n_mean_latents=10000, record_offsets=False, optimize_pose=False, lr_pose=None, init_pose=None, gt_depth=None, depth_mask=None,
+                   lambda_depth=0.0):
     """GAN inversion in FiLM space (inverse_render_double_semantic.py:306-410): optimise additive offsets on the geometry /
     appearance frequencies and phase shifts with Adam (lr 1e-2, weight_decay 1e-4, StepLR(100, 0.75)) under annealed
     latent noise so that generator.forward_with_frequencies reproduces gt_image [1,3,S,S] and gt_seg [1,18,S,S] (both in
@@ -344,7 +345,11 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
     optimize_pose: the camera's yaw / pitch (options['h_mean'] / ['v_mean'], or init_pose = (yaw, pitch)) are optimised with the offsets --
     what the reference leaves to an external pose estimate (its hand-over is commented out, :422-423, :440, :490-491): leaf parameters in
     an Adam group of their own (lr_pose, default lr; no weight decay -- an angle has no reason to shrink towards 0), through the rays'
-    gradient of the differentiable render.  Off: every value and draw is what it was; `yaw` / `pitch` report the options' pose."""
+    gradient of the differentiable render.  Off: every value and draw is what it was; `yaw` / `pitch` report the options' pose.
+    gt_depth [1,S,S] (an RGB-D capture, a second view's geometry; depth_mask [1,S,S] or None = every pixel) with lambda_depth > 0 adds
+    lambda_depth * mean(mask * |depth - gt_depth|) on the render's depth map, which then carries the graph
+    (forward_with_frequencies(return_depth=True)); the result gains `depth_losses`, the unweighted term per iteration.  With the defaults
+    the loop is what it was: no return_depth, the same launches."""
     device = generator.device
     siren = generator.siren
     draws = generator.draws
@@ -378,15 +383,28 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
     optimizer = torch.optim.Adam(opt_params, lr=lr, weight_decay=1e-4)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, 100, gamma=0.75)
     mse = torch.nn.MSELoss(reduction="mean")
-    losses, history = [], []
+    losses, history, depth_losses = [], [], []
+    use_depth = gt_depth is not None and lambda_depth != 0
+    if use_depth:
+        gt_depth = torch.as_tensor(gt_depth, dtype=torch.float32).to(device)
+        depth_mask = None if depth_mask is None else torch.as_tensor(depth_mask).to(device=device, dtype=torch.float32)
     for i in range(n_iterations):
         k = (n_iterations - i) / n_iterations                     # annealed noise on the FiLM parameters (:381-384; 0.03 there)
         # draw order and arithmetic of the reference (:381-384): geo freq, geo phase, app freq, app phase; (0.03 * randn) * k
         n_gf, n_gp = latent_noise * draws.randn(tuple(w_gf.shape), device) * k, latent_noise * draws.randn(tuple(w_gp.shape), device) * k
         n_af, n_ap = latent_noise * draws.randn(tuple(w_af.shape), device) * k, latent_noise * draws.randn(tuple(w_ap.shape), device) * k
-        frame, _ = generator.forward_with_frequencies(w_gf + n_gf + o_gf, w_af + n_af + o_af, w_gp + n_gp + o_gp, w_ap + n_ap + o_ap,
-                                                      **options)
+        if use_depth:
+            frame, _, depth = generator.forward_with_frequencies(w_gf + n_gf + o_gf, w_af + n_af + o_af, w_gp + n_gp + o_gp, w_ap + n_ap + o_ap,
+                                                                 return_depth=True, **options)
+        else:
+            frame, _ = generator.forward_with_frequencies(w_gf + n_gf + o_gf, w_af + n_af + o_af, w_gp + n_gp + o_gp, w_ap + n_ap + o_ap,
+                                                          **options)
         loss = lambda_seg * mse(frame[:, :-3], gt_seg) + lambda_img * mse(frame[:, -3:], gt_image)
+        if use_depth:
+            err = (depth - gt_depth.reshape(depth.shape)).abs()
+            depth_term = (err if depth_mask is None else err * depth_mask.reshape(depth.shape)).mean()
+            loss = loss + lambda_depth * depth_term
+            depth_losses.append(depth_term.detach())
         if lambda_percept and percept is not None:
             loss = loss + lambda_percept * percept(frame[:, -3:], gt_image).sum()
         if lambda_norm > 0:
@@ -407,6 +425,8 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
     if losses and on_step is None:
         losses = torch.stack(losses).cpu().tolist()
     extra = dict(offset_history=history) if record_offsets else {}
+    if use_depth:
+        extra["depth_losses"] = torch.stack(depth_losses).cpu().tolist() if depth_losses else []
     return dict(**extra, w_geo_frequencies=w_gf, w_geo_phase_shifts=w_gp, w_app_frequencies=w_af, w_app_phase_shifts=w_ap,
                 w_geo_frequency_offsets=o_gf.detach(), w_geo_phase_shift_offsets=o_gp.detach(),
                 w_app_frequency_offsets=o_af.detach(), w_app_phase_shift_offsets=o_ap.detach(), losses=losses,

@@ -1158,6 +1158,27 @@ extern "C" int fenerf_composite_backward(int64_t BR, int N, int C, int merge, co
   { PhaseScope ph(PH_COMPOSITE_BWD, stream); return launch_composite_backward(p, merge != 0, stream); }
 }
 
+extern "C" int fenerf_composite_backward_outputs(int64_t BR, int N, int C, int merge, const float* rows_a, const float* rows_b,
+                                                 const float* z_a, const float* z_b, const float* noise, const FenerfCompositeOpts* opts,
+                                                 const float* g_rgb, const float* g_depth, const float* g_weights, const float* g_wsum,
+                                                 float* d_rows_a, float* d_rows_b, void* stream) {
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  const int M = merge ? 2 * N : N;
+  if (BR < 0 || N < 1 || M > FENERF_MAX_RAY_SAMPLES || C < 2) return fail(FENERF_E_INVALID, "need BR >= 0, 1 <= samples <= 1024 (FENERF_MAX_RAY_SAMPLES), C >= 2");
+  if (opts->fill_mode != FENERF_FILL_NONE) return fail(FENERF_E_UNSUPPORTED, "fill modes are not differentiated (generator.forward does not use them)");
+  if (!g_rgb && !g_depth && !g_weights && !g_wsum) return fail(FENERF_E_INVALID, "g_rgb, g_depth, g_weights and g_wsum are all NULL: no upstream gradient");
+  if (BR == 0) return FENERF_OK;
+  if (!rows_a || !z_a || !d_rows_a || (merge && (!rows_b || !z_b || !d_rows_b))) return fail(FENERF_E_INVALID, "NULL pointer");
+  CompositeParams p;
+  memset(&p, 0, sizeof(p));
+  p.BR = BR; p.M = M; p.C = C; p.N = N;
+  p.rows_a = rows_a; p.rows_b = rows_b; p.z_a = z_a; p.z_b = z_b; p.noise = noise; p.o = *opts;
+  p.g_rgb = g_rgb; p.d_rows_a = d_rows_a; p.d_rows_b = d_rows_b;
+  const CompositeOutGrads g{g_depth, g_weights, g_wsum};
+  { PhaseScope ph(PH_COMPOSITE_BWD, stream); return launch_composite_backward_outputs(p, g, merge != 0, stream); }
+}
+
 extern "C" size_t fenerf_sparse_select_workspace_bytes(int B, int64_t P) {
   if (B < 1 || P < 1) return 0;
   return sparse_select_workspace_bytes(B, P);
@@ -1520,14 +1541,14 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
                                 int tape_format, const float* z_coarse, const float* noise_final, const FenerfCompositeOpts* opts,
                                 const float* g_rgb, const FenerfSirenGrads* grads, float* d_grid_ncdhw, const FenerfSirenGrads* weights,
                                 int64_t chunk_points, int64_t film_sums_budget_bytes, void* workspace, size_t workspace_bytes,
-                                void* stream, int keep_chunks, int stage, const RayGrads* rays = nullptr) {
+                                void* stream, int keep_chunks, int stage, const RayGrads* rays = nullptr, const float* g_depth = nullptr) {
   if (!m) return fail(FENERF_E_INVALID, "model is NULL");
   if (!m->differentiable || !m->d_bwd_stream) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
   int rc = check_opts(opts);
   if (rc) return rc;
   if ((rc = check_tape_format(m, tape_format))) return rc;
   if (B <= 0 || R <= 0 || N < 3 || 2 * N > FENERF_MAX_RAY_SAMPLES) return fail(FENERF_E_INVALID, "need B, R > 0 and 3 <= num_steps <= 512 (hierarchical render; FENERF_MAX_RAY_SAMPLES / 2)");
-  if (!save || !grads || !workspace || (stage != 2 && (!z_coarse || !g_rgb))) return fail(FENERF_E_INVALID, "NULL pointer");
+  if (!save || !grads || !workspace || (stage != 2 && (!z_coarse || (!g_rgb && !g_depth)))) return fail(FENERF_E_INVALID, "NULL pointer");
   if (!grads->d_freq_geo || !grads->d_phase_geo || !grads->d_freq_app || !grads->d_phase_app) return fail(FENERF_E_INVALID, "grads: film pointer is NULL");
   int have = 0, want = 0;
   for (int i = 0; i < m->n_geo; ++i) { want += 2; have += (grads->geo_w[i] != nullptr) + (grads->geo_b[i] != nullptr); }
@@ -1582,7 +1603,12 @@ static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int l
     float* d_f = Pp == P ? d_out2 + (size_t)B * Pp * C : (float*)(wb + wsz.d_fc);
     float* d_c = Pp == P ? d_out2 : (float*)(wb + wsz.d_fc) + (size_t)B * P * C;
     cp.d_rows_a = d_f; cp.d_rows_b = d_c;
-    { PhaseScope ph(PH_COMPOSITE_BWD, stream); if ((rc = launch_composite_backward(cp, true, stream))) return rc; }
+    {         // a depth gradient (fenerf_render_backward_outputs) takes the kernel variant; without one, the launch this always was
+      PhaseScope ph(PH_COMPOSITE_BWD, stream);
+      if ((rc = g_depth ? launch_composite_backward_outputs(cp, CompositeOutGrads{g_depth, nullptr, nullptr}, true, stream)
+                        : launch_composite_backward(cp, true, stream)))
+        return rc;
+    }
     if (Pp != P) {
       PhaseScope ph(PH_OTHER, stream);
       if ((rc = launch_pad_rows(d_c, d_out2, B, P, Pp, C, true, stream))) return rc;
@@ -1761,6 +1787,24 @@ extern "C" int fenerf_render_backward_rays(const FenerfModel* m, int B, int R, i
   const RayGrads rays{w_geo0, w_color0, w_color0_ld, d_origins, d_dirs};
   return render_backward_impl(m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
                               chunk_points, film_sums_budget_bytes, workspace, workspace_bytes, stream, 1, 0, &rays);
+}
+
+// replaces: loss.backward() through a render whose loss reads the depth map beside (or instead of) the pixels -- one entry for a depth
+// gradient, ray gradients, and both; with neither it is fenerf_render_backward
+extern "C" int fenerf_render_backward_outputs(const FenerfModel* m, int B, int R, int N, int lock_view, const void* save, size_t save_bytes,
+                                              int tape_format, const float* z_coarse, const float* noise_final, const FenerfCompositeOpts* opts,
+                                              const float* g_rgb, const float* g_depth, const FenerfSirenGrads* grads, float* d_grid_ncdhw,
+                                              const FenerfSirenGrads* weights, int64_t chunk_points, int64_t film_sums_budget_bytes, void* workspace,
+                                              size_t workspace_bytes, const float* w_geo0, const float* w_color0, int w_color0_ld, float* d_origins,
+                                              float* d_dirs, void* stream) {
+  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
+  if (!g_rgb && !g_depth) return fail(FENERF_E_INVALID, "g_rgb and g_depth are both NULL: no upstream gradient");
+  const bool want_rays = d_origins || d_dirs;
+  if (want_rays && (!w_geo0 || !w_color0)) return fail(FENERF_E_INVALID, "w_geo0 / w_color0 is NULL");
+  if (want_rays && w_color0_ld < 3 + m->grid_ch) return fail(FENERF_E_INVALID, "w_color0_ld < 3 + grid channels");
+  const RayGrads rays{w_geo0, w_color0, w_color0_ld, d_origins, d_dirs};
+  return render_backward_impl(m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
+                              chunk_points, film_sums_budget_bytes, workspace, workspace_bytes, stream, 1, 0, want_rays ? &rays : nullptr, g_depth);
 }
 
 extern "C" int fenerf_render_backward(const FenerfModel* m, int B, int R, int N, int lock_view, const void* save, size_t save_bytes,

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_kernel(Compo
 // composite backward: d(loss)/d(rgb_final) -> d(loss)/d(rows) for the final fancy_integration of a render
 // (what torch autograd derives for volumetric_rendering.py:23-50).  Same wave-per-ray layout; the suffix sum
 // S_k = sum_{j>k} dw_j w_j is a reverse wavefront scan.  fill modes are not differentiated (generator.forward, the only
-// differentiated caller, does not use them: generators.py:519); depth is not differentiated.
+// differentiated caller, does not use them: generators.py:519); depth / weights / wsum: the OUTS variant below.
 //   w_k = a_k T_k, T_k = prod_{j<k} u_j, u_j = 1 - a_j + 1e-10, a_k = 1 - exp(-delta_k act(sigma_k + noise))
 //   dL/da_k = T_k dL/dw_k - S_k / u_k ;  dL/dsigma_k = dL/da_k * delta_k (1 - a_k) act'(.)
 // ------------------------------------------------------------------------------------------------
@@ -52,8 +52,15 @@ __device__ __forceinline__ float wave_suffix_incl(float v, int lane) {   // incl
   return v;
 }
 
-template <bool MERGE, int MAXM>
-__global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_kernel(CompositeParams P) {
+// OUTS (fenerf_composite_backward_outputs): upstream gradients of depth = sum_k w'_k z_k, of the weights w' (sorted order) and of wsum =
+// sum_k w_k (before the last_back adjustment) join g_rgb's -- three more terms of dL/dw, everything after them is shared:
+//   dL/dw'_k = sum_c g_c row_kc + g_depth z_k + g_weights_k ;  last_back: dL/dw_k = dL/dw'_k - dL/dw'_last ;  then dL/dw_k += g_wsum
+// Each of the four may be nullptr (wave-uniform branches; a missing term is not added, so g_rgb alone gives the bits of OUTS = false).
+// A compile-time variant: with OUTS = false the argument is CompositeParams alone, no line below reads a `G`, and the kernel is the one it was.
+struct CompositeOutParams : CompositeParams { CompositeOutGrads G; };
+
+template <bool MERGE, int MAXM, bool OUTS = false, typename Args = CompositeParams>
+__global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_kernel(Args P) {
   constexpr int SLOTS = MAXM / 64, WPB = RayWaves<MAXM>::n;
   __shared__ float s_z[WPB][MAXM];
   __shared__ float s_zs[WPB][MAXM + 1];
@@ -97,10 +104,20 @@ __global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_ker
     float alpha[SLOTS], tt[SLOTS], dact[SLOTS], delta[SLOTS], gw[SLOTS];
     const float* row[SLOTS];
     float* drow[SLOTS];
+    const bool has_rgb = !OUTS || P.g_rgb != nullptr;
     const float* g = P.g_rgb + ray * (long long)nch;
     float gsum = 0.f;
-    for (int c = lane; c < nch; c += 64) gsum += g[c];
-    gsum = wave_sum(gsum);
+    if (has_rgb) {
+      for (int c = lane; c < nch; c += 64) gsum += g[c];
+      gsum = wave_sum(gsum);
+    }
+    float g_depth = 0.f, g_wsum = 0.f;
+    const float* g_weights = nullptr;
+    if constexpr (OUTS) {
+      if (P.G.g_depth) g_depth = P.G.g_depth[ray];
+      if (P.G.g_wsum) g_wsum = P.G.g_wsum[ray];
+      if (P.G.g_weights) g_weights = P.G.g_weights + ray * (long long)M;
+    }
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
       const int k = lane + 64 * s;
@@ -124,7 +141,12 @@ __global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_ker
         alpha[s] = M > 1 ? 1.f - expf(-delta[s] * act) : 0.f;
         tt[s] = 1.f - alpha[s] + 1e-10f;
         float acc = 0.f;
-        for (int c = 0; c < nch; ++c) acc += g[c] * row[s][c];
+        if (has_rgb)
+          for (int c = 0; c < nch; ++c) acc += g[c] * row[s][c];
+        if constexpr (OUTS) {
+          if (P.G.g_depth) acc += g_depth * s_zs[wv][k];
+          if (g_weights) acc += g_weights[k];
+        }
         gw[s] = acc;
       }
     }
@@ -166,6 +188,9 @@ __global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_ker
     for (int s = 0; s < SLOTS; ++s) {
       if (P.o.white_back) gw[s] -= gsum;
       if (P.o.black_back) gw[s] += gsum;
+      if constexpr (OUTS) {
+        if (P.G.g_wsum) gw[s] += g_wsum;          // the same pre-adjustment sum
+      }
     }
     // S_k = sum_{j>k} gw_j w_j
     float S[SLOTS];
@@ -189,10 +214,10 @@ __global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_ker
         if (P.o.clamp_mode != FENERF_CLAMP_SOFTPLUS && dact[s] == 0.f && dsigma != dsigma) dsigma = 0.f;
         if (staged) {
           float* o = s_out[wv] + s_ord[wv][k] * C;
-          for (int c = 0; c < nch; ++c) o[c] = wp[s] * g[c];
+          for (int c = 0; c < nch; ++c) o[c] = has_rgb ? wp[s] * g[c] : 0.f;
           o[C - 1] = dsigma;
         } else {
-          for (int c = 0; c < nch; ++c) drow[s][c] = wp[s] * g[c];
+          for (int c = 0; c < nch; ++c) drow[s][c] = has_rgb ? wp[s] * g[c] : 0.f;
           drow[s][C - 1] = dsigma;
         }
       }
@@ -211,6 +236,10 @@ __global__ __launch_bounds__(64 * RayWaves<MAXM>::n) void composite_backward_ker
     __builtin_amdgcn_wave_barrier();
   }
 }
+
+// the OUTS instantiations by the two template arguments FENERF_BY_RAY_SAMPLES names
+template <bool MERGE, int MAXM>
+static constexpr auto composite_backward_outputs_kernel = composite_backward_kernel<MERGE, MAXM, true, CompositeOutParams>;
 
 // one launch of a wave-per-ray kernel instantiated for MAXM samples per ray
 template <int MAXM, typename K, typename... A>
@@ -235,6 +264,14 @@ int launch_composite_backward(const CompositeParams& p, bool merge, void* stream
   if (merge) FENERF_BY_RAY_SAMPLES(p.M, composite_backward_kernel, true, p.BR, stream, p);
   else FENERF_BY_RAY_SAMPLES(p.M, composite_backward_kernel, false, p.BR, stream, p);
   return check_launch("composite_backward launch");
+}
+
+int launch_composite_backward_outputs(const CompositeParams& p, const CompositeOutGrads& g, bool merge, void* stream) {
+  if (p.BR <= 0) return FENERF_OK;
+  const CompositeOutParams a{p, g};     // (aggregate with a base: C++17)
+  if (merge) FENERF_BY_RAY_SAMPLES(p.M, composite_backward_outputs_kernel, true, p.BR, stream, a);
+  else FENERF_BY_RAY_SAMPLES(p.M, composite_backward_outputs_kernel, false, p.BR, stream, a);
+  return check_launch("composite_backward_outputs launch");
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -165,6 +165,15 @@ struct CompositeParams {
   float* d_rows_b;         // merge: d coarse [BR][N][C]
 };
 
+// fenerf_composite_backward_outputs: the upstream gradients beside CompositeParams::g_rgb (which may then be nullptr too).  Appended to the
+// kernel argument of that variant only, so CompositeParams -- which the fused forward render keeps in LDS and the rgb-only backward in
+// SGPRs -- stays as it is
+struct CompositeOutGrads {
+  const float* g_depth;    // [BR] or nullptr
+  const float* g_weights;  // [BR][M] by sorted position (like out_weights) or nullptr
+  const float* g_wsum;     // [BR] (sum of the weights BEFORE the last_back adjustment) or nullptr
+};
+
 int launch_film_prep(const FenerfModel* m, long long B, const float* fg, const float* pg, const float* fa, const float* pa,
                      float* fp, float* pp, void* stream, bool for_f32_kernel = false,    // for_f32_kernel: biases of d_consts32, no GEMM result scale
                      bool twice = false);                                                // twice: rows [B, 2B) of fp / pp receive a copy of rows [0, B)
@@ -203,6 +212,7 @@ int launch_render16w_fused(const FenerfModel* m, const SirenParams& p, const Fus
                            const CompositeParams& coarse, const CompositeParams& final_, void* stream);
 int launch_composite(const CompositeParams& p, bool merge, void* stream);
 int launch_composite_backward(const CompositeParams& p, bool merge, void* stream);
+int launch_composite_backward_outputs(const CompositeParams& p, const CompositeOutGrads& g, bool merge, void* stream);   // p.g_rgb may be nullptr
 int launch_resample(long long BR, int N, const float* z, const float* w, const float* u, float* zf, void* stream);
 int launch_sample_pdf(long long BR, int K, int NS, const float* bins, const float* w, const float* u, float* out, void* stream);
 int launch_ray_setup(int B, int S, int N, float z_cam, float ray_start, float ray_end, const float* u_jitter,

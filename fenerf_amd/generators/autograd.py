@@ -1,8 +1,10 @@
 """Differentiable final compositing: torch.autograd.Function wrappers whose forward AND backward are the
 HIP kernels behind fenerf_composite / fenerf_merge_composite / fenerf_composite_backward (include/fenerf.h) -- what
 torch autograd derives for fancy_integration (volumetric_rendering.py:23-50) after the cat / sort / gather of
-generators.py:508-519.  Depth is returned detached (the reference's losses never read it); z values and noise are
-constants of the graph, exactly as in the reference where they are produced under torch.no_grad()."""
+generators.py:508-519.  Depth is returned detached (the reference's losses never read it) unless the caller asks for a differentiable
+depth: the *DepthFunction variants of the nodes below (`depth_grad = True` on the node class), whose backward is
+fenerf_composite_backward_outputs / fenerf_render_backward_outputs; z values and noise are constants of the graph, exactly as in the
+reference where they are produced under torch.no_grad()."""
 import torch
 
 from .. import _lib, native
@@ -30,28 +32,86 @@ class ImageLayoutFunction(torch.autograd.Function):
         return d.reshape(ctx.shape), None, None
 
 
+def _depth_output(ctx, depth):
+    """A node's depth output: non-differentiable, as ever, unless the node class says `depth_grad = True` -- then an unused output's
+    gradient (depth's or rgb's) arrives as None, costs nothing, and reaches the library as a NULL pointer"""
+    ctx.depth_grad = bool(ctx._forward_cls.depth_grad)
+    if ctx.depth_grad:
+        ctx.set_materialize_grads(False)
+    else:
+        ctx.mark_non_differentiable(depth)
+
+
+def _upstream(ctx, g_rgb, g_depth, rgb_shape):
+    """-> (g_rgb, g_depth) as the composite backward takes them: contiguous fp32 or None; without depth_grad exactly what the node passed before"""
+    if not ctx.depth_grad:
+        return g_rgb, None
+    return (g_rgb.contiguous().float().reshape(rgb_shape) if g_rgb is not None else None,
+            g_depth.contiguous().float().reshape(-1) if g_depth is not None else None)
+
+
 class CompositeFunction(torch.autograd.Function):
+    depth_grad = False      # CompositeDepthFunction: depth is a differentiable output too
+
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)   # under autocast (the reference's training loop) inputs arrive as fp16
     def forward(ctx, rows, z, noise, opts):
         rgb, depth, _, _ = native.composite(rows, z, noise, opts, want_weights=False, want_wsum=False)
         ctx.opts = opts
         ctx.save_for_backward(rows, z, noise if noise is not None else rows.new_empty(0))
-        ctx.mark_non_differentiable(depth)
+        _depth_output(ctx, depth)
         return rgb, depth
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, g_rgb, _g_depth):
+    def backward(ctx, g_rgb, g_depth):
         rows, z, noise = ctx.saved_tensors
         lead, M, C = rows.shape[:-2], rows.shape[-2], rows.shape[-1]
-        d = native.composite_backward(g_rgb.reshape(-1, C - 1), rows.reshape(-1, M, C), z.reshape(-1, M), ctx.opts,
-                                      noise=noise.reshape(-1, M) if noise.numel() else None)
+        g_rgb, g_depth = _upstream(ctx, g_rgb, g_depth, (-1, C - 1))
+        if g_rgb is None and g_depth is None:
+            return None, None, None, None
+        d = native.composite_backward(g_rgb.reshape(-1, C - 1) if g_rgb is not None else None, rows.reshape(-1, M, C), z.reshape(-1, M), ctx.opts,
+                                      noise=noise.reshape(-1, M) if noise.numel() else None, g_depth=g_depth)
+        return d.reshape(*lead, M, C), None, None, None
+
+
+class CompositeDepthFunction(CompositeFunction):
+    """CompositeFunction whose depth output carries the graph too (backward: fenerf_composite_backward_outputs)."""
+    depth_grad = True
+
+
+class CompositeOutputsFunction(torch.autograd.Function):
+    """rows [..., M, C], z [..., M], noise or None -> (rgb [..., C-1], depth [...], weights [..., M] in sorted order, wsum [...]): every
+    output of fancy_integration (volumetric_rendering.py:23-50; wsum = sum of the weights before the last_back adjustment, :40)
+    differentiable wrt the rows -- the node behind the drop-in volumetric_rendering.fancy_integration under grad.  Values are
+    native.composite's; backward is fenerf_composite_backward_outputs with NULL for every output the loss does not read."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, rows, z, noise, opts):
+        rgb, depth, weights, wsum = native.composite(rows, z, noise, opts)
+        ctx.opts = opts
+        ctx.save_for_backward(rows, z, noise if noise is not None else rows.new_empty(0))
+        ctx.set_materialize_grads(False)
+        return rgb, depth, weights, wsum
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g_rgb, g_depth, g_weights, g_wsum):
+        if g_rgb is None and g_depth is None and g_weights is None and g_wsum is None:
+            return None, None, None, None
+        rows, z, noise = ctx.saved_tensors
+        lead, M, C = rows.shape[:-2], rows.shape[-2], rows.shape[-1]
+        f = lambda g, *shape: g.contiguous().float().reshape(*shape) if g is not None else None
+        d = native.composite_backward(f(g_rgb, -1, C - 1), rows.reshape(-1, M, C), z.reshape(-1, M), ctx.opts,
+                                      noise=noise.reshape(-1, M) if noise.numel() else None, g_depth=f(g_depth, -1), g_weights=f(g_weights, -1, M),
+                                      g_wsum=f(g_wsum, -1))
         return d.reshape(*lead, M, C), None, None, None
 
 
 class MergeCompositeFunction(torch.autograd.Function):
     """fine / coarse [BR,N,C] with their own depths [BR,N] -> (rgb [BR,C-1], depth [BR])."""
+    depth_grad = False      # MergeCompositeDepthFunction: depth is a differentiable output too
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)   # under autocast (the reference's training loop) inputs arrive as fp16
@@ -60,16 +120,24 @@ class MergeCompositeFunction(torch.autograd.Function):
                                                      want_wsum=False, want_z=False)
         ctx.opts = opts
         ctx.save_for_backward(fine, coarse, z_fine, z_coarse, noise if noise is not None else fine.new_empty(0))
-        ctx.mark_non_differentiable(depth)
+        _depth_output(ctx, depth)
         return rgb, depth
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, g_rgb, _g_depth):
+    def backward(ctx, g_rgb, g_depth):
         fine, coarse, z_fine, z_coarse, noise = ctx.saved_tensors
+        g_rgb, g_depth = _upstream(ctx, g_rgb, g_depth, (fine.shape[0], fine.shape[-1] - 1))
+        if g_rgb is None and g_depth is None:
+            return (None,) * 6
         d_f, d_c = native.composite_backward(g_rgb, fine, z_fine, ctx.opts, rows_b=coarse, z_b=z_coarse,
-                                             noise=noise if noise.numel() else None)
+                                             noise=noise if noise.numel() else None, g_depth=g_depth)
         return d_f, d_c, None, None, None, None
+
+
+class MergeCompositeDepthFunction(MergeCompositeFunction):
+    """MergeCompositeFunction whose depth output carries the graph too (backward: fenerf_composite_backward_outputs)."""
+    depth_grad = True
 
 
 def _hierarchical_forward(ctx, module, opts, copts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, params, film_only):
@@ -115,8 +183,9 @@ def _hierarchical_forward(ctx, module, opts, copts, lock_view, origins, dirs, z_
     empty = origins.new_empty(0)
     ctx.save_for_backward(pts2, rd if rd is not None else empty, fg, pg, fa, pa, out2, tape2, tape_e2 if G else empty, z_f, zc,
                           noise_f if noise_f is not None else empty, *params)
-    ctx.mark_non_differentiable(depth)
-    return rgb.reshape(B, R, C - 1), depth.reshape(B, R)
+    depth = depth.reshape(B, R)
+    _depth_output(ctx, depth)
+    return rgb.reshape(B, R, C - 1), depth
 
 
 # The render runs through fenerf_render_forward_save / fenerf_render_backward (round 5: chunk planning, workspaces, launch order and gradient
@@ -137,11 +206,11 @@ def _abi_forward(ctx, module, opts, lock_view, origins, dirs, z_c, u, noise_c, n
     ctx.module, ctx.nat, ctx.opts, ctx.dims, ctx.lock_view = module, nat, opts, (B, R, N), lock_view
     ctx.pack_generation = nat.pack_generation
     ctx.save_for_backward(save, z_c, noise_f if noise_f is not None else origins.new_empty(0), *params)
-    ctx.mark_non_differentiable(depth)
+    _depth_output(ctx, depth)
     return rgb, depth
 
 
-def _python_composite_backward(nat, opts, dims, g_rgb, rd, film, out2, z_f, zc, noise_f):
+def _python_composite_backward(nat, opts, dims, g_rgb, rd, film, out2, z_f, zc, noise_f, g_depth=None):
     """Start of the backward of the Python orchestration, over what _hierarchical_forward saved: the composite backward of both passes
     -> (d_out2 [2B,Pp,C], film2, rd2): the chain's upstream gradient, FiLM parameters and view directions over 2B pass-major "images"
     (image b' = pass * B + b: coarse | fine)."""
@@ -149,12 +218,13 @@ def _python_composite_backward(nat, opts, dims, g_rgb, rd, film, out2, z_f, zc, 
     C = nat.C
     fine, coarse = out2[B:, :P].reshape(B * R, N, C), out2[:B, :P].reshape(B * R, N, C)
     noise = noise_f if noise_f.numel() else None
+    g_rgb = g_rgb.reshape(B * R, C - 1) if g_rgb is not None else None         # None: a loss that reads the depth only (g_depth given)
     if Pp == P:     # whole tiles per image: the composite backward writes the chain's input directly
         d_out2 = torch.empty_like(out2)
-        native.composite_backward(g_rgb.reshape(B * R, C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc, noise=noise,
-                                  out_a=d_out2[B:].view(B * R, N, C), out_b=d_out2[:B].view(B * R, N, C))
+        native.composite_backward(g_rgb, fine, z_f, opts, rows_b=coarse, z_b=zc, noise=noise,
+                                  out_a=d_out2[B:].view(B * R, N, C), out_b=d_out2[:B].view(B * R, N, C), g_depth=g_depth)
     else:
-        d_f, d_c = native.composite_backward(g_rgb.reshape(B * R, C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc, noise=noise)
+        d_f, d_c = native.composite_backward(g_rgb, fine, z_f, opts, rows_b=coarse, z_b=zc, noise=noise, g_depth=g_depth)
         d_out2 = torch.zeros((2 * B, Pp, C), dtype=torch.float32, device=out2.device)
         d_out2[:B, :P] = d_c.reshape(B, P, C)
         d_out2[B:, :P] = d_f.reshape(B, P, C)
@@ -181,6 +251,7 @@ class HierarchicalRenderFunction(torch.autograd.Function):
     SirenFunction nodes.  Inputs: rays (origins / dirs [B,R,3], coarse depths z_c [B,R,N]), the caller's draws (u [B*R,N],
     noise_c / noise_f or None), composite options, raw FiLM parameters, then module._render_params().
     -> (rgb [B,R,C-1], depth [B,R])."""
+    depth_grad = False      # HierarchicalRenderDepthFunction: depth is a differentiable output too
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -198,11 +269,17 @@ class HierarchicalRenderFunction(torch.autograd.Function):
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, g_rgb, _g_depth):
+    def backward(ctx, g_rgb, g_depth):
         module, nat, opts = ctx.module, ctx.nat, ctx.opts
         _siren_autograd.check_same_weights(ctx, nat)
         need = ctx.needs_input_grad
         film_only = not any(need[14:])
+        if ctx.depth_grad:
+            g_rgb, g_depth = _upstream(ctx, g_rgb, g_depth, (ctx.dims[0], ctx.dims[1], nat.C - 1))
+            if g_rgb is None and g_depth is None:
+                return (None,) * len(need)
+        else:
+            g_depth = None
         if ctx.abi:
             B, R, N = ctx.dims
             save, z_c, noise_f, *params = ctx.saved_tensors
@@ -211,16 +288,17 @@ class HierarchicalRenderFunction(torch.autograd.Function):
             if need[4] or need[5]:
                 w_geo, w_col = _siren_autograd.film_layer_weights(module, params)
                 ray_grads = (w_geo[0], w_col[0], need[4], need[5])
-            r, g_grid = nat.render_backward(B, R, N, save, z_c, noise_f if noise_f.numel() else None, opts, g_rgb.contiguous().float(), film_only,
+            r, g_grid = nat.render_backward(B, R, N, save, z_c, noise_f if noise_f.numel() else None, opts,
+                                            g_rgb.contiguous().float() if g_rgb is not None else None, film_only,
                                             lock_view=ctx.lock_view, tape_format=ctx.tape_format,
                                             weights=_siren_autograd.film_layer_weights(module, params) if ctx.tape_format else None,
                                             chunk_points=_siren_autograd.BACKWARD_CHUNK_POINTS, film_sums_budget_bytes=_siren_autograd.FILM_SUMS_BUDGET_BYTES,
-                                            ray_grads=ray_grads)
+                                            ray_grads=ray_grads, g_depth=g_depth)
             return (None,) * 4 + (r.get("d_origins"), r.get("d_dirs")) + (None,) * 4 \
                 + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, d_grid_ncdhw=g_grid)
         B, R, N, P, Pp = ctx.dims
         pts2, rd, fg, pg, fa, pa, out2, tape2, tape_e2, z_f, zc, noise_f, *params = ctx.saved_tensors
-        d_out2, film2, rd2 = _python_composite_backward(nat, opts, ctx.dims, g_rgb, rd, (fg, pg, fa, pa), out2, z_f, zc, noise_f)
+        d_out2, film2, rd2 = _python_composite_backward(nat, opts, ctx.dims, g_rgb, rd, (fg, pg, fa, pa), out2, z_f, zc, noise_f, g_depth)
         rows = _siren_autograd.begin_grid_gradient(module, nat, 2 * B * Pp, film_only)
         input_grads = None
         if need[4] or need[5]:      # per-sample d points / d view directions of both passes, chunk by chunk, then one reduction per ray
@@ -239,6 +317,13 @@ class HierarchicalRenderFunction(torch.autograd.Function):
         return (None,) * 4 + (d_o, d_d) + (None,) * 4 + _siren_autograd.grads_tail(module, nat, params, r, need, 10, film_only, B=B, d_grid_cl=d_grid)
 
 
+class HierarchicalRenderDepthFunction(HierarchicalRenderFunction):
+    """HierarchicalRenderFunction whose depth output carries the graph too: a loss may read the depth map (a depth target, a second view's
+    geometry) beside or instead of the pixels.  backward: fenerf_render_backward_outputs (C-ABI route) / the composite backward's
+    depth term (Python orchestration); everything behind the composite backward is the same."""
+    depth_grad = True
+
+
 # ----------------------------------------------------------------------------------------------------------------------------------
 # Exact sparsity of the backward pass (round 6; opt-in per module, `siren.sparse_backward = True`).  A sample whose row of upstream
 # gradients is ALL ZERO contributes exact zeros to every gradient of the step -- and under the reference's relu clamp that is every
@@ -253,9 +338,14 @@ class HierarchicalRenderFunction(torch.autograd.Function):
 # the dense backward plus a re-evaluation (`siren.sparse_backward = "auto"` then falls back to the dense node, below).  The backward does not wait for the device: the length of its buffers is a bound the FORWARD
 # computes (samples with sigma + max|noise| std > 0, + one per ray with last_back: a row is non-zero only if alpha > 0), fetched
 # asynchronously; which samples are kept is decided on the device from the rows themselves.
+# A differentiable depth (the Sparse*DepthFunction variants) leaves that bound as it is: gradients of depth / weights / wsum reach a
+# row's density only through act'(sigma + noise) (`dact` in composite_backward_kernel), which is 0 -- a selected zero -- at a clamped
+# sample, and they never reach its colour channels (those are w'_k g_rgb_c whatever else the loss reads).  So the rows that can be
+# non-zero are the same rows.
 # ----------------------------------------------------------------------------------------------------------------------------------
 class SparseHierarchicalRenderFunction(torch.autograd.Function):
     """HierarchicalRenderFunction's signature and results; see the block comment above."""
+    depth_grad = False      # SparseHierarchicalRenderDepthFunction: depth is a differentiable output too
 
     # report and check state of the LAST sparse backward of the process (either sparse node)
     last_kept = None            # (kept samples: a device scalar -- read it after the step, all samples)
@@ -303,20 +393,33 @@ class SparseHierarchicalRenderFunction(torch.autograd.Function):
         ctx.module, ctx.nat, ctx.opts, ctx.dims, ctx.lock_view = module, nat, opts, (B, R, N), lock_view
         ctx.pack_generation = nat.pack_generation
         ctx.save_for_backward(origins, dirs, zc, z_f, coarse, fine, noise_f if noise_f is not None else origins.new_empty(0), fg, pg, fa, pa, *params)
-        ctx.mark_non_differentiable(depth)
-        return rgb.reshape(B, R, C - 1), depth.reshape(B, R)
+        depth = depth.reshape(B, R)
+        _depth_output(ctx, depth)
+        return rgb.reshape(B, R, C - 1), depth
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, g_rgb, _g_depth):
+    def backward(ctx, g_rgb, g_depth):
         module, nat, opts = ctx.module, ctx.nat, ctx.opts
         _siren_autograd.check_same_weights(ctx, nat)
         need = ctx.needs_input_grad
         B, R, N = ctx.dims
         origins, dirs, zc, z_f, coarse, fine, noise_f, fg, pg, fa, pa, *params = ctx.saved_tensors
-        d_f, d_c = native.composite_backward(g_rgb.contiguous().float().reshape(B * R, nat.C - 1), fine, z_f, opts, rows_b=coarse, z_b=zc,
-                                             noise=noise_f if noise_f.numel() else None)
-        return _sparse_siren_backward(ctx, module, nat, need, B, R, N, 2, d_c, d_f, zc, z_f, origins, dirs, (fg, pg, fa, pa), params, g_rgb)
+        if ctx.depth_grad:
+            g_rgb, g_depth = _upstream(ctx, g_rgb, g_depth, (B * R, nat.C - 1))
+            if g_rgb is None and g_depth is None:
+                return (None,) * len(need)
+        else:
+            g_rgb, g_depth = g_rgb.contiguous().float().reshape(B * R, nat.C - 1), None
+        d_f, d_c = native.composite_backward(g_rgb, fine, z_f, opts, rows_b=coarse, z_b=zc, noise=noise_f if noise_f.numel() else None,
+                                             g_depth=g_depth)
+        return _sparse_siren_backward(ctx, module, nat, need, B, R, N, 2, d_c, d_f, zc, z_f, origins, dirs, (fg, pg, fa, pa), params,
+                                      [g for g in (g_rgb, g_depth) if g is not None])
+
+
+class SparseHierarchicalRenderDepthFunction(SparseHierarchicalRenderFunction):
+    """SparseHierarchicalRenderFunction whose depth output carries the graph too (g_depth goes to the composite backward it already calls)."""
+    depth_grad = True
 
 
 def _record_bound(ctx, opts, sig, noise, B, R):
@@ -336,9 +439,10 @@ def _record_bound(ctx, opts, sig, noise, B, R):
         ctx.cap_host, ctx.cap_ready = None, None
 
 
-def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc, z_f, origins, dirs, film, params, g_rgb):
+def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc, z_f, origins, dirs, film, params, upstream):
     """The SIREN part of a sparse backward: d_c (/ d_f) [B*R, N, C] = gradients wrt the outputs of the pass(es) -> the autograd node's
-    return tuple (10 Nones, four FiLM gradients, parameter gradients).  passes = 2: coarse | fine; 1: d_f = z_f = None."""
+    return tuple (10 Nones, four FiLM gradients, parameter gradients).  passes = 2: coarse | fine; 1: d_f = z_f = None.  upstream: the
+    node's upstream gradients (g_rgb, and g_depth of a differentiable depth) -- only asked whether they are finite."""
     fg, pg, fa, pa = film
     S = passes * R * N                                                          # samples per image
     dev = origins.device
@@ -392,7 +496,9 @@ def _sparse_siren_backward(ctx, module, nat, need, B, R, N, passes, d_c, d_f, zc
     # non-finite too (a GradScaler skips it).  So the flag is raised only while the upstream gradient is finite; otherwise the rows that
     # were dropped are made up for by a NaN added to every gradient this node returns (all on the device, nothing waits).
     overflowed = (flags[0] if whole else torch.stack(flags).max()) != 0
-    g_ok = torch.isfinite(g_rgb).all()
+    g_ok = torch.isfinite(upstream[0]).all()
+    for g in upstream[1:]:
+        g_ok = g_ok & torch.isfinite(g).all()
     SparseHierarchicalRenderFunction._check_overflow(overflowed & g_ok)
     poison = torch.where(overflowed & ~g_ok, float("nan"), 0.0)
     SparseHierarchicalRenderFunction.last_kept = (kept[0] if whole else torch.stack(kept).sum(), S * B)            # for reports (a device scalar: read it after the step)
@@ -411,6 +517,7 @@ class SparseSinglePassRenderFunction(torch.autograd.Function):
     """The render WITHOUT importance resampling (hierarchical_sample False: generators.py:479-483 + :519 on the coarse samples -- the
     reference's inversion renders, inverse_render_double_semantic.py:225-247) as one node with the exact-sparsity backward of the block
     comment above: SparseHierarchicalRenderFunction's signature (u and noise_c unused) and results."""
+    depth_grad = False      # SparseSinglePassRenderDepthFunction: depth is a differentiable output too
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -425,19 +532,32 @@ class SparseSinglePassRenderFunction(torch.autograd.Function):
         ctx.module, ctx.nat, ctx.opts, ctx.dims, ctx.lock_view = module, nat, opts, (B, R, N), lock_view
         ctx.pack_generation = nat.pack_generation
         ctx.save_for_backward(origins, dirs, zc, rows, noise_f if noise_f is not None else origins.new_empty(0), fg, pg, fa, pa, *params)
-        ctx.mark_non_differentiable(depth)
-        return rgb.reshape(B, R, C - 1), depth.reshape(B, R)
+        depth = depth.reshape(B, R)
+        _depth_output(ctx, depth)
+        return rgb.reshape(B, R, C - 1), depth
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, g_rgb, _g_depth):
+    def backward(ctx, g_rgb, g_depth):
         module, nat, opts = ctx.module, ctx.nat, ctx.opts
         _siren_autograd.check_same_weights(ctx, nat)
         B, R, N = ctx.dims
         origins, dirs, zc, rows, noise_f, fg, pg, fa, pa, *params = ctx.saved_tensors
         C = nat.C
-        d = native.composite_backward(g_rgb.contiguous().float().reshape(B * R, C - 1), rows, zc, opts, noise=noise_f if noise_f.numel() else None)
-        return _sparse_siren_backward(ctx, module, nat, ctx.needs_input_grad, B, R, N, 1, d, None, zc, None, origins, dirs, (fg, pg, fa, pa), params, g_rgb)
+        if ctx.depth_grad:
+            g_rgb, g_depth = _upstream(ctx, g_rgb, g_depth, (B * R, C - 1))
+            if g_rgb is None and g_depth is None:
+                return (None,) * len(ctx.needs_input_grad)
+        else:
+            g_rgb, g_depth = g_rgb.contiguous().float().reshape(B * R, C - 1), None
+        d = native.composite_backward(g_rgb, rows, zc, opts, noise=noise_f if noise_f.numel() else None, g_depth=g_depth)
+        return _sparse_siren_backward(ctx, module, nat, ctx.needs_input_grad, B, R, N, 1, d, None, zc, None, origins, dirs, (fg, pg, fa, pa), params,
+                                      [g for g in (g_rgb, g_depth) if g is not None])
+
+
+class SparseSinglePassRenderDepthFunction(SparseSinglePassRenderFunction):
+    """SparseSinglePassRenderFunction whose depth output carries the graph too."""
+    depth_grad = True
 
 
 # `siren.sparse_backward = "auto"`: the sparse node while it pays, the dense node otherwise.  What the sparse backward costs is set by the
@@ -578,6 +698,7 @@ class HierarchicalWeightStage(torch.autograd.Function):
 class HierarchicalRenderSplitFunction(torch.autograd.Function):
     """Downstream node: the render itself.  Differentiable inputs: the weight stage's token and the grid.  backward: composite backward,
     every chunk's chain (with the fused grid scatter), the grid gradient; the dumps go to the weight stage through `state`."""
+    depth_grad = False      # the two-node form has no depth variant (hierarchical_render_split refuses up front)
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -654,8 +775,11 @@ class HierarchicalRenderSplitFunction(torch.autograd.Function):
         return (None, g_token, g_grid) + (None,) * 14
 
 
-def hierarchical_render_split(module, opts, copts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa):
+def hierarchical_render_split(module, opts, copts, lock_view, origins, dirs, z_c, u, noise_c, noise_f, fg, pg, fa, pa, depth_grad=False):
     """The two-node form of HierarchicalRenderFunction.apply(...) for a module with a feature grid (see the banner above)."""
+    if depth_grad:
+        raise NotImplementedError("fenerf_amd: the two-node (split_backward) render has no differentiable depth (fenerf_render_backward_stage "
+                                  "takes no depth gradient); set siren.split_backward = False")
     params = module._render_params()
     grid = module._roles(params)["grid"]
     state = _SplitState()

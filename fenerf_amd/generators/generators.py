@@ -18,8 +18,10 @@ import torch.nn as nn
 
 from .. import _lib, native
 from ..siren import autograd as _siren_autograd
-from .autograd import (check_ray_grads_supported, rays_require_grad, CompositeFunction, HierarchicalRenderFunction, ImageLayoutFunction, MergeCompositeFunction, SparseHierarchicalRenderFunction,
-                       SparseSinglePassRenderFunction, hierarchical_render_split, sparse_auto_choice)
+from .autograd import (check_ray_grads_supported, rays_require_grad, CompositeDepthFunction, CompositeFunction, HierarchicalRenderDepthFunction,
+                       HierarchicalRenderFunction, ImageLayoutFunction, MergeCompositeFunction, SparseHierarchicalRenderDepthFunction,
+                       SparseHierarchicalRenderFunction, SparseSinglePassRenderDepthFunction, SparseSinglePassRenderFunction, hierarchical_render_split,
+                       sparse_auto_choice)
 from . import volumetric_rendering as VR
 from .volumetric_rendering import _DEFAULT_DRAWS, sample_rays
 
@@ -138,12 +140,13 @@ class _Generator3dBase(nn.Module):
                                             any(isinstance(t, torch.Tensor) and t.requires_grad for t in pose))
 
     def _render_grad(self, film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
-                     hierarchical_sample, sample_dist, lock_view_dependence, kwargs):
+                     hierarchical_sample, sample_dist, lock_view_dependence, kwargs, return_depth=False):
         """The differentiable render of generators.py:468-519: same random draws in the same order as _render, same kernels,
         but the two SIREN passes and the final integration are autograd nodes with native backward kernels.  The coarse
         weights and the resampled depths are constants (computed under no_grad in the reference too, :485-503).
         With kwargs['grad_points'] < img_size^2 only a random subset of the rays is differentiable (part_forward, :858-910).
-        Returns (pixels [B,R,C-1], depth [B,R] or None, pitch, yaw)."""
+        return_depth: the depth map is wanted IN the graph (the *DepthFunction nodes); the draws, the pixels and the poses are the same.
+        Returns (pixels [B,R,C-1], depth [B,R] -- None for a part_forward without return_depth --, pitch, yaw)."""
         B = film[0].shape[0]
         dev = self.device
         R, N = img_size * img_size, num_steps
@@ -154,25 +157,29 @@ class _Generator3dBase(nn.Module):
         grad_points = kwargs.get("grad_points", R)
         if grad_points == R:
             rgb, depth = self._render_rays(film, origins, dirs, z_c, hierarchical_sample, lock_view_dependence, kwargs,
-                                           self._wants_grad(film, origins, dirs))
+                                           self._wants_grad(film, origins, dirs), depth_grad=return_depth)
             return rgb, depth, pitch, yaw
         # part_forward: randperm AFTER the camera draws, then the gradient part's draws, then the rest's (:880-900)
         assert R > grad_points
         perm = d.randperm(R, dev)
         idx_g, idx_n = perm[:grad_points], perm[grad_points:]
         take = lambda t, idx: t[:, idx].contiguous()
-        rgb_g, _ = self._render_rays(film, take(origins, idx_g), take(dirs, idx_g), take(z_c, idx_g), hierarchical_sample,
-                                     lock_view_dependence, kwargs, self._wants_grad(film, origins, dirs))
+        rgb_g, depth_g = self._render_rays(film, take(origins, idx_g), take(dirs, idx_g), take(z_c, idx_g), hierarchical_sample,
+                                           lock_view_dependence, kwargs, self._wants_grad(film, origins, dirs), depth_grad=return_depth)
         with torch.no_grad():
-            rgb_n, _ = self._render_rays(film, take(origins, idx_n), take(dirs, idx_n), take(z_c, idx_n), hierarchical_sample,
-                                         lock_view_dependence, kwargs, False)
+            rgb_n, depth_n = self._render_rays(film, take(origins, idx_n), take(dirs, idx_n), take(z_c, idx_n), hierarchical_sample,
+                                               lock_view_dependence, kwargs, False)
         pixels = torch.zeros((B, R, rgb_g.shape[-1]), dtype=rgb_g.dtype, device=dev)
         pixels = pixels.index_copy(1, idx_g, rgb_g).index_copy(1, idx_n, rgb_n)
-        return pixels, None, pitch, yaw
+        depth = None
+        if return_depth:        # the no-grad rays' depth is scattered in like their pixels
+            depth = torch.zeros((B, R), dtype=depth_g.dtype, device=dev).index_copy(1, idx_g, depth_g).index_copy(1, idx_n, depth_n)
+        return pixels, depth, pitch, yaw
 
-    def _render_rays(self, film, origins, dirs, z_c, hierarchical_sample, lock_view_dependence, kwargs, differentiable):
+    def _render_rays(self, film, origins, dirs, z_c, hierarchical_sample, lock_view_dependence, kwargs, differentiable, depth_grad=False):
         """origins / dirs [B,R,3], z_c [B,R,N] -> (rgb [B,R,C-1], depth [B,R]).  Draws: coarse noise randn [B,R,N,1] and u rand
-        [B*R,N] (hierarchical only), final noise randn [B,R,M,1].  differentiable=False is the fused no-grad call."""
+        [B*R,N] (hierarchical only), final noise randn [B,R,M,1].  differentiable=False is the fused no-grad call.  depth_grad: depth
+        is a differentiable output too (the nodes' *DepthFunction variants); without it depth is detached and the launches are what they were."""
         fg, pg, fa, pa = film
         B, R, N = z_c.shape
         dev = self.device
@@ -213,12 +220,12 @@ class _Generator3dBase(nn.Module):
                                           "siren.sparse_backward = False or 'auto'")
         if not hierarchical_sample:
             if sparse:      # opt-in exact-sparsity backward (autograd.py), the render without importance resampling: the reference's inversion renders
-                return SparseSinglePassRenderFunction.apply(self.siren, opts, None, bool(lock_view_dependence), origins, dirs, z_c, None, None,
-                                                            noise_f.reshape(B * R, M) if use_noise else None, fg, pg, fa, pa,
-                                                            *self.siren._render_params())
+                node = SparseSinglePassRenderDepthFunction if depth_grad else SparseSinglePassRenderFunction
+                return node.apply(self.siren, opts, None, bool(lock_view_dependence), origins, dirs, z_c, None, None,
+                                  noise_f.reshape(B * R, M) if use_noise else None, fg, pg, fa, pa, *self.siren._render_params())
             coarse = field(z_c)
-            rgb, depth = CompositeFunction.apply(coarse.reshape(B * R, N, C), z_c.reshape(B * R, N),
-                                                 noise_f.reshape(B * R, M) if use_noise else None, opts)
+            rgb, depth = (CompositeDepthFunction if depth_grad else CompositeFunction).apply(
+                coarse.reshape(B * R, N, C), z_c.reshape(B * R, N), noise_f.reshape(B * R, M) if use_noise else None, opts)
             return rgb.reshape(B, R, C - 1), depth.reshape(B, R)
         # both SIREN passes + the merged composite as one autograd node (one chain launch and one set of weight-gradient
         # launches for the two passes)
@@ -230,8 +237,8 @@ class _Generator3dBase(nn.Module):
             # opt-in: the backward runs only over the samples whose upstream gradient row is not all zero (autograd.py: exact).  It goes before
             # the two-node form below: what that form hides behind the weight-gradient kernels (the grid's all-reduce, ~1.5 ms) is less than
             # what this one removes, and its backward is short
-            return SparseHierarchicalRenderFunction.apply(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg,
-                                                          fa, pa, *params)
+            node = SparseHierarchicalRenderDepthFunction if depth_grad else SparseHierarchicalRenderFunction
+            return node.apply(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg, fa, pa, *params)
         split = getattr(self.siren, "split_backward", False) and grid is not None and grid.requires_grad and \
             any(p.requires_grad for p in params if p is not grid)
         if split and pose:
@@ -239,9 +246,18 @@ class _Generator3dBase(nn.Module):
                                       "siren.split_backward = False")
         if split:
             # two autograd nodes: the grid gradient reaches DistributedDataParallel before the weight-gradient kernels run (autograd.py)
-            return hierarchical_render_split(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg, fa, pa)
-        return HierarchicalRenderFunction.apply(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg, fa, pa,
-                                                *params)
+            return hierarchical_render_split(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg, fa, pa,
+                                             depth_grad=depth_grad)         # (refuses a differentiable depth)
+        node = HierarchicalRenderDepthFunction if depth_grad else HierarchicalRenderFunction
+        return node.apply(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg, fa, pa, *params)
+
+    @staticmethod
+    def _outputs(pixels, poses, depth, img_size, return_depth):
+        """what forward / forward_with_frequencies / part_forward return: the reference's (pixels, poses), or with return_depth=True
+        (pixels, poses, depth [B, S, S]) -- depth in the graph when the render is differentiable"""
+        if not return_depth:
+            return pixels, poses
+        return pixels, poses, depth.reshape(depth.shape[0], img_size, img_size)
 
     def _finish(self, pixels, batch_size, img_size):
         if self.softmax_label:
@@ -301,7 +317,7 @@ class DoubleImplicitGenerator3d(_Generator3dBase):
         return out
 
     def forward(self, z_geo, z_app, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
-                hierarchical_sample, sample_dist=None, lock_view_dependence=False, **kwargs):
+                hierarchical_sample, sample_dist=None, lock_view_dependence=False, return_depth=False, **kwargs):
         """-> (pixels [B, output_dim-1, S, S] in [-1,1], cat(pitch, yaw) [B,2])   (generators.py:452-527)."""
         batch_size = z_app.shape[0]
         fg, pg = self.siren.geo_mapping_network(z_geo)
@@ -310,28 +326,29 @@ class DoubleImplicitGenerator3d(_Generator3dBase):
             # generators.py:459-461 -- NB the reference drops the caller's sample_dist / lock_view_dependence on this path
             # (camera at the mean pose, view dependence on); kept as is
             return self.part_forward(z_geo, z_app, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
-                                     hierarchical_sample, sample_dist=None, lock_view_dependence=False, **kwargs)
+                                     hierarchical_sample, sample_dist=None, lock_view_dependence=False, return_depth=return_depth, **kwargs)
         if self._wants_grad((fg, pg, fa, pa), h_mean, v_mean):
             pixels, depth, pitch, yaw = self._render_grad((fg, pg, fa, pa), img_size, fov, ray_start, ray_end, num_steps, h_stddev,
                                                           v_stddev, h_mean, v_mean, hierarchical_sample, sample_dist,
-                                                          lock_view_dependence, kwargs)
-            return self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1)
+                                                          lock_view_dependence, kwargs, return_depth=return_depth)
+            return self._outputs(self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
         # forward() ignores fill_mode (generators.py:519) -> C-1 channels
         pixels, depth, _, pitch, yaw = self._render((fg, pg, fa, pa), img_size, fov, ray_start, ray_end, num_steps, h_stddev,
                                                     v_stddev, h_mean, v_mean, hierarchical_sample, sample_dist,
                                                     lock_view_dependence, kwargs, use_fill=False, third=None)
         pixels = self._finish_scaled(pixels, batch_size, img_size)
-        return pixels, torch.cat([pitch, yaw], -1)
+        return self._outputs(pixels, torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
 
     def part_forward(self, z_geo, z_app, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
-                     hierarchical_sample, sample_dist=None, lock_view_dependence=False, **kwargs):
+                     hierarchical_sample, sample_dist=None, lock_view_dependence=False, return_depth=False, **kwargs):
         """Gradient on kwargs['grad_points'] random rays only, the rest rendered without (generators.py:858-910)."""
         batch_size = z_app.shape[0]
         fg, pg = self.siren.geo_mapping_network(z_geo)
         fa, pa = self.siren.app_mapping_network(z_app)
-        pixels, _, pitch, yaw = self._render_grad((fg, pg, fa, pa), img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
-                                                  h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence, kwargs)
-        return self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1)
+        pixels, depth, pitch, yaw = self._render_grad((fg, pg, fa, pa), img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
+                                                      h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence, kwargs,
+                                                      return_depth=return_depth)
+        return self._outputs(self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
 
     def point_forward(self, transformed_points, transformed_ray_directions_expanded, transformed_ray_origins,
                       transformed_ray_directions, z_vals, z_geo, z_app, num_steps, hierarchical_sample,
@@ -418,21 +435,21 @@ class DoubleImplicitGenerator3d(_Generator3dBase):
 
     def forward_with_frequencies(self, frequencies_geo, frequencies_app, phase_shifts_geo, phase_shifts_app, img_size, fov,
                                  ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean, hierarchical_sample,
-                                 sample_dist=None, lock_view_dependence=False, **kwargs):
+                                 sample_dist=None, lock_view_dependence=False, return_depth=False, **kwargs):
         """-> (pixels [B, output_dim-1, S, S], poses)   (generators.py:735-797)."""
         batch_size = frequencies_app.shape[0]
         film = (frequencies_geo, phase_shifts_geo, frequencies_app, phase_shifts_app)
         if self._wants_grad(film, h_mean, v_mean):
             pixels, depth, pitch, yaw = self._render_grad(film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
                                                           h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence,
-                                                          kwargs)
-            return self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1)
+                                                          kwargs, return_depth=return_depth)
+            return self._outputs(self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
         pixels, depth, _, pitch, yaw = self._render((frequencies_geo, phase_shifts_geo, frequencies_app, phase_shifts_app),
                                                     img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean,
                                                     v_mean, hierarchical_sample, sample_dist, lock_view_dependence, kwargs,
                                                     use_fill=False, third=None)
         pixels = self._finish_scaled(pixels, batch_size, img_size)
-        return pixels, torch.cat([pitch, yaw], -1)
+        return self._outputs(pixels, torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
 
 
 class ImplicitGenerator3d(_Generator3dBase):
@@ -482,7 +499,7 @@ class ImplicitGenerator3d(_Generator3dBase):
                 self.avg_phase_shifts + psi * (raw_phase_shifts - self.avg_phase_shifts))
 
     def forward(self, z, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean, hierarchical_sample,
-                sample_dist=None, lock_view_dependence=False, **kwargs):
+                sample_dist=None, lock_view_dependence=False, return_depth=False, **kwargs):
         """-> (pixels [B,3,S,S], poses)   (generators.py:32-119)."""
         batch_size = z.shape[0]
         frequencies, phase_shifts = self.siren.mapping_network(z)
@@ -490,13 +507,13 @@ class ImplicitGenerator3d(_Generator3dBase):
         if self._wants_grad(film, h_mean, v_mean):
             pixels, depth, pitch, yaw = self._render_grad(film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
                                                           h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence,
-                                                          kwargs)
-            return self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1)
+                                                          kwargs, return_depth=return_depth)
+            return self._outputs(self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
         pixels, depth, _, pitch, yaw = self._render(film, img_size, fov, ray_start, ray_end,
                                                     num_steps, h_stddev, v_stddev, h_mean, v_mean, hierarchical_sample,
                                                     sample_dist, lock_view_dependence, kwargs, use_fill=False, third=None)
         pixels = self._finish_scaled(pixels, batch_size, img_size)
-        return pixels, torch.cat([pitch, yaw], -1)
+        return self._outputs(pixels, torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
 
     def staged_forward(self, z, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean, psi=1,
                        lock_view_dependence=False, max_batch_size=50000, depth_map=False, near_clip=0, far_clip=2,
@@ -531,20 +548,20 @@ class ImplicitGenerator3d(_Generator3dBase):
 
     def forward_with_frequencies(self, frequencies, phase_shifts, img_size, fov, ray_start, ray_end, num_steps, h_stddev,
                                  v_stddev, h_mean, v_mean, hierarchical_sample, sample_dist=None, lock_view_dependence=False,
-                                 **kwargs):
+                                 return_depth=False, **kwargs):
         """(generators.py:353-431)"""
         batch_size = frequencies.shape[0]
         film = self._film(frequencies, phase_shifts)
         if self._wants_grad(film, h_mean, v_mean):
             pixels, depth, pitch, yaw = self._render_grad(film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
                                                           h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence,
-                                                          kwargs)
-            return self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1)
+                                                          kwargs, return_depth=return_depth)
+            return self._outputs(self._finish_scaled(pixels, batch_size, img_size), torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
         pixels, depth, _, pitch, yaw = self._render(film, img_size, fov, ray_start, ray_end,
                                                     num_steps, h_stddev, v_stddev, h_mean, v_mean, hierarchical_sample,
                                                     sample_dist, lock_view_dependence, kwargs, use_fill=False, third=None)
         pixels = self._finish_scaled(pixels, batch_size, img_size)
-        return pixels, torch.cat([pitch, yaw], -1)
+        return self._outputs(pixels, torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
 
 
 class StyleGenerator3d(ImplicitGenerator3d):

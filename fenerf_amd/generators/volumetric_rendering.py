@@ -236,9 +236,16 @@ def sample_rays(n, num_steps, device, fov, resolution, ray_start, ray_end, h_std
 def fancy_integration(rgb_sigma, z_vals, device, noise_std=0.5, last_back=False, white_back=False, black_back=False,
                       clamp_mode=None, fill_mode=None, fill_color="black", draws=_DEFAULT_DRAWS):
     """NeRF alpha compositing on the GPU (HIP kernel behind fenerf_composite); reference :18-106.
-    rgb_sigma [B,R,M,C], z_vals [B,R,M,1] -> the reference's 3-tuple for the given fill_mode."""
+    rgb_sigma [B,R,M,C], z_vals [B,R,M,1] -> the reference's 3-tuple for the given fill_mode.  Under grad, with rgb_sigma.requires_grad
+    and no fill mode, all three are differentiable wrt rgb_sigma (z_vals and the noise are constants of the graph)."""
     opts = _lib.composite_opts(clamp_mode, noise_std, last_back, white_back, black_back, fill_mode, fill_color)
     noise = draws.randn(rgb_sigma[..., -1:].shape, rgb_sigma.device)  # always drawn, like the reference (:27)
+    if fill_mode is None and torch.is_grad_enabled() and rgb_sigma.requires_grad:
+        # rows that carry a graph: rgb, depth and weights carry it on, as the reference's three tensors do (:50) -- the same kernel and the
+        # same draw as below, behind a node whose backward is fenerf_composite_backward_outputs (fill modes stay undifferentiated)
+        from .autograd import CompositeOutputsFunction
+        rgb, depth, weights, _ = CompositeOutputsFunction.apply(rgb_sigma, z_vals.squeeze(-1), noise.squeeze(-1) if noise_std != 0 else None, opts)
+        return rgb, depth.unsqueeze(-1), weights.unsqueeze(-1)
     rgb, depth, weights, wsum = native.composite(rgb_sigma, z_vals.squeeze(-1), noise.squeeze(-1) if noise_std != 0 else None, opts)
     depth = depth.unsqueeze(-1)
     if fill_mode in ("weight", "eval_seg_padding_background", "eval_white_back"):

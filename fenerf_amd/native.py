@@ -898,13 +898,18 @@ class NativeModel:
         return w0, wc0
 
     def render_backward(self, B, R, N, save, z_coarse, noise_final, opts, g_rgb, film_only, lock_view=False, tape_format=0, weights=None,
-                        chunk_points=0, film_sums_budget_bytes=0, ray_grads=None):
+                        chunk_points=0, film_sums_budget_bytes=0, ray_grads=None, g_depth=None):
         """fenerf_render_backward: every gradient of the render in ONE call -> (dict like siren_param_grads -- FiLM gradients [B, n*H], both
         passes summed; weight / bias gradients unless film_only --, d_grid [1,32,D,H,W] or None).
         ray_grads: None, or (w_geo0, w_color0, want_origins, want_dirs) -- layer 0's [H,3] and colour layer 0's [H,3+G+H] nn.Linear weights
         and which of the two ray gradients to deliver: fenerf_render_backward_rays, and the result dict gains d_origins / d_dirs [B,R,3]
-        (None for the one not asked for)."""
+        (None for the one not asked for).
+        g_depth [B,R]: the gradient wrt the render's depth map -- fenerf_render_backward_outputs, with or without ray_grads; g_rgb may then
+        be None (a loss that reads the depth only)."""
         dev = self.device
+        if g_depth is not None:
+            return self._render_backward_outputs(B, R, N, save, z_coarse, noise_final, opts, g_rgb, g_depth, film_only, lock_view, tape_format,
+                                                 weights, chunk_points, film_sums_budget_bytes, ray_grads)
         if ray_grads is not None:
             return self._render_backward_rays(B, R, N, save, z_coarse, noise_final, opts, g_rgb, film_only, lock_view, tape_format, weights,
                                               chunk_points, film_sums_budget_bytes, ray_grads)
@@ -947,6 +952,41 @@ class NativeModel:
                                                      _ptr(w0), _ptr(wc0), int(wc0.shape[1]), _ptr(d_o), _ptr(d_d), _stream()))
         res = self._unpad_grads(res)
         res["d_origins"], res["d_dirs"] = d_o, d_d
+        return res, d_grid
+
+    def _render_backward_outputs(self, B, R, N, save, z_coarse, noise_final, opts, g_rgb, g_depth, film_only, lock_view, tape_format, weights,
+                                 chunk_points, film_sums_budget_bytes, ray_grads):
+        dev = self.device
+        w_geo0, w_color0, want_o, want_d = ray_grads if ray_grads is not None else (None, None, False, False)
+        rays = bool(want_o or want_d)
+        if self.spec["grid_ch"] and not film_only and self.grid_grad_mode == _lib.GRID_GRAD_ATOMIC:
+            alert_not_deterministic("NativeModel.render_backward (atomic grid-gradient mode)")
+        res, g, d_grid = self._render_grad_buffers(B, film_only)
+        wts, keep = self._film_weight_struct(weights)
+        w0, wc0 = self._input_grad_weights(w_geo0, w_color0) if rays else (None, None)
+        d_o = torch.empty((B, R, 3), dtype=torch.float32, device=dev) if want_o else None
+        d_d = torch.empty((B, R, 3), dtype=torch.float32, device=dev) if want_d else None
+        gd = _f32(g_depth, dev) if g_depth is not None else None
+        if gd is not None and gd.numel() != B * R:
+            raise ValueError(f"g_depth must hold [{B}, {R}] values")
+        l = _lib.lib()
+        with torch.cuda.device(dev):
+            if rays:
+                nbytes = l.fenerf_render_backward_rays_workspace_bytes(self._h, B, R, N, int(film_only), int(lock_view), int(chunk_points),
+                                                                       int(film_sums_budget_bytes))
+            else:
+                nbytes = l.fenerf_render_backward_workspace_bytes(self._h, B, R, N, int(film_only), int(chunk_points), int(film_sums_budget_bytes))
+            ws = self._workspace("render_bwd", nbytes)
+            _lib.check(l.fenerf_render_backward_outputs(self._h, B, R, N, int(lock_view), C.c_void_p(save.data_ptr()), C.c_size_t(save.numel()),
+                                                        int(tape_format), _ptr(_f32(z_coarse, dev)),
+                                                        _ptr(_f32(noise_final, dev)) if noise_final is not None else None, C.byref(opts),
+                                                        _ptr(_f32(g_rgb, dev)) if g_rgb is not None else None, _ptr(gd), C.byref(g), _ptr(d_grid),
+                                                        C.byref(wts) if wts is not None else None, int(chunk_points), int(film_sums_budget_bytes),
+                                                        C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _ptr(w0), _ptr(wc0),
+                                                        int(wc0.shape[1]) if rays else 0, _ptr(d_o), _ptr(d_d), _stream()))
+        res = self._unpad_grads(res)
+        if ray_grads is not None:
+            res["d_origins"], res["d_dirs"] = d_o, d_d
         return res, d_grid
 
     def render_backward_stage(self, stage, keep_chunks, B, R, N, save, z_coarse, noise_final, opts, g_rgb, lock_view=False, tape_format=0,
@@ -1332,14 +1372,21 @@ def ray_grads(d_points, d_viewdirs, z_coarse, z_fine=None, want_origins=True, wa
     return d_o, d_d
 
 
-def composite_backward(g_rgb, rows_a, z_a, opts, rows_b=None, z_b=None, noise=None, out_a=None, out_b=None):
+def composite_backward(g_rgb, rows_a, z_a, opts, rows_b=None, z_b=None, noise=None, out_a=None, out_b=None, g_depth=None, g_weights=None,
+                       g_wsum=None):
     """Gradient of the final composite wrt its input rows.  Non-merge: rows_a [BR,M,C], z_a [BR,M] -> d_rows_a.
     Merge (rows_b given): fine rows_a / coarse rows_b [BR,N,C], z_a / z_b [BR,N] -> (d_fine, d_coarse).
-    out_a / out_b: contiguous fp32 device buffers of the rows' shapes to write into (views of a larger tensor: no copy afterwards)."""
+    out_a / out_b: contiguous fp32 device buffers of the rows' shapes to write into (views of a larger tensor: no copy afterwards).
+    g_depth [BR] / g_weights [BR,M] (sorted order, like the forward's weights) / g_wsum [BR]: gradients wrt the other outputs of the
+    composite -- with any of them fenerf_composite_backward_outputs, where g_rgb may be None too; with none, fenerf_composite_backward."""
     BR, N, Cc = rows_a.shape
     dev = rows_a.device
     merge = rows_b is not None
-    ra, za, g = _f32(rows_a, dev), _f32(z_a, dev), _f32(g_rgb, dev).reshape(BR, Cc - 1)
+    outputs = g_depth is not None or g_weights is not None or g_wsum is not None
+    if g_rgb is None and not outputs:
+        raise ValueError("composite_backward: no upstream gradient (g_rgb, g_depth, g_weights and g_wsum are all None)")
+    ra, za = _f32(rows_a, dev), _f32(z_a, dev)
+    g = _f32(g_rgb, dev).reshape(BR, Cc - 1) if g_rgb is not None else None
     rb, zb = (_f32(rows_b, dev), _f32(z_b, dev)) if merge else (None, None)
     nz = _f32(noise, dev).reshape(BR, -1) if noise is not None else None
     for o, r in ((out_a, ra), (out_b, rb)):
@@ -1347,6 +1394,14 @@ def composite_backward(g_rgb, rows_a, z_a, opts, rows_b=None, z_b=None, noise=No
     da = out_a if out_a is not None else torch.empty_like(ra)
     db = (out_b if out_b is not None else torch.empty_like(rb)) if merge else None
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().fenerf_composite_backward(BR, N, Cc, int(merge), _ptr(ra), _ptr(rb), _ptr(za), _ptr(zb), _ptr(nz),
-                                                        C.byref(opts), _ptr(g), _ptr(da), _ptr(db), _stream()))
+        if outputs:
+            M = 2 * N if merge else N
+            gd = _f32(g_depth, dev).reshape(BR) if g_depth is not None else None
+            gw = _f32(g_weights, dev).reshape(BR, M) if g_weights is not None else None
+            gs = _f32(g_wsum, dev).reshape(BR) if g_wsum is not None else None
+            _lib.check(_lib.lib().fenerf_composite_backward_outputs(BR, N, Cc, int(merge), _ptr(ra), _ptr(rb), _ptr(za), _ptr(zb), _ptr(nz),
+                                                                    C.byref(opts), _ptr(g), _ptr(gd), _ptr(gw), _ptr(gs), _ptr(da), _ptr(db), _stream()))
+        else:
+            _lib.check(_lib.lib().fenerf_composite_backward(BR, N, Cc, int(merge), _ptr(ra), _ptr(rb), _ptr(za), _ptr(zb), _ptr(nz),
+                                                            C.byref(opts), _ptr(g), _ptr(da), _ptr(db), _stream()))
     return (da, db) if merge else da

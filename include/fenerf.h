@@ -653,14 +653,49 @@ int fenerf_render_backward_rays(const FenerfModel* m, int B, int R, int N, int l
                                 int64_t film_sums_budget_bytes, void* workspace, size_t workspace_bytes, const float* w_geo0,
                                 const float* w_color0, int w_color0_ld, float* d_origins, float* d_dirs, void* stream);
 
+/* replaces: loss.backward() through a render whose loss also reads the DEPTH map generators.py:519 returns beside the pixels (a depth
+ * target, a second view's geometry): fenerf_render_backward_rays' arguments plus g_depth [B][R], the gradient wrt out_depth of
+ * fenerf_render_forward_save.  The final composite backward then runs as fenerf_composite_backward_outputs (dL/dw'_k gains g_depth z_k
+ * over the merged, sorted depths; formulas there); everything behind it is fenerf_render_backward's.  g_rgb and g_depth may each be NULL,
+ * not both.  d_origins / d_dirs may both be NULL here (w_geo0 / w_color0 are then not read and may be NULL): one entry for depth, rays,
+ * and both.  With g_depth NULL and no ray outputs it returns fenerf_render_backward's gradients bit for bit; with ray outputs,
+ * fenerf_render_backward_rays'.  workspace: fenerf_render_backward_workspace_bytes without ray outputs,
+ * fenerf_render_backward_rays_workspace_bytes with them (the depth term needs no buffer of its own).  The two-stage form has no depth
+ * variant. */
+int fenerf_render_backward_outputs(const FenerfModel* m, int B, int R, int N, int lock_view, const void* save, size_t save_bytes, int tape_format,
+                                   const float* z_coarse, const float* noise_final, const FenerfCompositeOpts* opts, const float* g_rgb,
+                                   const float* g_depth, const FenerfSirenGrads* grads, float* d_grid_ncdhw, const FenerfSirenGrads* weights,
+                                   int64_t chunk_points, int64_t film_sums_budget_bytes, void* workspace, size_t workspace_bytes,
+                                   const float* w_geo0, const float* w_color0, int w_color0_ld, float* d_origins, float* d_dirs, void* stream);
+
 /* replaces: what torch autograd derives for the final fancy_integration of a differentiable render
  * (generators.py:519 / :790; G-step and inversion): gradient wrt rgb_final g_rgb [BR, C-1] -> gradients wrt the SIREN
  * outputs.  merge = 0: rows_a [BR,N,C], z_a [BR,N] -> d_rows_a [BR,N,C].  merge = 1: fine rows_a / coarse rows_b with
  * z_a / z_b as in fenerf_merge_composite -> d_rows_a (fine), d_rows_b (coarse), each in its own (unsorted) order.
- * noise is indexed by sorted position like the forward.  fill_mode must be FENERF_FILL_NONE; depth is not differentiated. */
+ * noise is indexed by sorted position like the forward.  fill_mode must be FENERF_FILL_NONE; the colour output alone is differentiated
+ * here (fenerf_composite_backward_outputs below takes gradients of depth / weights / wsum as well). */
 int fenerf_composite_backward(int64_t BR, int N, int C, int merge, const float* rows_a, const float* rows_b,
                               const float* z_a, const float* z_b, const float* noise, const FenerfCompositeOpts* opts,
                               const float* g_rgb, float* d_rows_a, float* d_rows_b, void* stream);
+
+/* replaces: what torch autograd derives for fancy_integration (volumetric_rendering.py:23-50, after the cat / sort / gather of
+ * generators.py:508-519 with merge = 1) when the loss reads ANY of its outputs -- the reference returns three differentiable tensors
+ * (rgb, depth, weights; :50) and a caller may also want the opacity sum(weights) taken BEFORE the last_back adjustment (:40, fenerf_composite's
+ * out_wsum).  fenerf_composite_backward's arguments plus three more upstream gradients; each of the four may be NULL (= zeros, at no cost):
+ *   g_rgb [BR][C-1], g_depth [BR], g_weights [BR][M] (M = N, merge: 2N; by SORTED position, like out_weights), g_wsum [BR]
+ * With w'_k the weights after the last_back adjustment (the ones rgb, depth and out_weights use) and z_k the sorted depths:
+ *   dL/dw'_k = sum_c g_rgb_c row_kc + g_depth z_k + g_weights_k
+ *   last_back (w'_last = w_last + 1 - sum_j w_j, :41-42):   dL/dw_k = dL/dw'_k - dL/dw'_last   (dL/dw'_last from the full sum above)
+ *   then, on the pre-adjustment weights:  dL/dw_k += g_wsum  (-= / += sum_c g_rgb_c for white_back / black_back, :44-48)
+ * and from there exactly fenerf_composite_backward: dL/da_k = T_k dL/dw_k - S_k / u_k, dL/dsigma_k = dL/da_k delta_k (1 - a_k) act'(.).
+ * The colour channels of a row receive w'_k g_rgb_c (zeros with g_rgb NULL): depth, weights and wsum reach a row only through its
+ * density.  z, the noise and the sort order are constants of the graph.  A relu-clamped sample receives a selected zero, NaN propagates,
+ * and M = 1 gives alpha = 0 and all-zero gradients, as in fenerf_composite_backward.  With only g_rgb given the result equals
+ * fenerf_composite_backward's bit for bit.  All four NULL: FENERF_E_INVALID.  fill_mode must be FENERF_FILL_NONE. */
+int fenerf_composite_backward_outputs(int64_t BR, int N, int C, int merge, const float* rows_a, const float* rows_b,
+                                      const float* z_a, const float* z_b, const float* noise, const FenerfCompositeOpts* opts,
+                                      const float* g_rgb, const float* g_depth, const float* g_weights, const float* g_wsum,
+                                      float* d_rows_a, float* d_rows_b, void* stream);
 
 /* Bytes of [dev] scratch fenerf_sparse_select needs for B images of P = R * N samples per pass. */
 size_t fenerf_sparse_select_workspace_bytes(int B, int64_t P);

@@ -4,7 +4,7 @@ launches per SIREN call recorded and replayed by autograd), in fp32 and under to
 reference's training loop (train_double_latent_semantic.py:279).  Measurement tool only -- imports the test oracle for
 the eager restatement.
 
-    python tools/bench_gstep.py [--B 4] [--size 64] [--steps 24] [--iters 5] [--pose] [--single-pass]
+    python tools/bench_gstep.py [--B 4] [--size 64] [--steps 24] [--iters 5] [--pose] [--single-pass] [--depth]
 """
 import argparse
 import functools
@@ -49,6 +49,7 @@ def main():
     ap.add_argument("--grad-precision", choices=["f32", "tape16", "amp", "amp16"], default="f32", help="weight-gradient operands (siren.grad_precision)")
     ap.add_argument("--pose", action="store_true", help="h_mean / v_mean as tensors that require grad: the step also delivers the camera-pose gradient")
     ap.add_argument("--single-pass", action="store_true", help="hierarchical_sample=False (the inversion renders: N samples per ray, no resampling)")
+    ap.add_argument("--depth", action="store_true", help="return_depth=True and a depth term in the loss: the step also differentiates the depth map")
     a = ap.parse_args()
     B, S_, N, H = a.B, a.size, a.steps, a.H
     spec = proc.model_spec("texture", hidden_dim=H, grid_size=a.grid, z_dim=8)
@@ -74,7 +75,8 @@ def main():
     params = [p for n, p in mod.named_parameters() if "mapping_network" not in n]
     passes = 1 if a.single_pass else 2
     res = {"config": {"B": B, "img_size": S_, "num_steps": f"{N}+{N}" if passes == 2 else f"{N}", "H": H, "grid": a.grid, "points": B * S_ * S_ * passes * N,
-                      "pose": bool(a.pose)}}
+                      "pose": bool(a.pose), "depth": bool(a.depth)}}
+    w_d = torch.randn((B, S_, S_), device=DEV)
 
     def native_step(repack):
         for p in params:
@@ -84,6 +86,11 @@ def main():
         if repack:
             with torch.no_grad():
                 params[0].add_(0)        # bumps the version counter like optimizer.step(): weights are re-packed
+        if a.depth:
+            px, _, depth = gen.forward_with_frequencies(film_t["freq_geo"], film_t["freq_app"], film_t["phase_geo"], film_t["phase_app"],
+                                                        return_depth=True, **kw)
+            ((px * w).sum() + (depth * w_d).sum()).backward()
+            return
         px, _ = gen.forward_with_frequencies(film_t["freq_geo"], film_t["freq_app"], film_t["phase_geo"], film_t["phase_app"], **kw)
         (px * w).sum().backward()
 
@@ -104,8 +111,8 @@ def main():
         p.requires_grad_(True)
 
     if not a.skip_eager:
-        if a.pose or a.single_pass:
-            raise SystemExit("--pose / --single-pass time the native step only: add --skip-eager")
+        if a.pose or a.single_pass or a.depth:
+            raise SystemExit("--pose / --single-pass / --depth time the native step only: add --skip-eager")
         sdt = {k: torch.tensor(v, device=DEV).requires_grad_(True) for k, v in sd.items()}
         film_e = {k: torch.tensor(v, device=DEV).requires_grad_(True) for k, v in film.items()}
         R = S_ * S_

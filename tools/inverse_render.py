@@ -81,6 +81,10 @@ def build_parser():
                         help="optimise the camera's yaw / pitch with the FiLM offsets (the reference assumes a frontal, externally estimated pose); "
                              "the recovered pose is saved with the checkpoint and centres the preview / recon renders")
     parser.add_argument('--lr_pose', type=float, default=None, help='learning rate of the yaw / pitch parameter group (default: the offsets\' 1e-2)')
+    parser.add_argument('--depth_path', type=str, default=None,
+                        help='FILE.npy: a depth map [image_size, image_size] (camera distance along the ray, the units of ray_start / ray_end) for '
+                             'a depth term on the render\'s differentiable depth; non-finite or non-positive entries are masked out')
+    parser.add_argument('--lambda_depth', type=float, default=0., help='weight of mean(mask * |depth - target|); needs --depth_path')
     return parser
 
 
@@ -117,11 +121,17 @@ def run_inverse_render(opt, generator, img_path, seg_path, percept=None):
             gen_masks = callers.mask2labels(torch.argmax(img[:, :-3], dim=1).float()[0].cpu().numpy(), 19)
             mious.append(callers.mIOU(torch.Tensor(gen_masks[None]), gt_seg_19).item())
 
+    gt_depth = depth_mask = None
+    if opt.depth_path and opt.lambda_depth:
+        target = torch.from_numpy(np.load(opt.depth_path).astype(np.float32)).reshape(1, opt.image_size, opt.image_size)
+        depth_mask = (torch.isfinite(target) & (target > 0)).float()
+        gt_depth = torch.where(depth_mask > 0, target, torch.zeros_like(target))
     z_dim = callers._latent_dims(generator)[0]
     res = callers.inverse_render(generator, gt_image, gt_seg_18, options, n_iterations=opt.iteration, init_psi=opt.init_psi,
                                  lambda_seg=opt.lambda_seg, lambda_img=opt.lambda_img, lambda_percept=opt.lambda_percept,
                                  lambda_norm=opt.lambda_norm if opt.latent_normalize else 0.0, percept=percept, z_dim=z_dim, on_step=on_step,
-                                 optimize_pose=opt.optimize_pose, lr_pose=opt.lr_pose)
+                                 optimize_pose=opt.optimize_pose, lr_pose=opt.lr_pose, gt_depth=gt_depth, depth_mask=depth_mask,
+                                 lambda_depth=opt.lambda_depth if gt_depth is not None else 0.0)
     meta = {k: res[k] for k in ('w_geo_frequencies', 'w_geo_phase_shifts', 'w_geo_frequency_offsets', 'w_geo_phase_shift_offsets',
                                 'w_app_frequencies', 'w_app_phase_shifts', 'w_app_frequency_offsets', 'w_app_phase_shift_offsets')}
     if opt.optimize_pose:
@@ -131,7 +141,9 @@ def run_inverse_render(opt, generator, img_path, seg_path, percept=None):
     np.save(os.path.join(opt.save_dir, 'mious.npy'), mious)
     print(f"{os.path.basename(img_path)}: loss {res['losses'][0]:.5f} -> {res['losses'][-1]:.5f} in {opt.iteration} iterations"
           + (f", frontal mIoU {mious[0]:.3f} -> {mious[-1]:.3f}" if mious else "")
-          + (f", yaw {res['yaw']:.4f} pitch {res['pitch']:.4f}" if opt.optimize_pose else "") + f" -> {checkpoint_path}")
+          + (f", yaw {res['yaw']:.4f} pitch {res['pitch']:.4f}" if opt.optimize_pose else "")
+          + (f", depth term {res['depth_losses'][0]:.5f} -> {res['depth_losses'][-1]:.5f}" if res.get('depth_losses') else "")
+          + f" -> {checkpoint_path}")
     return checkpoint_path
 
 
