@@ -66,6 +66,11 @@ def padded_hidden_dim(H):
     raise ValueError(f"hidden_dim {H}: the kernels are instantiated up to {SUPPORTED_HIDDEN[-1]} (include/fenerf.h)")
 
 
+# Bytes of FiLM scratch NativeModel.siren_forward_pointwise aims at: its pre-pass writes 2 L H floats per point (18 KB at H = 256), so the
+# points are walked in slabs of POINTWISE_FILM_SCRATCH_BYTES // (8 L H) points (whole 32-point tiles, at least one) per image.
+POINTWISE_FILM_SCRATCH_BYTES = 1 << 28
+
+
 def _pad_axes(name, n_label_layers):
     """which axes of render parameter `name` are hidden-width axes: (pad rows?, pad the LAST H columns?) -- the colour layer 0's input is
     [dirs | grid features | x]: its hidden part is the trailing H columns; the LAST label layer, final_layer and color_layer_linear map
@@ -487,16 +492,13 @@ class NativeModel:
         B, P = points.shape[0], points.shape[1]
         H, ng, nc = self.spec["hidden_dim"], self.spec["n_geo"], self.spec["n_color"]
         dev = self.device
-        fg, pg, fa, pa = (_f32(t, dev) for t in (fg, pg, fa, pa))
-        for t, n in ((fg, ng), (pg, ng), (fa, nc), (pa, nc)):
-            if tuple(t.shape) != (B, P, n * H):
-                raise ValueError(f"per-point film parameter of shape {tuple(t.shape)}, expected {(B, P, n * H)}")
+        fg, pg, fa, pa = self._film_pointwise(B, P, fg, pg, fa, pa)
         points = _f32(points, dev)
         ray_dirs = _f32(ray_dirs, dev) if ray_dirs is not None else None
         out = torch.empty((B, P, self.C), dtype=torch.float32, device=dev)
         # the FiLM pre-pass writes 2 L H floats per point (18 KB at H = 256): walk the points in slabs so that the scratch stays
         # below ~300 MB whatever P is
-        slab = max(32, (1 << 28) // (8 * (ng + nc) * H) // 32 * 32)
+        slab = max(32, POINTWISE_FILM_SCRATCH_BYTES // (8 * (ng + nc) * H) // 32 * 32)
         with torch.cuda.device(dev):
             for b in range(B):
                 for s in range(0, P, slab):
@@ -511,11 +513,11 @@ class NativeModel:
     def _film_pointwise(self, B, P, fg, pg, fa, pa):
         H, ng, nc = self.spec["hidden_dim"], self.spec["n_geo"], self.spec["n_color"]
         fg, pg, fa, pa = (_f32(t, self.device) for t in (fg, pg, fa, pa))
+        for t, n in ((fg, ng), (pg, ng), (fa, nc), (pa, nc)):       # at the module's own width, or already at the kernels'
+            if tuple(t.shape) not in ((B, P, n * self.logical_H), (B, P, n * H)):
+                raise ValueError(f"per-point film parameter of shape {tuple(t.shape)}, expected {(B, P, n * self.logical_H)}")
         if self.padded:
             fg, pg, fa, pa = self._pad_film(fg, ng), self._pad_film(pg, ng), self._pad_film(fa, nc), self._pad_film(pa, nc)
-        for t, n in ((fg, ng), (pg, ng), (fa, nc), (pa, nc)):
-            if tuple(t.shape) != (B, P, n * H):
-                raise ValueError(f"per-point film parameter of shape {tuple(t.shape)}, expected {(B, P, n * H)}")
         return fg, pg, fa, pa
 
     def siren_forward_save_pointwise(self, points, ray_dirs, fg, pg, fa, pa):
@@ -1072,7 +1074,10 @@ class NativeLocalModel:
     evaluates both in one launch (fenerf_siren_forward_local).  sd / spec as NativeModel, mp = the mapping network's six tensors."""
 
     def __init__(self, sd, spec, mp, device):
+        self.logical_H = int(spec["hidden_dim"])                       # the module's width; self.spec carries the (padded) width the kernel runs at
+        spec = dict(spec, hidden_dim=padded_hidden_dim(self.logical_H))
         self.spec = dict(spec)
+        sd, mp = self._pad_state(sd, mp)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("fenerf_amd renders on the GPU only (there is no CPU path); got device %s" % device)
@@ -1081,6 +1086,24 @@ class NativeLocalModel:
             d, keep = _lib.make_desc(sd, spec, "f32")
             md, keep2 = _lib.make_local_map_desc(mp)
             _lib.check(_lib.lib().fenerf_local_model_create(C.byref(d), C.byref(md), C.byref(self._h)))
+
+    def _pad_state(self, sd, mp):
+        """a hidden width between the instantiated ones (padded_hidden_dim): the SIREN's parameters like NativeModel._pad_state, and the
+        mapping network's last layer, whose output rows are [2][L][H] (frequencies | phase shifts, one H-block per FiLM layer), to
+        [2][L][Hp] with zero rows and zero biases.  A padded feature is still exactly 0: its raw frequency is 0, so its frequency is
+        15 * 0 + 30 = 30; its layer row and bias are 0, so its pre-activation is 0; its phase is (30 * 0 + 0 + 0) / 2 pi = 0 -- the
+        activation is sin(30 * 0 + 0) = sin(0), and the zero columns behind it add exact zeros to every sum it enters."""
+        H, Hp, nl = self.logical_H, self.spec["hidden_dim"], self.spec.get("n_label_layers", 0)
+        if H == Hp:
+            return sd, mp
+        L = self.spec["n_geo"] + self.spec["n_color"]
+        w2, b2 = np.asarray(mp["4.weight"], np.float32), np.asarray(mp["4.bias"], np.float32)
+        if w2.shape[0] != 2 * L * H or b2.shape != (2 * L * H,):
+            raise ValueError(f"mapping network output of {w2.shape[0]} rows, expected 2 x {L} x {H} (frequencies | phase shifts at hidden_dim {H})")
+        mp = dict(mp)
+        mp["4.weight"] = np.pad(w2.reshape(2, L, H, -1), ((0, 0), (0, 0), (0, Hp - H), (0, 0))).reshape(2 * L * Hp, -1)
+        mp["4.bias"] = np.pad(b2.reshape(2, L, H), ((0, 0), (0, 0), (0, Hp - H))).reshape(-1)
+        return {k: _pad_param(k, np.asarray(v), H, Hp, nl, True) for k, v in sd.items()}, mp
 
     def forward(self, points, ray_dirs, latents):
         """points [B,P,3] local coordinates, ray_dirs [B,P,3] or None, latents [B,P,32] -> [B,P,4] = [rgb | sigma]"""

@@ -39,7 +39,10 @@
  *   - fenerf_mapping_forward / _backward, fenerf_label_head_backward: the mask of the PyTorch ops / fp64 autograd, element for element.
  *   - the sparse backward of the Python package: a non-finite upstream gradient may keep more rows than its buffer bound; that is not an
  *     overflow error -- every gradient of that step then carries a NaN.
- *   Not covered by tests yet: per-point-modulated and one-launch local kernels, input gradients, the FiLM-only inversion route.
+ *   - fenerf_siren_forward_local / fenerf_siren_forward_pointwise / fenerf_siren_*_pointwise: per-point FiLM blocks confine a non-finite
+ *     frequency, phase shift or local latent to ITS POINT's row (not the image); a NaN weight of the per-point mapping network reaches
+ *     every point.  fenerf_siren_input_grads and fenerf_siren_backward_film / _film_grads: autograd's mask, the point's row for d points /
+ *     d view directions, the image for the FiLM gradients.
  */
 #ifndef FENERF_H_
 #define FENERF_H_
@@ -62,7 +65,9 @@ enum {
                               * reference constructs any, siren/siren.py:1451) runs EXACTLY at the next instantiated one with zero padding:
                               * zero rows / trailing hidden columns of every weight matrix, zero biases and zero FiLM phase shifts make a
                               * padded feature sin(f' 0 + 0) = 0; the host packs that way (fenerf_amd/native.py padded_hidden_dim pads on
-                              * the way in and slices gradients on the way out: pixels bit-identical to the padded network's) */
+                              * the way in and slices gradients on the way out: pixels bit-identical to the padded network's).  The
+                              * per-point-modulated routes too: per-point FiLM blocks are padded per layer, and the one-launch local model
+                              * pads the mapping network's last layer ([2][L][H] output rows) with zero rows and zero biases */
   FENERF_E_CLAMP_MODE = -5   /* reference raises TypeError("Need to choose clamp mode"), volumetric_rendering.py:34 */
 };
 

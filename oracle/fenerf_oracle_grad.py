@@ -88,3 +88,17 @@ def siren_forward(sd, spec, points, ray_dirs, freq_geo, phase_geo, freq_app, pha
                   phase_app[:, i * H:(i + 1) * H], taps)
     rgb = torch.sigmoid(c @ sd["color_layer_linear.0.weight"].T + sd["color_layer_linear.0.bias"])
     return torch.cat([labels, rgb, sigma], -1)
+
+
+def siren_forward_pointwise(prm, H, points, ray_dirs, freq, phase):
+    """Differentiable restatement of siren.py:464-477 (SPATIALSIRENGRID.forward_with_frequencies_phase_shifts): one FiLM block PER POINT.
+    prm: reference-named torch tensors of the 'spatial' SIREN; points (local coordinates) / ray_dirs [B,P,3]; raw freq / phase
+    [B,P,(n_geo+1)*H] -> [B,P,4] = [rgb | sigma]."""
+    n_geo = sum(1 for k in prm if k.startswith("network.") and k.endswith(".layer.weight"))
+    x = points * BOX_SCALE
+    fr = freq * 15 + 30
+    for i in range(n_geo):
+        x = torch.sin(fr[..., i * H:(i + 1) * H] * F.linear(x, prm[f"network.{i}.layer.weight"], prm[f"network.{i}.layer.bias"]) + phase[..., i * H:(i + 1) * H])
+    sigma = F.linear(x, prm["final_layer.weight"], prm["final_layer.bias"])
+    c = torch.sin(fr[..., -H:] * F.linear(torch.cat([ray_dirs, x], -1), prm["color_layer_sine.layer.weight"], prm["color_layer_sine.layer.bias"]) + phase[..., -H:])
+    return torch.cat([torch.sigmoid(F.linear(c, prm["color_layer_linear.0.weight"], prm["color_layer_linear.0.bias"])), sigma], -1)

@@ -899,3 +899,269 @@ def test_label_head_backward_nonfinite(n_layers, H, n_lab, inj):
             a = N_(a)
             assert (~np.isfinite(a)).any() == (~np.isfinite(r)).any(), (tag, name, "has a non-finite element", int((~np.isfinite(a)).sum()), int((~np.isfinite(r)).sum()))
             check(tag, name, a, r, np.ones(r.shape, bool), _rel_bound(2e-6, r), inj.endswith("nan"))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The per-point-modulated family (SPATIALSIRENGRID): the one-launch local kernel (fenerf_siren_forward_local), the explicit per-point
+# forward (fenerf_siren_forward_pointwise) and the per-point backward (PointwiseSirenFunction over fenerf_siren_forward_save_pointwise /
+# _backward_pointwise / _param_grads_pointwise).  B = 2, P = 33 (a full tile and a 1-point tile), an instantiated width and a padded one;
+# one value per case at point 5 and at point P - 3 of image 1.  Module, inputs and forward bounds of tests/test_gpu_pointwise.py
+# (test_pointwise_and_local_forward_vs_fp64_at_every_width: rgb absolute, sigma relative to max(1, max|sigma|), per route and width).
+# ---------------------------------------------------------------------------------------------------------------------------------------
+PW_B, PW_P = 2, 33
+PW_POINTS = (5, PW_P - 3)
+
+
+def _pointwise_case(H):
+    import test_gpu_pointwise as PW
+    mod = PW._module(H)
+    pts, dirs, lat = PW._inputs(PW_B, PW_P, seed=H)
+    with torch.no_grad():
+        sampled = mod.sample_local_latents(lat, mod.gridwarper(pts))
+        f, p = mod.mapping_network(sampled)
+        local = mod.get_local_coordinates(pts, 32, preserve_y=False)
+    mp = {n: N_(q) for n, q in mod.mapping_network.network.named_parameters()}
+    a = dict(local=N_(local), dirs=N_(dirs), sampled=N_(sampled), f=N_(f), p=N_(p))
+    return mod, mod._state_numpy(), mod._spec(), mp, a, PW._bound(native.padded_hidden_dim(H))
+
+
+def _pointwise_bounds(ref, b_rgb, b_sig):
+    b = np.full(ref.shape, b_rgb)
+    fin = np.isfinite(ref[..., 3])
+    b[..., 3] = b_sig * max(1.0, float(np.abs(ref[..., 3][fin]).max(initial=0.0)))
+    return b
+
+
+def _print_clean(case, clean, ref):
+    e = np.abs(clean - ref)
+    print(f"[nonfinite] {case}: the call without an injection, max|err| vs fp64 rgb {e[..., :3].max():.2e} sigma rel "
+          f"{e[..., 3].max() / max(1.0, float(np.abs(ref[..., 3]).max())):.2e}")
+
+
+def _rows(channels=slice(None)):
+    D = np.zeros((PW_B, PW_P, 4), bool)
+    for pt in PW_POINTS:
+        D[1, pt, channels] = True
+    return D
+
+
+@pytest.mark.parametrize("H", [32, 72])
+def test_local_kernel_nonfinite(H):
+    """fenerf_siren_forward_local: a non-finite coordinate, direction or latent touches its point's row only (a direction: its rgb only);
+    a NaN weight of the mapping network's last layer or of the trunk touches everything.  Reference mask: the fp64 mapping network + SIREN."""
+    mod, sd, spec, mp, a, (bound, _) = _pointwise_case(H)
+    msd = lambda m: {"m.network." + k: v.astype(np.float64) for k, v in m.items()}
+
+    def oracle(sd_, mp_, x):
+        with quiet():
+            f64, p64 = O.mapping_network(msd(mp_), "m", x["sampled"].astype(np.float64))
+            return O.siren_forward(sd_, spec, x["local"], x["dirs"], f64, p64, dtype=np.float64)
+    fwd = lambda nat, x: N_(nat.forward(T(x["local"]), T(x["dirs"]), T(x["sampled"])))
+    nat = mod.native_local(DEV)
+    clean = fwd(nat, a)
+    ref0 = oracle(sd, mp, a)
+    _print_clean(f"local_kernel[H{H}]", clean, ref0)
+    assert np.isfinite(clean).all() and (np.abs(clean - ref0) <= _pointwise_bounds(ref0, *bound)).all()
+    for inj in ("coord-nan", "coord-pinf", "dir-nan", "latent-nan", "mapping-weight-nan", "trunk-weight-nan"):
+        v = VALUES[inj.rsplit("-", 1)[1]]
+        x, sd2, mp2 = {k: t.copy() for k, t in a.items()}, {k: t.copy() for k, t in sd.items()}, {k: t.copy() for k, t in mp.items()}
+        D = _rows(slice(0, 3)) if inj == "dir-nan" else _rows()
+        for pt in PW_POINTS:
+            if inj.startswith("coord"):
+                x["local"][1, pt, 1] = v
+            elif inj == "dir-nan":
+                x["dirs"][1, pt, 0] = v
+            elif inj == "latent-nan":
+                x["sampled"][1, pt, 9] = v
+        if inj == "mapping-weight-nan":
+            mp2["4.weight"][2 * H + 3, 6] = v; D[:] = True          # the frequency of feature 3 of FiLM layer 2, of every point
+        elif inj == "trunk-weight-nan":
+            sd2["network.3.layer.weight"][2, 5] = v; D[:] = True
+        tag = f"local_kernel[H{H}]|{inj}"
+        if inj.endswith("weight-nan"):
+            nat2 = native.NativeLocalModel(sd2, spec, mp2, DEV)          # the host packer
+            got = fwd(nat2, a)
+            nat2.close()
+        else:
+            got = fwd(nat, x)
+        ref = oracle(sd2, mp2, x)
+        check(tag, "out", got, ref, D, _pointwise_bounds(ref, *bound), inj.endswith("nan"), clean)
+
+
+@pytest.mark.parametrize("H", [32, 72])
+def test_pointwise_forward_nonfinite(H):
+    """fenerf_siren_forward_pointwise: what distinguishes it from the per-image kernel -- a non-finite frequency or phase shift in ONE
+    POINT's FiLM block touches that point's row, not the image."""
+    mod, sd, spec, mp, a, (_, bound) = _pointwise_case(H)
+    nat = mod.native(DEV)
+    split = lambda t: (t[..., :8 * H], t[..., 8 * H:])
+    def fwd(x):
+        (fg, fa), (pg, pa) = split(T(x["f"])), split(T(x["p"]))
+        return N_(nat.siren_forward_pointwise(T(x["local"]), T(x["dirs"]), fg, pg, fa, pa))
+    def oracle(x):
+        with quiet():
+            return O.siren_forward(sd, spec, x["local"], x["dirs"], x["f"], x["p"], dtype=np.float64)
+    clean = fwd(a)
+    ref0 = oracle(a)
+    _print_clean(f"pointwise_forward[H{H}]", clean, ref0)
+    assert np.isfinite(clean).all() and (np.abs(clean - ref0) <= _pointwise_bounds(ref0, *bound)).all()
+    for inj in ("coord-nan", "coord-pinf", "dir-nan", "freq-nan", "freq-pinf", "phase-nan"):
+        v = VALUES[inj.rsplit("-", 1)[1]]
+        x = {k: t.copy() for k, t in a.items()}
+        D = _rows(slice(0, 3)) if inj == "dir-nan" else _rows()
+        for pt in PW_POINTS:
+            if inj.startswith("coord"):
+                x["local"][1, pt, 1] = v
+            elif inj == "dir-nan":
+                x["dirs"][1, pt, 0] = v
+            elif inj.startswith("freq"):
+                x["f"][1, pt, 2 * H + 3] = v
+            else:
+                x["p"][1, pt, 5 * H + 1] = v
+        ref = oracle(x)
+        check(f"pointwise_forward[H{H}]|{inj}", "out", fwd(x), ref, D, _pointwise_bounds(ref, *bound), inj.endswith("nan"), clean)
+
+
+@pytest.mark.parametrize("H", [32, 72])
+@pytest.mark.parametrize("inj", ["upstream-nan", "upstream-pinf", "phase-nan"])
+def test_pointwise_backward_nonfinite(inj, H):
+    """PointwiseSirenFunction vs the fp64 restatement (OG.siren_forward_pointwise) cast to fp32.  Inputs of
+    test_gpu_parity.py::test_pointwise_siren_backward_native_vs_fp64_autograd and its bound: 8.5e-5 of the tensor's largest |gradient|.
+    d_freq / d_phase [B, P, 9H]: D = the injected points' rows; the weight gradients sum over every point: D = everything."""
+    B, P = PW_B, PW_P
+    torch.manual_seed(H + P)
+    mod = S.SPATIALSIRENGRID(input_dim=3, z_dim=16, hidden_dim=H, output_dim=4).to(DEV).train()
+    mod.device = torch.device(DEV)
+    with torch.no_grad():
+        mod.final_layer.weight.mul_(20.0)
+    rng = np.random.default_rng(7)
+    pts = rng.uniform(-1, 1, (B, P, 3)).astype(np.float32)
+    dirs = rng.normal(size=(B, P, 3)).astype(np.float32)
+    dirs /= np.linalg.norm(dirs, axis=-1, keepdims=True)
+    f0 = rng.normal(0, 0.4, (B, P, 9 * H)).astype(np.float32)
+    p0 = rng.normal(0, 0.4, (B, P, 9 * H)).astype(np.float32)
+    w = rng.normal(size=(B, P, 4)).astype(np.float32)
+    w[..., -1] *= 0.05
+    for pt in PW_POINTS:
+        if inj == "upstream-nan":
+            w[1, pt, 0] = np.nan
+        elif inj == "upstream-pinf":
+            w[1, pt, 3] = np.inf
+        else:
+            p0[1, pt, 5 * H + 1] = np.nan
+    f, p = T(f0).requires_grad_(True), T(p0).requires_grad_(True)
+    out = mod.forward_with_frequencies_phase_shifts(T(pts), f, p, T(dirs))
+    assert "PointwiseSirenFunction" in str(out.grad_fn) or "Slice" in str(out.grad_fn), out.grad_fn
+    (out * T(w)).sum().backward()
+    t64 = lambda t: torch.tensor(np.asarray(t), dtype=torch.float64)
+    prm = {n: q.detach().double().cpu().requires_grad_(True) for n, q in mod.named_parameters() if mod._is_render_param(n)}
+    f64, p64 = t64(f0).requires_grad_(True), t64(p0).requires_grad_(True)
+    ref = OG.siren_forward_pointwise(prm, H, t64(pts), t64(dirs), f64, p64)
+    (ref * t64(w)).sum().backward()
+    tag = f"pointwise_backward[{inj}-H{H}]"
+    nan = inj != "upstream-pinf"
+    rows = np.zeros((B, P, 1), bool)
+    for pt in PW_POINTS:
+        rows[1, pt] = True
+    for name, got, r64 in (("d_freq", f.grad, f64), ("d_phase", p.grad, p64)):
+        r = _f32_grad(r64)
+        check(tag, name, N_(got), r, rows, _rel_bound(8.5e-5, r), nan)
+    named = dict(mod.named_parameters())
+    for k, v in prm.items():
+        r, got = _f32_grad(v), N_(named[k].grad)
+        assert (~np.isfinite(got)).any() == (~np.isfinite(r)).any(), (tag, k, "has a non-finite element", int((~np.isfinite(got)).sum()), int((~np.isfinite(r)).sum()))
+        check(tag, "d_" + k, got, r, np.ones(r.shape, bool), _rel_bound(8.5e-5, r), nan)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Gradients wrt the SIREN's inputs (fenerf_siren_input_grads behind the autograd node) and the FiLM-only inversion route
+# (fenerf_siren_backward_film / _film_grads: frozen weights) vs fp64 autograd (OG).  D = the injected point's row for d_points / d_dirs
+# (a NaN FiLM phase of image 1: the image's rows), image 1 for the FiLM gradients.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _inject_backward(inj, g_out, film, H, Cc, points):
+    for pt in points:
+        if inj == "upstream-nan":
+            g_out[1, pt, 0] = np.nan
+        elif inj == "upstream-pinf":
+            g_out[1, pt, Cc - 1] = np.inf
+    if inj == "phase-nan":
+        film["phase_geo"][1, 5 * H + 1] = np.nan
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3", "tape16"])
+@pytest.mark.parametrize("kind,H,grid,P", [("texture", 32, 5, 75), ("spatial", 32, 0, 33), ("texture", 100, 5, 75)])
+@pytest.mark.parametrize("inj", ["upstream-nan", "upstream-pinf", "phase-nan"])
+def test_siren_input_gradients_nonfinite(inj, kind, H, grid, P, precision):
+    """Shapes of test_gpu_parity.py::test_siren_input_gradients_vs_fp64_autograd and its bound (INPUT_GRAD_BOUND there: 2.1e-5 f32, 4.2e-5 f16x3,
+    1.9e-4 tape16, of the tensor's largest |gradient|)."""
+    B = 2
+    mod, spec, sd = _siren_module(kind, H, grid, precision)
+    _, _, _, _, film = _siren_inputs(kind, H, grid, P)
+    Cc = spec["output_dim"]
+    rng = np.random.default_rng(11)          # points, directions and upstream gradient as that test draws them: its measured bound is for these
+    pts = rng.uniform(-0.125, 0.125, (B, P, 3)).astype(np.float32)
+    dirs = rng.normal(size=(B, P, 3)).astype(np.float32)
+    dirs /= np.linalg.norm(dirs, axis=-1, keepdims=True)
+    g_out = rng.normal(size=(B, P, Cc)).astype(np.float32)
+    g_out[..., -1] *= 0.02
+    _inject_backward(inj, g_out, film, H, Cc, (5, P - 3))
+    film_t = {k: T(v).requires_grad_(True) for k, v in film.items()}
+    p_t, d_t = T(pts).requires_grad_(True), T(dirs).requires_grad_(True)
+    if kind == "spatial":
+        out = mod.forward_with_frequencies_phase_shifts(p_t, torch.cat([film_t["freq_geo"], film_t["freq_app"]], -1),
+                                                        torch.cat([film_t["phase_geo"], film_t["phase_app"]], -1), d_t)
+    else:
+        out = mod.forward_with_frequencies_phase_shifts(p_t, film_t["freq_geo"], film_t["freq_app"], film_t["phase_geo"], film_t["phase_app"], d_t)
+    (out * T(g_out)).sum().backward()
+    t64 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
+    sd64 = {k: t64(v) for k, v in sd.items()}
+    film64 = {k: t64(v).requires_grad_(True) for k, v in film.items()}
+    p64, d64 = t64(pts).requires_grad_(True), t64(dirs).requires_grad_(True)
+    ref = OG.siren_forward(sd64, spec, p64, d64, film64["freq_geo"], film64["phase_geo"], film64["freq_app"], film64["phase_app"])
+    (ref * t64(g_out)).sum().backward()
+    tag = f"siren_input_grads[{inj}-{kind}-H{H}-{precision}]"
+    nan = inj != "upstream-pinf"
+    D = np.zeros((B, P, 1), bool)
+    if inj == "phase-nan":
+        D[1] = True
+    else:
+        D[1, 5] = D[1, P - 3] = True
+    rel = {"f32": 2.1e-5, "f16x3": 4.2e-5, "tape16": 1.9e-4}[precision]
+    for name, got, r64 in (("d_points", p_t.grad, p64), ("d_dirs", d_t.grad, d64)):
+        r = _f32_grad(r64)
+        check(tag, name, N_(got), r, D, _rel_bound(rel, r), nan)
+    for k in film:          # the FiLM gradients of the same backward: D = image 1 (test_siren_backward_vs_autograd's 2e-4)
+        r = _f32_grad(film64[k])
+        Df = np.zeros(r.shape, bool); Df[1] = True
+        check(tag, "d_" + k, N_(film_t[k].grad), r, Df, _rel_bound(2e-4, r), nan)
+
+
+@pytest.mark.parametrize("inj", ["upstream-nan", "upstream-pinf", "phase-nan"])
+def test_inversion_film_only_nonfinite(inj):
+    """Model and shape of test_gpu_parity.py::test_inversion_film_only_gradients_and_loop (texture, H = 32, 5^3 grid, sigma gain 150, B = 2,
+    P = 128, weights frozen).  Bound: that test holds the FiLM-only gradients to the full backward's (1e-5 phase, 2e-4 frequency, relative) and
+    test_siren_backward_vs_autograd holds the full backward's to fp64 autograd (2e-4): their sums."""
+    B, P, H = 2, 128, 32
+    mod, spec, sd = _siren_module("texture", H, 5, "f16x3", sigma_gain=150.0)
+    assert mod.native_differentiable(DEV).film_only_native()
+    for q in mod.parameters():
+        q.requires_grad_(False)
+    rng = np.random.default_rng(9)
+    pts, dirs = rng.uniform(-0.12, 0.12, (B, P, 3)).astype(np.float32), rng.normal(size=(B, P, 3)).astype(np.float32)
+    g_out = rng.normal(size=(B, P, 22)).astype(np.float32)
+    film = proc.film_params(spec, B, seed=4)
+    _inject_backward(inj, g_out, film, H, 22, (5, P - 3))
+    film_t = {k: T(v).requires_grad_(True) for k, v in film.items()}
+    out = mod.forward_with_frequencies_phase_shifts(T(pts), film_t["freq_geo"], film_t["freq_app"], film_t["phase_geo"], film_t["phase_app"], T(dirs))
+    (out * T(g_out)).sum().backward()
+    assert all(q.grad is None for q in mod.parameters())
+    t64 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)
+    sd64 = {k: t64(v) for k, v in sd.items()}
+    film64 = {k: t64(v).requires_grad_(True) for k, v in film.items()}
+    ref = OG.siren_forward(sd64, spec, t64(pts), t64(dirs), film64["freq_geo"], film64["phase_geo"], film64["freq_app"], film64["phase_app"])
+    (ref * t64(g_out)).sum().backward()
+    tag = f"film_only[{inj}]"
+    for k in film:
+        r = _f32_grad(film64[k])
+        D = np.zeros(r.shape, bool); D[1] = True
+        check(tag, "d_" + k, N_(film_t[k].grad), r, D, _rel_bound(2e-4 + (1e-5 if "phase" in k else 2e-4), r), inj != "upstream-pinf")

@@ -3636,12 +3636,13 @@ def test_spatial_siren_grid_gradients_vs_reference_autograd(native_route):
     assert e_fwd <= 2e-5 and errs[worst] <= (4.4e-4 if native_route else 3e-4), errs
 
 
-@pytest.mark.parametrize("H,B,P", [(32, 2, 96), (64, 1, 100), (96, 3, 160), (192, 1, 512), (256, 2, 2048)])
+@pytest.mark.parametrize("H,B,P", [(32, 2, 96), (64, 1, 100), (96, 3, 160), (192, 1, 512), (256, 2, 2048), (100, 2, 100)])
 def test_pointwise_siren_backward_native_vs_fp64_autograd(H, B, P):
     """fenerf_siren_forward_save_pointwise / _backward_pointwise / _param_grads_pointwise (round 6): the per-point-modulated
     SIREN (siren.py:464-477 with [B, P, 9H] frequencies / phase shifts) through SPATIALSIRENGRID.forward_with_frequencies_phase_shifts under
     autograd, against fp64 autograd of the same statements -- the gradient of every SIREN weight and bias and of the per-point frequency /
-    phase tensors themselves --, and against the PyTorch-ROCm route on the same inputs.  P = 100: padded to whole 32-point tiles."""
+    phase tensors themselves --, and against the PyTorch-ROCm route on the same inputs.  P = 100: padded to whole 32-point tiles.  H = 100: a width
+    between the instantiated ones, run at 128 with zero padding (native.padded_hidden_dim)."""
     torch.manual_seed(H + P)
     mod = S.SPATIALSIRENGRID(input_dim=3, z_dim=16, hidden_dim=H, output_dim=4).to(DEV).train()
     mod.device = torch.device(DEV)
@@ -3668,13 +3669,8 @@ def test_pointwise_siren_backward_native_vs_fp64_autograd(H, B, P):
     t64 = lambda t: t.detach().double().cpu()
     prm = {n: t64(q).requires_grad_(True) for n, q in mod.named_parameters() if mod._is_render_param(n)}
     f64, p64 = t64(f0).requires_grad_(True), t64(p0).requires_grad_(True)
-    x = t64(pts) * (2 / 0.24)
-    fr = f64 * 15 + 30
-    for i in range(8):
-        x = torch.sin(fr[..., i * H:(i + 1) * H] * torch.nn.functional.linear(x, prm[f"network.{i}.layer.weight"], prm[f"network.{i}.layer.bias"]) + p64[..., i * H:(i + 1) * H])
-    sigma = torch.nn.functional.linear(x, prm["final_layer.weight"], prm["final_layer.bias"])
-    c = torch.sin(fr[..., -H:] * torch.nn.functional.linear(torch.cat([t64(dirs), x], -1), prm["color_layer_sine.layer.weight"], prm["color_layer_sine.layer.bias"]) + p64[..., -H:])
-    ref = torch.cat([torch.sigmoid(torch.nn.functional.linear(c, prm["color_layer_linear.0.weight"], prm["color_layer_linear.0.bias"])), sigma], -1)
+    from oracle import fenerf_oracle_grad as OG
+    ref = OG.siren_forward_pointwise(prm, H, t64(pts), t64(dirs), f64, p64)
     (ref * t64(w)).sum().backward()
     want = dict(out=ref.detach().numpy(), f=f64.grad.numpy(), p=p64.grad.numpy(), **{n: q.grad.numpy() for n, q in prm.items()})
     assert set(want) == set(res["native"]) == set(res["torch"])
