@@ -180,6 +180,84 @@ def sample_generator_wth_frequencies_phase_shifts(generator, meta, max_batch=Non
     return native.to_host(out[..., -1].reshape(voxel_resolution, voxel_resolution, voxel_resolution).contiguous()).numpy()
 
 
+MESH_NORMAL_CHUNK = 262144       # vertices per differentiable SIREN call of extract_mesh's normals: bounds the tape
+
+
+def extract_mesh(generator, z_geo, z_app=None, *, film=None, voxel_resolution=256, voxel_origin=(0, 0, 0), cube_length=2.0, psi=0.5, iso=10.0,
+                 attributes=("normal", "label", "rgb")):
+    """Labelled, coloured iso-surface of one identity: the step the reference leaves to skimage.measure.marching_cubes + plyfile
+    (extract_shapes.py, extract_double_semantic_shapes.py).  The lattice is evaluated exactly as sample_generator does (truncated FiLM
+    parameters, locked view direction, one fused launch) -- or, with film= (the meta dict of
+    sample_generator_wth_frequencies_phase_shifts), as that function does; z_geo / z_app / psi are then ignored.  The density volume stays on
+    the device and goes through native.mesh_from_volume (marching tetrahedra, include/fenerf.h) with the per-column origin and spacing of
+    create_samples: vertex column k is in the coordinates of samples[:, k], so vertices can be fed straight back to the SIREN.  That is what
+    happens next: one forward at the vertices (padded to whole 32-point tiles) gives `label` (argmax of the label logits, uint8) and `rgb`
+    (the SIREN's rgb as the image writer maps a pixel: * 2 - 1, then [-1, 1] -> 0..255); `normal` is -grad(sigma) normalised, through the
+    differentiable bare-SIREN route in chunks of at most MESH_NORMAL_CHUNK vertices.
+    -> dict of numpy arrays: vertices [V,3] float32, faces [F,3] int32 and the requested attributes (normal [V,3] float32, label [V] uint8,
+    rgb [V,3] uint8).  iso = 10.0 is this project's choice: the reference's scripts name no level.
+    Like sample_generator, the z_geo route calls generate_avg_frequencies, whose 2 x 10,000 draws start from the generator state the caller
+    leaves: for the surface of a volume sample_generator returned, restore that state first (tools/extract_shapes.py re-seeds)."""
+    from . import imageio_lite
+    from .siren import autograd as siren_autograd
+    unknown = set(attributes) - {"normal", "label", "rgb"}
+    if unknown:
+        raise ValueError(f"extract_mesh: unknown attributes {sorted(unknown)}")
+    N = voxel_resolution
+    siren = generator.siren
+    with torch.no_grad():
+        if film is None:
+            z_app = z_geo if z_app is None else z_app
+            device = z_geo.device
+            avg_fg, avg_pg, avg_fa, avg_pa = generator.generate_avg_frequencies()
+            raw_fg, raw_pg = siren.geo_mapping_network(z_geo)
+            raw_fa, raw_pa = siren.app_mapping_network(z_app)
+            fg, pg = avg_fg + psi * (raw_fg - avg_fg), avg_pg + psi * (raw_pg - avg_pg)
+            fa, pa = avg_fa + psi * (raw_fa - avg_fa), avg_pa + psi * (raw_pa - avg_pa)
+        else:
+            device = generator.device
+            fg, pg = film["truncated_frequencies_geo"], film["truncated_phase_shifts_geo"]
+            fa, pa = film["truncated_frequencies_app"], film["truncated_phase_shifts_app"]
+        samples, origin, voxel_size = create_samples(N, voxel_origin, cube_length, device=device)
+        nat = siren.native(samples.device)
+        out = nat.siren_forward(samples, None, fg, pg, fa, pa)          # None = locked view dir
+        sigma = out[..., -1].reshape(N, N, N).contiguous()
+        del out
+        # samples[:, k] = (lattice index along axis k) * voxel_size + origin[2 - k]  (create_samples)
+        vertices, faces = native.mesh_from_volume(sigma, iso, origin=(origin[2], origin[1], origin[0]), spacing=(voxel_size,) * 3)
+        V = vertices.shape[0]
+        mesh = dict(vertices=native.to_host(vertices).numpy(), faces=native.to_host(faces).numpy())
+        if V and ("label" in attributes or "rgb" in attributes):
+            pad = (-V) % 32
+            pts = torch.cat([vertices, vertices[-1:].expand(pad, -1)])[None] if pad else vertices[None]
+            rows = nat.siren_forward(pts.contiguous(), None, fg, pg, fa, pa)[0, :V]
+            if "label" in attributes:
+                mesh["label"] = native.to_host(torch.argmax(rows[:, :-4], dim=1).to(torch.uint8)).numpy()
+            if "rgb" in attributes:
+                pix = native.to_host((rows[:, -4:-1] * 2 - 1).t().contiguous()).numpy()[None, :, :, None]        # [1, 3, V, 1]: an image one pixel wide
+                mesh["rgb"] = imageio_lite.to_uint8_hwc(imageio_lite._grid_np(pix, normalize=True, value_range=(-1, 1)))[:, 0]
+        elif not V:
+            mesh.update({k: np.zeros(s, d) for k, s, d in (("label", (0,), np.uint8), ("rgb", (0, 3), np.uint8)) if k in attributes})
+    if "normal" in attributes:
+        normal = torch.empty((V, 3), dtype=torch.float32, device=vertices.device)
+        # only the positions take a gradient: with every weight constant the backward is the chain and the input-gradient pass alone
+        params = [p for p in siren._render_params() if p.requires_grad]
+        for p in params:
+            p.requires_grad_(False)
+        try:
+            for s0 in range(0, V, MESH_NORMAL_CHUNK):
+                with torch.enable_grad():
+                    pts = vertices[None, s0:s0 + MESH_NORMAL_CHUNK].detach().clone().requires_grad_(True)
+                    sig = siren_autograd.siren_apply(siren, pts, None, fg.detach(), pg.detach(), fa.detach(), pa.detach())[..., -1]
+                    g, = torch.autograd.grad(sig.sum(), pts)
+                normal[s0:s0 + MESH_NORMAL_CHUNK] = -g[0] / g[0].norm(dim=-1, keepdim=True).clamp_min(1e-30)
+        finally:
+            for p in params:
+                p.requires_grad_(True)
+        mesh["normal"] = native.to_host(normal).numpy()
+    return mesh
+
+
 # ---- the inversion script's host pieces (inverse_render_double_semantic.py) ------------------------------------------------------------
 COLOR_MAP_COMPLETE_KEYS = 19      # labels 0 (background) .. 18 of the script's COLOR_MAP_COMPLETE (:50-69); COLOR_MAP has 1 .. 18
 

@@ -1195,6 +1195,43 @@ extern "C" int fenerf_sparse_select(int B, int R, int N, int C, int64_t cap, con
   { PhaseScope ph(PH_OTHER, stream); return launch_sparse_select(B, R, N, C, cap, d_coarse, d_fine, z_coarse, z_fine, origins, dirs, (const long long*)images, pts, rd, d_sel, counts, workspace, stream); }
 }
 
+// ---- iso-surface extraction (fenerf_mesh.hip) ----
+namespace {
+int check_lattice(const char* who, int n0, int n1, int n2) {
+  if (n0 < 2 || n1 < 2 || n2 < 2) return fail(FENERF_E_INVALID, std::string(who) + ": every lattice axis needs at least 2 points");
+  if ((int64_t)n0 * n1 * n2 > INT32_MAX) return fail(FENERF_E_INVALID, std::string(who) + ": more than 2^31 - 1 lattice points");
+  return FENERF_OK;
+}
+}  // namespace
+
+extern "C" size_t fenerf_mesh_workspace_bytes(int n0, int n1, int n2) {
+  if (check_lattice("fenerf_mesh_workspace_bytes", n0, n1, n2) != FENERF_OK) return 0;
+  return mesh_workspace_bytes(n0, n1, n2);
+}
+
+extern "C" int fenerf_mesh_count(const float* vol, int n0, int n1, int n2, float iso, void* workspace, int64_t* counts_dev, void* stream) {
+  if (int rc = check_lattice("fenerf_mesh_count", n0, n1, n2)) return rc;
+  if (!vol || !workspace || !counts_dev) return fail(FENERF_E_INVALID, "fenerf_mesh_count: vol / workspace / counts_dev is NULL");
+  { PhaseScope ph(PH_OTHER, stream); return launch_mesh_count(vol, n0, n1, n2, iso, workspace, (long long*)counts_dev, stream); }
+}
+
+extern "C" int fenerf_mesh_emit(const float* vol, int n0, int n1, int n2, float iso, const float origin[3], const float spacing[3], const void* workspace,
+                                int64_t n_vertices, int64_t n_faces, float* vertices, int32_t* faces, void* stream) {
+  if (int rc = check_lattice("fenerf_mesh_emit", n0, n1, n2)) return rc;
+  if (!vol || !workspace || !origin || !spacing) return fail(FENERF_E_INVALID, "fenerf_mesh_emit: vol / workspace / origin / spacing is NULL");
+  if (n_vertices < 0 || n_faces < 0) return fail(FENERF_E_INVALID, "fenerf_mesh_emit: negative count");
+  if (n_vertices > INT32_MAX || n_faces > INT32_MAX)
+    return fail(FENERF_E_UNSUPPORTED, "fenerf_mesh_emit: 2^31 or more vertices or faces (faces index vertices as int32): extract the volume in parts");
+  if ((n_vertices > 0 && !vertices) || (n_faces > 0 && !faces)) return fail(FENERF_E_INVALID, "fenerf_mesh_emit: vertices / faces is NULL");
+  long long held[2] = {-1, -1};       // what fenerf_mesh_count left in the workspace: the one host read of this call
+  if (hipError_t e = hipMemcpyAsync(held, mesh_workspace_totals(workspace), sizeof(held), hipMemcpyDeviceToHost, (hipStream_t)stream)) return hip_fail(e, "mesh counts copy");
+  if (hipError_t e = hipStreamSynchronize((hipStream_t)stream)) return hip_fail(e, "mesh counts copy");
+  if (held[0] != n_vertices || held[1] != n_faces)
+    return fail(FENERF_E_INVALID, "fenerf_mesh_emit: the workspace holds " + std::to_string(held[0]) + " vertices and " + std::to_string(held[1]) +
+                                      " faces, the call says " + std::to_string((long long)n_vertices) + " and " + std::to_string((long long)n_faces));
+  { PhaseScope ph(PH_OTHER, stream); return launch_mesh_emit(vol, n0, n1, n2, iso, origin, spacing, workspace, n_vertices, n_faces, vertices, faces, stream); }
+}
+
 // workspace layout of fenerf_render_forward
 namespace {
 struct RenderWs {

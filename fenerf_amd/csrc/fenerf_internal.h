@@ -227,6 +227,12 @@ size_t sparse_select_workspace_bytes(int B, long long P);
 int launch_sparse_select(int B, int R, int N, int C, long long cap, const float* d_coarse, const float* d_fine, const float* z_coarse,
                          const float* z_fine, const float* origins, const float* dirs, const long long* images, float* pts, float* rd, float* d_sel,
                          int* counts, void* workspace, void* stream);
+// fenerf_mesh.hip: marching tetrahedra (fenerf_mesh_count / fenerf_mesh_emit)
+size_t mesh_workspace_bytes(int n0, int n1, int n2);
+const long long* mesh_workspace_totals(const void* workspace);      // [dev] vertices, faces: what launch_mesh_count left there
+int launch_mesh_count(const float* vol, int n0, int n1, int n2, float iso, void* workspace, long long* counts_dev, void* stream);
+int launch_mesh_emit(const float* vol, int n0, int n1, int n2, float iso, const float* origin, const float* spacing, const void* workspace,
+                     long long n_vertices, long long n_faces, float* vertices, int* faces, void* stream);
 int launch_pad_rows(const float* src, float* dst, long long nb, long long P, long long Pp, int C, bool to_padded, void* stream);
 int launch_multi_add(const MultiAdd& J, void* stream);
 int launch_film_fold(const FilmFold& J, void* stream);

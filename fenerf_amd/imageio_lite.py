@@ -166,3 +166,76 @@ def read_mrc(path):
     dmin, dmax, dmean = struct.unpack_from("<3f", raw, 76)
     return data, dict(nx=nx, ny=ny, nz=nz, mode=mode, cella=struct.unpack_from("<3f", raw, 40), ispg=struct.unpack_from("<i", raw, 88)[0],
                       dmin=dmin, dmax=dmax, dmean=dmean, rms=struct.unpack_from("<f", raw, 216)[0], nversion=struct.unpack_from("<i", raw, 108)[0])
+
+
+def _ply_vertex_layout(normal, rgb, label):
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normal:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if rgb:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    if label:
+        fields += [("label", "u1")]
+    return fields
+
+
+def write_ply(path, vertices, faces, normal=None, rgb=None, label=None):
+    """A triangle mesh as a binary_little_endian 1.0 PLY file (what the reference's shape scripts hand to plyfile; plyfile is not a
+    dependency here): vertex properties x y z float, then optionally nx ny nz float, red green blue uchar and label uchar; faces as
+    `list uchar int vertex_indices`.  Readable by MeshLab, Blender, trimesh and read_ply below."""
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int32).reshape(-1, 3)
+    fields = _ply_vertex_layout(normal is not None, rgb is not None, label is not None)
+    rec = np.zeros(v.shape[0], dtype=np.dtype(fields))
+    rec["x"], rec["y"], rec["z"] = v.T
+    if normal is not None:
+        rec["nx"], rec["ny"], rec["nz"] = np.asarray(normal, dtype=np.float32).reshape(v.shape[0], 3).T
+    if rgb is not None:
+        rec["red"], rec["green"], rec["blue"] = np.asarray(rgb, dtype=np.uint8).reshape(v.shape[0], 3).T
+    if label is not None:
+        rec["label"] = np.asarray(label, dtype=np.uint8).reshape(v.shape[0])
+    frec = np.zeros(f.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    frec["n"], frec["v"] = 3, f
+    names = {"<f4": "float", "u1": "uchar"}
+    header = ["ply", "format binary_little_endian 1.0", "comment fenerf_amd.imageio_lite.write_ply", f"element vertex {v.shape[0]}"]
+    header += [f"property {names[t]} {name}" for name, t in fields]
+    header += [f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(rec.tobytes())
+        fh.write(frec.tobytes())
+
+
+def read_ply(path):
+    """dict(vertices [V,3] float32, faces [F,3] int32 and, where the file has them, normal [V,3] float32, rgb [V,3] uint8, label [V] uint8) of
+    a PLY file in write_ply's layout (the inverse of write_ply: binary_little_endian, triangles only)."""
+    raw = open(path, "rb").read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    lines = raw[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or lines[1] != "format binary_little_endian 1.0":
+        raise ValueError(f"{path}: not a binary_little_endian 1.0 PLY file")
+    types = {"float": "<f4", "uchar": "u1"}
+    counts, fields, element = {}, [], None
+    for ln in lines[2:]:
+        w = ln.split()
+        if w[:1] == ["element"]:
+            element, counts[w[1]] = w[1], int(w[2])
+        elif w[:1] == ["property"] and element == "vertex":
+            fields.append((w[2], types[w[1]]))
+        elif w[:1] == ["property"] and w[1:] != ["list", "uchar", "int", "vertex_indices"]:
+            raise ValueError(f"{path}: face property '{ln}' (write_ply's layout has `list uchar int vertex_indices` only)")
+    nv, nf = counts["vertex"], counts["face"]
+    vdt = np.dtype(fields)
+    rec = np.frombuffer(raw, vdt, nv, end)
+    frec = np.frombuffer(raw, np.dtype([("n", "u1"), ("v", "<i4", (3,))]), nf, end + nv * vdt.itemsize)
+    if nf and not (frec["n"] == 3).all():
+        raise ValueError(f"{path}: faces that are not triangles")
+    have = set(vdt.names)
+    out = dict(vertices=np.stack([rec["x"], rec["y"], rec["z"]], -1).astype(np.float32), faces=np.ascontiguousarray(frec["v"], dtype=np.int32))
+    if {"nx", "ny", "nz"} <= have:
+        out["normal"] = np.stack([rec["nx"], rec["ny"], rec["nz"]], -1).astype(np.float32)
+    if {"red", "green", "blue"} <= have:
+        out["rgb"] = np.stack([rec["red"], rec["green"], rec["blue"]], -1).astype(np.uint8)
+    if "label" in have:
+        out["label"] = np.array(rec["label"], dtype=np.uint8)
+    return out

@@ -1428,3 +1428,27 @@ def composite_backward(g_rgb, rows_a, z_a, opts, rows_b=None, z_b=None, noise=No
             _lib.check(_lib.lib().fenerf_composite_backward(BR, N, Cc, int(merge), _ptr(ra), _ptr(rb), _ptr(za), _ptr(zb), _ptr(nz),
                                                             C.byref(opts), _ptr(g), _ptr(da), _ptr(db), _stream()))
     return (da, db) if merge else da
+
+
+def mesh_from_volume(vol, iso, origin=(0, 0, 0), spacing=(1, 1, 1)):
+    """Iso-surface of a device volume [n0,n1,n2] by marching tetrahedra (fenerf_mesh_count / fenerf_mesh_emit, include/fenerf.h; restated in
+    numpy by fenerf_amd/mesh_emulation.py) -> (vertices [V,3] float32, faces [F,3] int32) on the device.  Vertex column j =
+    origin[j] + (lattice coordinate along axis j) * spacing[j].  One host read (the two counts) between the two calls."""
+    assert vol.is_cuda and vol.dim() == 3
+    dev = vol.device
+    v = _f32(vol, dev)
+    n0, n1, n2 = v.shape
+    nbytes = _lib.lib().fenerf_mesh_workspace_bytes(n0, n1, n2)
+    ws = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
+    counts = torch.empty((2,), dtype=torch.int64, device=dev)
+    o3, s3 = (C.c_float * 3)(*(float(x) for x in origin)), (C.c_float * 3)(*(float(x) for x in spacing))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_mesh_count(_ptr(v), n0, n1, n2, float(iso), C.c_void_p(ws.data_ptr()), C.c_void_p(counts.data_ptr()), _stream()))
+        nv, nf = (int(x) for x in to_host(counts))
+        big = nv >= 2 ** 31 or nf >= 2 ** 31          # refused by the library (FENERF_E_UNSUPPORTED) before it looks at the outputs
+        vertices = torch.empty((0 if big else nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((0 if big else nf, 3), dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().fenerf_mesh_emit(_ptr(v), n0, n1, n2, float(iso), o3, s3, C.c_void_p(ws.data_ptr()), nv, nf,
+                                               C.c_void_p(vertices.data_ptr()) if vertices.numel() else None,
+                                               C.c_void_p(faces.data_ptr()) if faces.numel() else None, _stream()))
+    return vertices, faces

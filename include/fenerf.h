@@ -724,6 +724,36 @@ int fenerf_sparse_select(int B, int R, int N, int C, int64_t cap, const float* d
                          const float* z_fine, const float* origins, const float* dirs, const int64_t* images, float* pts, float* rd,
                          float* d_sel, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- iso-surface extraction: marching tetrahedra on the device (no model handle, like fenerf_composite) ----
+ * replaces: skimage.measure.marching_cubes on the host copy of the density volume (extract_shapes.py, extract_double_semantic_shapes.py).
+ * Marching tetrahedra on the Kuhn decomposition: 16 cases per tet derived in code (no 256-case table), crack-free across cells.
+ *   - vol [dev] [n0][n1][n2] fp32: point p = (a, b, c) has linear index i = (a * n1 + b) * n2 + c.  inside(p) := vol[p] >= iso, so a NaN
+ *     is not inside.
+ *   - a cell is a point c with c + (1,1,1) in the lattice; cells are ordered by the linear index of c.  Each cell has six tets, one per
+ *     axis permutation pi, in the order (0,1,2), (0,2,1), (1,0,2), (1,2,0), (2,0,1), (2,1,0): vertices c, c + e_pi0, c + e_pi0 + e_pi1,
+ *     c + (1,1,1).
+ *   - every tet edge is an owned edge of its lower endpoint: point p owns edge k = 1 .. 7 of direction d_k = (k & 1, (k >> 1) & 1,
+ *     (k >> 2) & 1) if p + d_k is in the lattice.  An owned edge with inside(p) != inside(q) carries exactly one vertex; vertices are
+ *     numbered in ascending (i, k).  t = (iso - vol[p]) / (vol[q] - vol[p]); coordinate j = origin[j] + (p_j + t * d_kj) * spacing[j],
+ *     every operation rounded to fp32 on its own (bit for bit fenerf_amd/mesh_emulation.py).
+ *   - a tet emits 0, 1 or 2 triangles over its crossing-edge vertices; a quad is split along the diagonal through its smallest vertex
+ *     number.  (v1 - v0) x (v2 - v0) points to the not-inside side (decided from integer lattice geometry).  Faces are ordered by cell,
+ *     then tet, then triangle.  Placement is by prefix sums, no atomics: the same bits on every run.
+ *   - zero-area triangles (t = 0 where a value equals iso) stay in the mesh.  A non-finite value yields non-finite coordinates of the
+ *     vertices on its own edges and changes nothing else: addresses and indices depend on integer indices and the `>= iso` bits only.
+ * FENERF_E_INVALID: an axis below 2 points, more than 2^31 - 1 points, a NULL pointer.
+ *
+ * fenerf_mesh_workspace_bytes: [dev] scratch for one lattice, about 5 bytes per point + 1 per cell (0 for an invalid lattice).
+ * fenerf_mesh_count: classifies and scans; counts_dev [dev] int64 [2] = vertices, faces.  Enqueues only.
+ * fenerf_mesh_emit: vol, iso and workspace as fenerf_mesh_count saw / left them; origin / spacing [host] [3]; n_vertices / n_faces = the two
+ *   counts (the caller reads them to size vertices [dev] [V][3] fp32 and faces [dev] [F][3] int32; either may be NULL when its count is 0).
+ *   This call WAITS for the stream once to compare them with what the workspace holds: FENERF_E_INVALID if they differ;
+ *   FENERF_E_UNSUPPORTED for 2^31 or more vertices or faces.  An empty mesh launches nothing and returns FENERF_OK. */
+size_t fenerf_mesh_workspace_bytes(int n0, int n1, int n2);
+int fenerf_mesh_count(const float* vol, int n0, int n1, int n2, float iso, void* workspace, int64_t* counts_dev, void* stream);
+int fenerf_mesh_emit(const float* vol, int n0, int n1, int n2, float iso, const float origin[3], const float spacing[3], const void* workspace,
+                     int64_t n_vertices, int64_t n_faces, float* vertices, int32_t* faces, void* stream);
+
 /* Bytes of [dev] scratch fenerf_render_forward needs. */
 size_t fenerf_render_workspace_bytes(const FenerfModel* m, int B, int R, int N, int hierarchical);
 

@@ -11,7 +11,11 @@ cube of side --cube_size with the view direction locked to (0, 0, -1) -> <output
 an inversion checkpoint (mean + offsets; tools/inverse_render.py or the reference's script wrote it) -> <output_dir>/<seeds[0]>.mrc.
 All N^3 points go through ONE fused SIREN launch (the reference walks them in chunks of 24,000 / 100,000).  The volume is written as an
 MRC2014 mode-2 map by fenerf_amd.imageio_lite.write_mrc (mrcfile is not a dependency); marching cubes on it is the downstream step
-the reference also leaves to other tools.  `<prefix>ema.pth` next to the generator pickle is loaded and copied in (:103-104).
+the reference also leaves to other tools (skimage.measure + plyfile).  With --mesh that step runs here, on the device:
+callers.extract_mesh (marching tetrahedra at the density level --iso, default 10; labels, colours and normals from the SIREN at the
+vertices) -> <output_dir>/<seed>.ply beside the .mrc.  `<prefix>ema.pth` next to the generator pickle is loaded and copied in (:103-104).
+
+    python tools/extract_shapes.py <path/to/generator.pth> --seeds 3 --mesh --iso 10
 """
 import argparse
 import os
@@ -29,7 +33,15 @@ def build_parser():
     parser.add_argument('--output_dir', type=str, default='shapes')
     parser.add_argument('--latent_path', type=str, default=None)
     parser.add_argument('--no_ema', action='store_true', help='use the raw generator weights (not in the reference: it always loads <prefix>ema.pth)')
+    parser.add_argument('--mesh', action='store_true', help='also write <seed>.ply: the labelled, coloured iso-surface (not in the reference)')
+    parser.add_argument('--iso', type=float, default=10.0, help='density level of the --mesh surface')
     return parser
+
+
+def write_mesh(callers, imageio_lite, path, generator, opt, **latent):
+    mesh = callers.extract_mesh(generator, latent.pop('z', None), cube_length=opt.cube_size, voxel_resolution=opt.voxel_resolution, iso=opt.iso, **latent)
+    imageio_lite.write_ply(path, mesh['vertices'], mesh['faces'], normal=mesh['normal'], rgb=mesh['rgb'], label=mesh['label'])
+    print(f"  mesh at sigma = {opt.iso:g}: {len(mesh['vertices'])} vertices, {len(mesh['faces'])} faces -> {path}")
 
 
 def main(argv=None):
@@ -52,6 +64,12 @@ def main(argv=None):
             out = os.path.join(opt.output_dir, f'{seed}.mrc')
             imageio_lite.write_mrc(out, voxel_grid)
             print(f"seed {seed}: sigma {voxel_grid.shape} in [{voxel_grid.min():.3g}, {voxel_grid.max():.3g}] -> {out}")
+            if opt.mesh:
+                # the mean FiLM parameters are drawn from the generator state the seed and the z draw leave behind: the same state again, so
+                # that the surface is the level set of the volume just written
+                torch.manual_seed(int(seed))
+                z = torch.randn(1, z_dim, device=device)
+                write_mesh(callers, imageio_lite, os.path.join(opt.output_dir, f'{seed}.ply'), generator, opt, z=z)
     else:
         meta = torch.load(opt.latent_path, map_location=device, weights_only=False)
         fg, fa, pg, pa = callers.film_from_inversion(meta, device)
@@ -60,6 +78,8 @@ def main(argv=None):
                                                                            voxel_resolution=opt.voxel_resolution)
         out = os.path.join(opt.output_dir, f'{opt.seeds[0]}.mrc')
         imageio_lite.write_mrc(out, voxel_grid)
+        if opt.mesh:
+            write_mesh(callers, imageio_lite, os.path.join(opt.output_dir, f'{opt.seeds[0]}.ply'), generator, opt, film=meta)
         print(f"inverted identity {opt.latent_path}: sigma {voxel_grid.shape} in [{voxel_grid.min():.3g}, {voxel_grid.max():.3g}] -> {out}")
 
 
