@@ -470,7 +470,10 @@ static int run_composite(const CompositeParams& p, bool merge, void* stream) {
   return launch_composite(p, merge, stream);
 }
 
-static void fill_common(const FenerfModel* m, SirenParams& sp, const float* fp, const float* pp) {
+// ---- how a SIREN launch is parameterised: nB images of n explicit points each, or nB images of R rays with N samples each
+static SirenParams point_params(const FenerfModel* m, const float* fp, const float* pp, long long nB, long long P, const float* points, const float* dirs,
+                                float* out) {
+  SirenParams sp;
   memset(&sp, 0, sizeof(sp));
   sp.stream = m->d_stream;
   sp.consts = m->d_consts;
@@ -478,6 +481,61 @@ static void fill_common(const FenerfModel* m, SirenParams& sp, const float* fp, 
   sp.grid = m->d_grid; sp.gd = m->gd; sp.gh = m->gh; sp.gw = m->gw;
   sp.box_scale = m->box_scale;
   sp.ring_offset_floats = (long long)m->sh.l0_entries * 256;
+  sp.points = points; sp.pdirs = dirs;
+  sp.P = nB * P; sp.pts_per_image = P; sp.n_per_ray = 1;
+  sp.out = out;
+  return sp;
+}
+static SirenParams ray_params(const FenerfModel* m, const float* fp, const float* pp, int B, int R, int N, const float* origins, const float* dirs,
+                              const float* z, int lock_view, float* out) {
+  SirenParams sp = point_params(m, fp, pp, B, (long long)R * N, nullptr, nullptr, out);      // no explicit points: the kernel builds them from the rays
+  sp.origins = origins; sp.dirs = dirs; sp.z = z; sp.n_per_ray = N; sp.lock_view = lock_view;
+  return sp;
+}
+// per-point FiLM blocks: the exact-fp32 kernel, on the exact-fp32 stream of a FENERF_PREC_F16X3 model
+static int run_siren_pointwise(const FenerfModel* m, SirenParams sp, void* stream) {
+  if (m->precision == FENERF_PREC_F16X3) { sp.stream = m->d_stream32; sp.consts = m->d_consts32; }
+  sp.film_per_point = 1;
+  PhaseScope ph(PH_SIREN, stream);
+  return launch_siren_f32(m, sp, stream);
+}
+
+static int check_tape_format(const FenerfModel* m, int tape_format) {
+  if (tape_format != FENERF_TAPE_F32 && tape_format != FENERF_TAPE_U16 && tape_format != FENERF_TAPE_F32_W) return fail(FENERF_E_INVALID, "unknown tape format");
+  if (tape_format != FENERF_TAPE_F32 && m->precision != FENERF_PREC_F16X3)
+    return fail(FENERF_E_UNSUPPORTED, "FENERF_TAPE_U16 / FENERF_TAPE_F32_W: FENERF_PREC_F16X3 models only (the exact-fp32 kernels keep the fp32 tape)");
+  return FENERF_OK;
+}
+
+// ---- the differentiable entries' preamble, in this order: model, tape format (FENERF_TAPE_F32 where the entry takes none), differentiable
+// (need_bwd_stream: the chain's stream too), B / P, then the entry's first pointer check (`ptrs_ok`, refused with `ptr_msg`) either behind
+// the P == 0 return (empty_last false) or in front of it.  *empty: nothing to do, return FENERF_OK
+static int diff_preamble(const FenerfModel* m, int tape_format, int B, int64_t P, bool need_bwd_stream, bool empty_last, bool ptrs_ok,
+                         const char* ptr_msg, bool* empty) {
+  *empty = false;
+  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
+  if (int rc = check_tape_format(m, tape_format)) return rc;
+  if (!m->differentiable || (need_bwd_stream && !m->d_bwd_stream)) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
+  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
+  if (P % 32) return fail(FENERF_E_INVALID, "differentiable path: points per image must be a multiple of 32");
+  *empty = P == 0;
+  if (*empty && !empty_last) return FENERF_OK;
+  return ptrs_ok ? FENERF_OK : fail(FENERF_E_INVALID, ptr_msg);
+}
+
+// ---- what makes a FenerfSirenGrads acceptable: the four FiLM gradients always; the weight / bias buffers all of them, or -- unless
+// all_required -- none of them (*film_only: FiLM gradients only, inversion)
+static int check_grads(const FenerfModel* m, const FenerfSirenGrads* g, bool all_required, bool* film_only) {
+  if (!g->d_freq_geo || !g->d_phase_geo || !g->d_freq_app || !g->d_phase_app) return fail(FENERF_E_INVALID, "grads: film pointer is NULL");
+  if (!film_only) return FENERF_OK;      // fenerf_siren_film_grads: it reads nothing else
+  int have = 0, want = 0;
+  for (int i = 0; i < m->n_geo; ++i) { want += 2; have += (g->geo_w[i] != nullptr) + (g->geo_b[i] != nullptr); }
+  for (int i = 0; i < m->n_color; ++i) { want += 2; have += (g->color_w[i] != nullptr) + (g->color_b[i] != nullptr); }
+  want += 4; have += (g->head_w != nullptr) + (g->head_b != nullptr) + (g->rgb_w != nullptr) + (g->rgb_b != nullptr);
+  if (all_required && have != want) return fail(FENERF_E_INVALID, "grads: every weight / bias buffer is required");
+  if (have != 0 && have != want) return fail(FENERF_E_INVALID, "grads: give every weight / bias buffer or none (FiLM gradients only)");
+  *film_only = have == 0;
+  return FENERF_OK;
 }
 
 extern "C" int fenerf_siren_forward(const FenerfModel* m, int B, int64_t P, const float* points, const float* ray_dirs,
@@ -490,12 +548,7 @@ extern "C" int fenerf_siren_forward(const FenerfModel* m, int B, int64_t P, cons
   const float *fp, *pp;
   int rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
-  SirenParams sp;
-  fill_common(m, sp, fp, pp);
-  sp.points = points; sp.pdirs = ray_dirs;
-  sp.P = (long long)B * P; sp.pts_per_image = P; sp.n_per_ray = 1;
-  sp.out = out;
-  return run_siren(m, sp, stream);
+  return run_siren(m, point_params(m, fp, pp, B, P, points, ray_dirs, out), stream);
 }
 
 extern "C" size_t fenerf_film_workspace_bytes_pointwise(const FenerfModel* m, int B, int64_t P) {
@@ -520,15 +573,7 @@ extern "C" int fenerf_siren_forward_pointwise(const FenerfModel* m, int B, int64
   float* pp = fp + (size_t)B * (size_t)P * m->L * m->H;
   int rc = [&] { PhaseScope ph(PH_FILM_PREP, stream); return launch_film_prep(m, (long long)B * P, freq_geo, phase_geo, freq_app, phase_app, fp, pp, stream, true); }();
   if (rc) return rc;
-  SirenParams sp;
-  fill_common(m, sp, fp, pp);
-  if (f16) { sp.stream = m->d_stream32; sp.consts = m->d_consts32; }
-  sp.points = points; sp.pdirs = ray_dirs;
-  sp.P = (long long)B * P; sp.pts_per_image = P; sp.n_per_ray = 1;
-  sp.out = out;
-  sp.film_per_point = 1;
-  PhaseScope ph(PH_SIREN, stream);
-  return launch_siren_f32(m, sp, stream);
+  return run_siren_pointwise(m, point_params(m, fp, pp, B, P, points, ray_dirs, out), stream);
 }
 
 extern "C" int fenerf_siren_forward_rays(const FenerfModel* m, int B, int R, int N, const float* origins,
@@ -542,12 +587,7 @@ extern "C" int fenerf_siren_forward_rays(const FenerfModel* m, int B, int R, int
   const float *fp, *pp;
   int rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
-  SirenParams sp;
-  fill_common(m, sp, fp, pp);
-  sp.origins = origins; sp.dirs = dirs; sp.z = z; sp.n_per_ray = N; sp.lock_view = lock_view;
-  sp.P = (long long)B * R * N; sp.pts_per_image = (long long)R * N;
-  sp.out = out;
-  return run_siren(m, sp, stream);
+  return run_siren(m, ray_params(m, fp, pp, B, R, N, origins, dirs, z, lock_view, out), stream);
 }
 
 extern "C" int fenerf_siren_time_rays(const FenerfModel* m, int B, int R, int N, const float* origins, const float* dirs,
@@ -559,11 +599,7 @@ extern "C" int fenerf_siren_time_rays(const FenerfModel* m, int B, int R, int N,
   const float *fp, *pp;
   int rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
-  SirenParams sp;
-  fill_common(m, sp, fp, pp);
-  sp.origins = origins; sp.dirs = dirs; sp.z = z; sp.n_per_ray = N;
-  sp.P = (long long)B * R * N; sp.pts_per_image = (long long)R * N;
-  sp.out = out;
+  const SirenParams sp = ray_params(m, fp, pp, B, R, N, origins, dirs, z, 0, out);
   hipEvent_t e0, e1;
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));
@@ -591,11 +627,7 @@ extern "C" int fenerf_siren_clock_probe(const FenerfModel* m, int B, int R, int 
   const float *fp, *pp;
   int rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
-  SirenParams sp;
-  fill_common(m, sp, fp, pp);
-  sp.origins = origins; sp.dirs = dirs; sp.z = z; sp.n_per_ray = N;
-  sp.P = (long long)B * R * N; sp.pts_per_image = (long long)R * N;
-  sp.out = out;
+  SirenParams sp = ray_params(m, fp, pp, B, R, N, origins, dirs, z, 0, out);
   if (sp.pts_per_image % 32 != 0 && B > 1) return fail(FENERF_E_INVALID, "clock probe: one launch only (R * N a multiple of 32, or B = 1)");
   int dev = 0, khz = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -744,13 +776,6 @@ extern "C" size_t fenerf_siren_tape_bytes(const FenerfModel* m, int64_t total_po
   return tape_format == FENERF_TAPE_U16 ? f * 2 : f * 4;      // same tiles, same slack, 2 instead of 4 bytes per (point, feature)
 }
 
-static int check_tape_format(const FenerfModel* m, int tape_format) {
-  if (tape_format != FENERF_TAPE_F32 && tape_format != FENERF_TAPE_U16 && tape_format != FENERF_TAPE_F32_W) return fail(FENERF_E_INVALID, "unknown tape format");
-  if (tape_format != FENERF_TAPE_F32 && m->precision != FENERF_PREC_F16X3)
-    return fail(FENERF_E_UNSUPPORTED, "FENERF_TAPE_U16 / FENERF_TAPE_F32_W: FENERF_PREC_F16X3 models only (the exact-fp32 kernels keep the fp32 tape)");
-  return FENERF_OK;
-}
-
 extern "C" size_t fenerf_siren_dtheta_floats(const FenerfModel* m, int64_t total_points) {
   if (!m || total_points <= 0) return 0;
   const long long tiles = (total_points + 31) / 32;
@@ -792,22 +817,46 @@ extern "C" int fenerf_siren_forward_save_fmt(const FenerfModel* m, int B, int64_
                                              const float* freq_geo, const float* phase_geo, const float* freq_app,
                                              const float* phase_app, float* out, void* tape, float* tape_e, void* film_ws,
                                              int tape_format, void* stream) {
-  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
-  if (int rcf = check_tape_format(m, tape_format)) return rcf;
-  if (!m->differentiable) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
-  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
-  if (P % 32) return fail(FENERF_E_INVALID, "differentiable path: points per image must be a multiple of 32");
-  if (P == 0) return FENERF_OK;
-  if (!points || !out || !tape || (m->grid_ch && !tape_e)) return fail(FENERF_E_INVALID, "points / out / tape is NULL");
+  bool empty;
+  int rc = diff_preamble(m, tape_format, B, P, false, false, points && out && tape && !(m && m->grid_ch && !tape_e), "points / out / tape is NULL", &empty);
+  if (rc || empty) return rc;
   const float *fp, *pp;
-  int rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
+  rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
-  SirenParams sp;
-  fill_common(m, sp, fp, pp);
-  sp.points = points; sp.pdirs = ray_dirs;
-  sp.P = (long long)B * P; sp.pts_per_image = P; sp.n_per_ray = 1;
-  sp.out = out; sp.tape = (float*)tape; sp.tape_e = tape_e; sp.tape_format = tape_format;
+  SirenParams sp = point_params(m, fp, pp, B, P, points, ray_dirs, out);
+  sp.tape = (float*)tape; sp.tape_e = tape_e; sp.tape_format = tape_format;
   return run_siren(m, sp, stream);
+}
+
+// ---- how a chain launch is parameterised: nb images of n points each, then "dump here" or "FiLM sums only", and where d(grid features) go:
+// nowhere, out to bp.d_e, or "scatter into this grid"
+static SirenBwdParams chain_params(const FenerfModel* m, const float* fp, const float* pp, long long nb, long long n, const float* out,
+                                   const float* d_out, const void* tape, int tape_format) {
+  SirenBwdParams bp;
+  memset(&bp, 0, sizeof(bp));
+  bp.stream = m->d_bwd_stream;
+  bp.ring_offset_floats = (long long)m->bsh.ht_entries * 256;
+  bp.fp = fp; bp.pp = pp;
+  bp.P = nb * n; bp.pts_per_image = n;
+  bp.out = out; bp.d_out = d_out; bp.tape = (const float*)tape; bp.tape_format = tape_format;
+  return bp;
+}
+// dump here: d(theta) at d_t in the format the chunk's size asks for (remembered for the call that reads it), the FiLM sums appended behind it
+static void chain_dump_to(const FenerfModel* m, SirenBwdParams& bp, float* d_t) {
+  bp.d_t = d_t;
+  bp.film_tiles = d_t + (size_t)m->L * m->H * (size_t)bp.P;
+  bp.bf16_dump = use_bf16_dump(m, bp.P);
+  note_dump(m, d_t, bp.P);
+}
+// FiLM sums only: no dump, no d(grid features)
+static void chain_film_sums_only(SirenBwdParams& bp, float* film_sums) { bp.film_tiles = film_sums; }
+// scatter into this grid: d(grid features) straight into the channels-last gradient grid instead of d_e (the f16x3 chain kernel)
+static void chain_scatter_into(const FenerfModel* m, SirenBwdParams& bp, const float* points, float* d_grid_cl) {
+  bp.points = points; bp.d_grid_cl = d_grid_cl; bp.box_scale = m->box_scale; bp.gd = m->gd; bp.gh = m->gh; bp.gw = m->gw;
+}
+static int run_chain(const FenerfModel* m, const SirenBwdParams& bp, void* stream) {
+  PhaseScope ph(PH_CHAIN, stream);
+  return m->precision == FENERF_PREC_F16X3 ? launch_siren_backward16w(m, bp, stream) : launch_siren_backward(m, bp, stream);
 }
 
 extern "C" int fenerf_siren_backward(const FenerfModel* m, int B, int64_t P, const float* freq_geo, const float* phase_geo,
@@ -819,28 +868,16 @@ extern "C" int fenerf_siren_backward(const FenerfModel* m, int B, int64_t P, con
 extern "C" int fenerf_siren_backward_fmt(const FenerfModel* m, int B, int64_t P, const float* freq_geo, const float* phase_geo,
                                          const float* freq_app, const float* phase_app, const float* out, const float* d_out,
                                          const void* tape, int tape_format, float* d_t, float* d_e, void* film_ws, void* stream) {
-  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
-  if (int rcf = check_tape_format(m, tape_format)) return rcf;
-  if (!m->differentiable || !m->d_bwd_stream) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
-  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
-  if (P % 32) return fail(FENERF_E_INVALID, "differentiable path: points per image must be a multiple of 32");
-  if (P == 0) return FENERF_OK;
-  if (!out || !d_out || !tape || !d_t || (m->grid_ch && !d_e)) return fail(FENERF_E_INVALID, "NULL pointer");
+  bool empty;
+  int rc = diff_preamble(m, tape_format, B, P, true, false, out && d_out && tape && d_t && !(m && m->grid_ch && !d_e), "NULL pointer", &empty);
+  if (rc || empty) return rc;
   const float *fp, *pp;
-  int rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
+  rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
-  SirenBwdParams bp;
-  memset(&bp, 0, sizeof(bp));
-  bp.stream = m->d_bwd_stream;
-  bp.ring_offset_floats = (long long)m->bsh.ht_entries * 256;
-  bp.fp = fp; bp.pp = pp;
-  bp.P = (long long)B * P; bp.pts_per_image = P;
-  bp.out = out; bp.d_out = d_out; bp.tape = (const float*)tape; bp.tape_format = tape_format; bp.d_t = d_t; bp.d_e = d_e;
-  bp.film_tiles = d_t + (size_t)m->L * m->H * (size_t)B * (size_t)P;    // appended to the dtheta dump
-  bp.bf16_dump = use_bf16_dump(m, (long long)B * P);
-  note_dump(m, d_t, (long long)B * P);
-  PhaseScope ph(PH_CHAIN, stream);
-  return m->precision == FENERF_PREC_F16X3 ? launch_siren_backward16w(m, bp, stream) : launch_siren_backward(m, bp, stream);
+  SirenBwdParams bp = chain_params(m, fp, pp, B, P, out, d_out, tape, tape_format);
+  chain_dump_to(m, bp, d_t);
+  bp.d_e = d_e;
+  return run_chain(m, bp, stream);
 }
 
 extern "C" size_t fenerf_siren_film_sums_floats(const FenerfModel* m, int B, int64_t P) {
@@ -855,43 +892,29 @@ extern "C" size_t fenerf_siren_film_sums_floats(const FenerfModel* m, int B, int
 extern "C" int fenerf_siren_backward_film(const FenerfModel* m, int B, int64_t P, const float* freq_geo, const float* phase_geo,
                                           const float* freq_app, const float* phase_app, const float* out, const float* d_out,
                                           const float* tape, float* film_sums, void* film_ws, void* stream) {
-  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
-  if (!m->differentiable || !m->d_bwd_stream) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
-  if (m->precision != FENERF_PREC_F16X3)
+  if (m && m->differentiable && m->precision != FENERF_PREC_F16X3)
     return fail(FENERF_E_UNSUPPORTED, "fenerf_siren_backward_film: FENERF_PREC_F16X3 models only (the exact-fp32 jobs take their FiLM sums from the dump)");
-  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
-  if (P % 32) return fail(FENERF_E_INVALID, "differentiable path: points per image must be a multiple of 32");
-  if (P == 0) return FENERF_OK;
-  if (!out || !d_out || !tape || !film_sums) return fail(FENERF_E_INVALID, "NULL pointer");
+  bool empty;
+  int rc = diff_preamble(m, FENERF_TAPE_F32, B, P, true, false, out && d_out && tape && film_sums, "NULL pointer", &empty);
+  if (rc || empty) return rc;
   const float *fp, *pp;
-  int rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
+  rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
-  SirenBwdParams bp;
-  memset(&bp, 0, sizeof(bp));
-  bp.stream = m->d_bwd_stream;
-  bp.ring_offset_floats = (long long)m->bsh.ht_entries * 256;
-  bp.fp = fp; bp.pp = pp;
-  bp.P = (long long)B * P; bp.pts_per_image = P;
-  bp.out = out; bp.d_out = d_out; bp.tape = tape;
-  bp.d_t = nullptr; bp.d_e = nullptr;          // no dump, no d(grid features)
-  bp.film_tiles = film_sums;
-  PhaseScope ph(PH_CHAIN, stream);
-  return launch_siren_backward16w(m, bp, stream);
+  SirenBwdParams bp = chain_params(m, fp, pp, B, P, out, d_out, tape, FENERF_TAPE_F32);
+  chain_film_sums_only(bp, film_sums);
+  return run_chain(m, bp, stream);
 }
 
 extern "C" int fenerf_siren_film_grads(const FenerfModel* m, int B, int64_t P, const float* freq_geo, const float* phase_geo,
                                        const float* freq_app, const float* phase_app, const float* film_sums,
                                        const FenerfSirenGrads* g, void* workspace, void* film_ws, void* stream) {
-  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
-  if (!m->differentiable) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
-  if (m->precision != FENERF_PREC_F16X3) return fail(FENERF_E_UNSUPPORTED, "fenerf_siren_film_grads: FENERF_PREC_F16X3 models only");
-  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
-  if (P % 32) return fail(FENERF_E_INVALID, "differentiable path: points per image must be a multiple of 32");
-  if (P == 0) return FENERF_OK;
-  if (!film_sums || !g || !workspace) return fail(FENERF_E_INVALID, "NULL pointer");
-  if (!g->d_freq_geo || !g->d_phase_geo || !g->d_freq_app || !g->d_phase_app) return fail(FENERF_E_INVALID, "grads: film pointer is NULL");
+  if (m && m->differentiable && m->precision != FENERF_PREC_F16X3) return fail(FENERF_E_UNSUPPORTED, "fenerf_siren_film_grads: FENERF_PREC_F16X3 models only");
+  bool empty;
+  int rc = diff_preamble(m, FENERF_TAPE_F32, B, P, false, false, film_sums && g && workspace, "NULL pointer", &empty);
+  if (rc || empty) return rc;
+  if ((rc = check_grads(m, g, false, nullptr))) return rc;
   const float *fp, *pp;
-  int rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
+  rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
   return launch_param_grads(m, B, P, nullptr, nullptr, fp, pp, nullptr, nullptr, nullptr, nullptr, nullptr, *g, true, workspace, stream, film_sums);
 }
@@ -923,26 +946,16 @@ extern "C" int fenerf_siren_backward_grid_fmt(const FenerfModel* m, int B, int64
     if (rc || P == 0) return rc;
     { PhaseScope ph(PH_GRID, stream); return launch_grid_backward(m, (long long)B * P, points, scratch_d_e, d_grid_cl, stream); }
   }
-  if (!m->differentiable || !m->d_bwd_stream) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
-  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
-  if (P % 32) return fail(FENERF_E_INVALID, "differentiable path: points per image must be a multiple of 32");
-  if (P == 0) return FENERF_OK;
-  if (!out || !d_out || !tape || !d_t) return fail(FENERF_E_INVALID, "NULL pointer");
+  bool empty;
+  int rc = diff_preamble(m, tape_format, B, P, true, false, out && d_out && tape && d_t, "NULL pointer", &empty);
+  if (rc || empty) return rc;
   const float *fp, *pp;
-  int rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
+  rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
-  SirenBwdParams bp;
-  memset(&bp, 0, sizeof(bp));
-  bp.stream = m->d_bwd_stream;
-  bp.ring_offset_floats = (long long)m->bsh.ht_entries * 256;
-  bp.fp = fp; bp.pp = pp;
-  bp.P = (long long)B * P; bp.pts_per_image = P;
-  bp.out = out; bp.d_out = d_out; bp.tape = (const float*)tape; bp.tape_format = tape_format; bp.d_t = d_t; bp.d_e = nullptr;
-  bp.film_tiles = d_t + (size_t)m->L * m->H * (size_t)B * (size_t)P;
-  bp.points = points; bp.d_grid_cl = d_grid_cl; bp.box_scale = m->box_scale; bp.gd = m->gd; bp.gh = m->gh; bp.gw = m->gw;
-  bp.bf16_dump = use_bf16_dump(m, (long long)B * P);
-  note_dump(m, d_t, (long long)B * P);
-  { PhaseScope ph(PH_CHAIN, stream); return launch_siren_backward16w(m, bp, stream); }
+  SirenBwdParams bp = chain_params(m, fp, pp, B, P, out, d_out, tape, tape_format);
+  chain_dump_to(m, bp, d_t);
+  chain_scatter_into(m, bp, points, d_grid_cl);
+  return run_chain(m, bp, stream);
 }
 
 extern "C" size_t fenerf_siren_grad_workspace_bytes(const FenerfModel* m, int B, int64_t P) {
@@ -964,30 +977,20 @@ extern "C" int fenerf_siren_param_grads_fmt(const FenerfModel* m, int B, int64_t
                                             const float* phase_app, const float* out, const float* d_out, const void* tape,
                                             int tape_format, const float* tape_e, const float* d_t, const FenerfSirenGrads* g,
                                             const FenerfSirenGrads* weights, void* workspace, void* film_ws, void* stream) {
-  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
-  if (int rcf = check_tape_format(m, tape_format)) return rcf;
-  if (tape_format != FENERF_TAPE_F32) {
+  if (m && tape_format != FENERF_TAPE_F32) {      // (ahead of the preamble: a 16-bit tape without the weights is refused whatever else is wrong)
+    if (int rcf = check_tape_format(m, tape_format)) return rcf;
     if (!weights) return fail(FENERF_E_INVALID, "FENERF_TAPE_U16 / _F32_W: the FiLM layers' weights are required (the frequency gradients are derived from the weight-gradient sums)");
     for (int i = 0; i < m->n_geo; ++i) if (!weights->geo_w[i]) return fail(FENERF_E_INVALID, "FENERF_TAPE_U16 / _F32_W: weights->geo_w has a NULL entry");
     for (int i = 0; i < m->n_color; ++i) if (!weights->color_w[i]) return fail(FENERF_E_INVALID, "FENERF_TAPE_U16 / _F32_W: weights->color_w has a NULL entry");
   }
-  if (!m->differentiable) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
-  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
-  if (P % 32) return fail(FENERF_E_INVALID, "differentiable path: points per image must be a multiple of 32");
-  if (P == 0) return FENERF_OK;
-  if (!points || !out || !d_out || !tape || !d_t || !g || !workspace || (m->grid_ch && !tape_e)) return fail(FENERF_E_INVALID, "NULL pointer");
-  if (!g->d_freq_geo || !g->d_phase_geo || !g->d_freq_app || !g->d_phase_app) return fail(FENERF_E_INVALID, "grads: film pointer is NULL");
-  // all weight / bias pointers NULL = FiLM gradients only (inversion); otherwise every one of them is required
-  int have = 0, want = 0;
-  for (int i = 0; i < m->n_geo; ++i) { want += 2; have += (g->geo_w[i] != nullptr) + (g->geo_b[i] != nullptr); }
-  for (int i = 0; i < m->n_color; ++i) { want += 2; have += (g->color_w[i] != nullptr) + (g->color_b[i] != nullptr); }
-  want += 4; have += (g->head_w != nullptr) + (g->head_b != nullptr) + (g->rgb_w != nullptr) + (g->rgb_b != nullptr);
-  if (have != 0 && have != want) return fail(FENERF_E_INVALID, "grads: give every weight / bias buffer or none (FiLM gradients only)");
-  const bool film_only = have == 0;
+  bool empty, film_only;
+  int rc = diff_preamble(m, tape_format, B, P, false, false,
+                         points && out && d_out && tape && d_t && g && workspace && !(m && m->grid_ch && !tape_e), "NULL pointer", &empty);
+  if (rc || empty) return rc;
+  if ((rc = check_grads(m, g, false, &film_only))) return rc;
   if (film_only && tape_format != FENERF_TAPE_F32)
     return fail(FENERF_E_INVALID, "FiLM-only gradients need FENERF_TAPE_F32 (the chain kernel's second FiLM sum)");
-  int rc = check_dump(m, d_t, (long long)B * P);
-  if (rc) return rc;
+  if ((rc = check_dump(m, d_t, (long long)B * P))) return rc;
   const float *fp, *pp;
   rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
@@ -1000,12 +1003,9 @@ extern "C" int fenerf_siren_param_grads_fmt(const FenerfModel* m, int B, int64_t
 extern "C" int fenerf_siren_input_grads(const FenerfModel* m, int B, int64_t P, const float* points, const float* freq_geo, const float* phase_geo,
                                         const float* freq_app, const float* phase_app, const float* d_t, const float* w_geo0,
                                         const float* w_color0, int w_color0_ld, float* d_points, float* d_dirs, void* film_ws, void* stream) {
-  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
-  if (!m->differentiable) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
-  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
-  if (P % 32) return fail(FENERF_E_INVALID, "differentiable path: points per image must be a multiple of 32");
-  if (P == 0) return FENERF_OK;
-  if (!d_t || !w_geo0 || !w_color0) return fail(FENERF_E_INVALID, "d_t / w_geo0 / w_color0 is NULL");
+  bool empty;
+  int rc = diff_preamble(m, FENERF_TAPE_F32, B, P, false, false, d_t && w_geo0 && w_color0, "d_t / w_geo0 / w_color0 is NULL", &empty);
+  if (rc || empty) return rc;
   if (!d_points && !d_dirs) return fail(FENERF_E_INVALID, "d_points and d_dirs are both NULL");
   if (m->grid_ch != 0 && m->grid_ch != 32) return fail(FENERF_E_UNSUPPORTED, "fenerf_siren_input_grads: feature grids of 32 channels only");
   if (m->grid_ch && d_points && !points) return fail(FENERF_E_INVALID, "points is NULL (the grid's coordinate gradient needs the sample positions)");
@@ -1013,8 +1013,7 @@ extern "C" int fenerf_siren_input_grads(const FenerfModel* m, int B, int64_t P, 
   if (B > 65535) return fail(FENERF_E_UNSUPPORTED, "fenerf_siren_input_grads: at most 65535 images per call (one grid row per image)");
   if (use_bf16_dump(m, (long long)B * P))
     return fail(FENERF_E_UNSUPPORTED, "fenerf_siren_input_grads reads the fp32 d(theta) dump; this chunk's dump is bf16 (wgrad_bf16_min_points)");
-  int rc = check_dump(m, d_t, (long long)B * P);
-  if (rc) return rc;
+  if ((rc = check_dump(m, d_t, (long long)B * P))) return rc;
   const float *fp, *pp;
   rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc) return rc;
@@ -1033,14 +1032,12 @@ extern "C" int fenerf_siren_input_grads(const FenerfModel* m, int B, int64_t P, 
 static int pointwise_prep(const FenerfModel* m, int B, int64_t P, const float* fg, const float* pg, const float* fa, const float* pa, void* film_ws,
                           const float** fp, const float** pp, void* stream, int prepared = 0) {
   if (m->precision != FENERF_PREC_F32) return fail(FENERF_E_UNSUPPORTED, "differentiable per-point FiLM parameters: FENERF_PREC_F32 models only");
-  if (!m->differentiable || !m->d_bwd_stream) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
-  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
-  if (P % 32) return fail(FENERF_E_INVALID, "differentiable path: points per image must be a multiple of 32");
-  if (!fg || !pg || !fa || !pa || !film_ws) return fail(FENERF_E_INVALID, "film parameter / workspace pointer is NULL");
+  bool empty;
+  if (int rc = diff_preamble(m, FENERF_TAPE_F32, B, P, true, true, fg && pg && fa && pa && film_ws, "film parameter / workspace pointer is NULL", &empty)) return rc;
   float* f = (float*)film_ws;
   float* q = f + (size_t)B * (size_t)P * m->L * m->H;
   *fp = f; *pp = q;
-  if (P == 0 || prepared) return FENERF_OK;     // prepared: film_ws still holds the blocks an earlier call of this family wrote for the same arguments
+  if (empty || prepared) return FENERF_OK;      // prepared: film_ws still holds the blocks an earlier call of this family wrote for the same arguments
   PhaseScope ph(PH_FILM_PREP, stream);
   return launch_film_prep(m, (long long)B * P, fg, pg, fa, pa, f, q, stream, true);
 }
@@ -1054,14 +1051,9 @@ extern "C" int fenerf_siren_forward_save_pointwise(const FenerfModel* m, int B, 
   int rc = pointwise_prep(m, B, P, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream);
   if (rc || P == 0) return rc;
   if (!points || !out || !tape) return fail(FENERF_E_INVALID, "points / out / tape is NULL");
-  SirenParams sp;
-  fill_common(m, sp, fp, pp);
-  sp.points = points; sp.pdirs = ray_dirs;
-  sp.P = (long long)B * P; sp.pts_per_image = P; sp.n_per_ray = 1;
-  sp.out = out; sp.tape = tape; sp.tape_format = FENERF_TAPE_F32;
-  sp.film_per_point = 1;
-  PhaseScope ph(PH_SIREN, stream);
-  return launch_siren_f32(m, sp, stream);
+  SirenParams sp = point_params(m, fp, pp, B, P, points, ray_dirs, out);
+  sp.tape = tape; sp.tape_format = FENERF_TAPE_F32;
+  return run_siren_pointwise(m, sp, stream);
 }
 
 extern "C" int fenerf_siren_backward_pointwise(const FenerfModel* m, int B, int64_t P, const float* freq_geo, const float* phase_geo,
@@ -1073,18 +1065,10 @@ extern "C" int fenerf_siren_backward_pointwise(const FenerfModel* m, int B, int6
   int rc = pointwise_prep(m, B, P, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream, film_ws_prepared);
   if (rc || P == 0) return rc;
   if (!out || !d_out || !tape || !d_t) return fail(FENERF_E_INVALID, "NULL pointer");
-  SirenBwdParams bp;
-  memset(&bp, 0, sizeof(bp));
-  bp.stream = m->d_bwd_stream;
-  bp.ring_offset_floats = (long long)m->bsh.ht_entries * 256;
-  bp.fp = fp; bp.pp = pp;
-  bp.P = (long long)B * P; bp.pts_per_image = P;
-  bp.out = out; bp.d_out = d_out; bp.tape = tape; bp.tape_format = FENERF_TAPE_F32; bp.d_t = d_t; bp.d_e = nullptr;
-  bp.film_tiles = d_t + (size_t)m->L * m->H * (size_t)B * (size_t)P;    // (written, not used: the sums mix points of different frequencies)
+  SirenBwdParams bp = chain_params(m, fp, pp, B, P, out, d_out, tape, FENERF_TAPE_F32);
+  chain_dump_to(m, bp, d_t);      // (the FiLM sums behind it are written, not used: they mix points of different frequencies)
   bp.film_per_point = 1;
-  note_dump(m, d_t, (long long)B * P);
-  PhaseScope ph(PH_CHAIN, stream);
-  return launch_siren_backward(m, bp, stream);
+  return run_chain(m, bp, stream);
 }
 
 extern "C" int fenerf_siren_param_grads_pointwise(const FenerfModel* m, int B, int64_t P, const float* points, const float* ray_dirs,
@@ -1098,12 +1082,9 @@ extern "C" int fenerf_siren_param_grads_pointwise(const FenerfModel* m, int B, i
   int rc = pointwise_prep(m, B, P, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &pp, stream, film_ws_prepared);
   if (rc || P == 0) return rc;
   if (!points || !out || !d_out || !tape || !d_t || !g || !workspace) return fail(FENERF_E_INVALID, "NULL pointer");
-  if (!g->d_freq_geo || !g->d_phase_geo || !g->d_freq_app || !g->d_phase_app) return fail(FENERF_E_INVALID, "grads: film pointer is NULL");
-  for (int i = 0; i < m->n_geo; ++i) if (!g->geo_w[i] || !g->geo_b[i]) return fail(FENERF_E_INVALID, "grads: every weight / bias buffer is required");
-  for (int i = 0; i < m->n_color; ++i) if (!g->color_w[i] || !g->color_b[i]) return fail(FENERF_E_INVALID, "grads: every weight / bias buffer is required");
-  if (!g->head_w || !g->head_b || !g->rgb_w || !g->rgb_b) return fail(FENERF_E_INVALID, "grads: every weight / bias buffer is required");
-  rc = check_dump(m, d_t, (long long)B * P);
-  if (rc) return rc;
+  bool film_only;
+  if ((rc = check_grads(m, g, true, &film_only))) return rc;
+  if ((rc = check_dump(m, d_t, (long long)B * P))) return rc;
   return launch_param_grads(m, B, P, points, ray_dirs, fp, pp, out, d_out, tape, nullptr, d_t, *g, false, workspace, stream, nullptr, FENERF_TAPE_F32, nullptr, 1);
 }
 
@@ -1284,11 +1265,7 @@ extern "C" int fenerf_render_forward(const FenerfModel* m, int B, int R, int N, 
   float* coarse = (float*)(base + ws.coarse);
   const long long BR = (long long)B * R;
 
-  SirenParams sp;
-  fill_common(m, sp, fp, pp);
-  sp.origins = origins; sp.dirs = dirs; sp.n_per_ray = N; sp.lock_view = lock_view;
-  sp.P = BR * N; sp.pts_per_image = (long long)R * N;
-  sp.z = z_coarse; sp.out = coarse;
+  SirenParams sp = ray_params(m, fp, pp, B, R, N, origins, dirs, z_coarse, lock_view, coarse);
   sp.raw_fg = freq_geo; sp.raw_pg = phase_geo; sp.raw_fa = freq_app; sp.raw_pa = phase_app;
   sp.film_bias = m->d_consts + CONST_FILM_BIAS;
   sp.film_inv_scale = m->precision == FENERF_PREC_F16X3 ? m->d_consts + CONST_FILM_BIAS + (size_t)m->L * m->H : nullptr;
@@ -1431,54 +1408,65 @@ long long backward_max_points(const FenerfModel* m, long long Pp, bool film16, l
   return (long long)cap;
 }
 
-struct BackwardWs {
-  size_t d_out2, d_fc, dump, dump_stride, d_grid_cl, d_e, det, wgrad, film2, scratch, total;      // dump_stride: bytes of one chunk's dump (split backward: several slots)
-  size_t d_pts2, d_rd2;                   // ray gradients (fenerf_render_backward_rays): per-sample d points / d view directions, [2B][Pp][3] each
+// ---- the plan of one render backward: its chunks, the route every gradient takes and where each workspace region begins.  The
+// *_workspace_bytes entries return `total`, the backward carves its pointers and walks its loop from the same object.
+// ray_mode: 0 = no ray gradients, 1 = with per-sample view-direction gradients, 2 = the view is locked (d points only)
+struct BackwardPlan {
+  long long P, Pp;
+  std::vector<Chunk> chunks;
+  bool film16;       // FiLM-only step of an f16x3 model: the chain writes its FiLM sums where the dump would be, and no dump
+  bool det;          // deterministic grid gradient: d_e holds d(grid features) of EVERY row ([2B][Pp][32]), reduced once into `det_ws`
+  bool grid_cl;      // else, with a grid and weight gradients: a channels-last gradient grid that ...
+  bool scatters;     // ... the chain scatters into itself, or that a launch per chunk scatters the chunk's d_e into
+  bool has_d_e;      // (d_e of one chunk's rows unless det; an exact-fp32 chain writes it on a FiLM-only step too)
   long long max_chunk_points, film_row;   // film_row = floats of one image's four FiLM gradient rows
   int max_nb;
+  // regions, in this order (an empty one begins where the next one does); dump = `dump_stride` bytes per slot
+  size_t d_out2, d_fc, dump, d_grid_cl, d_e, det_ws, wgrad, film2, scratch, d_pts2, d_rd2, total;
+  size_t dump_stride;
 };
-// rays: 0 = no ray gradients, 1 = with per-sample view-direction gradients, 2 = the view is locked (d points only)
-BackwardWs backward_ws(const FenerfModel* m, int B, int R, int N, int film_only, long long chunk_points, long long film_budget, int dump_slots = 1,
-                       int rays = 0) {
-  BackwardWs w;
-  const long long P = (long long)R * N, Pp = (P + 31) / 32 * 32;
-  const bool film16 = film_only && m->precision == FENERF_PREC_F16X3 && !rays;      // (the input gradients are read from the dump)
-  const std::vector<Chunk> chunks = plan_chunks(2 * B, Pp, backward_max_points(m, Pp, film16, chunk_points, film_budget));
-  w.max_chunk_points = 0; w.max_nb = 0;
+BackwardPlan backward_plan(const FenerfModel* m, int B, int R, int N, int film_only, long long chunk_points, long long film_budget, int dump_slots,
+                           int ray_mode) {
+  BackwardPlan p;
+  p.P = (long long)R * N; p.Pp = (p.P + 31) / 32 * 32;
+  const size_t P = (size_t)p.P, Pp = (size_t)p.Pp;
+  // (with ray gradients a FiLM-only step takes the dumping chain too: the input-gradient pass reads the dump)
+  p.film16 = film_only && m->precision == FENERF_PREC_F16X3 && !ray_mode;
+  p.chunks = plan_chunks(2 * B, p.Pp, backward_max_points(m, p.Pp, p.film16, chunk_points, film_budget));
+  p.det = grid_det(m) && !film_only;
+  p.grid_cl = m->grid_ch && !film_only && !p.det;
+  p.scatters = p.grid_cl && chain_scatters(m);
+  p.has_d_e = p.det || (m->grid_ch && !chain_scatters(m));
+  p.max_chunk_points = 0; p.max_nb = 0;
   size_t wg = 0, sums = 0;
-  for (const Chunk& c : chunks) {
-    if ((long long)c.nb * c.n > w.max_chunk_points) w.max_chunk_points = (long long)c.nb * c.n;
-    if (c.nb > w.max_nb) w.max_nb = c.nb;
+  for (const Chunk& c : p.chunks) {
+    if ((long long)c.nb * c.n > p.max_chunk_points) p.max_chunk_points = (long long)c.nb * c.n;
+    if (c.nb > p.max_nb) p.max_nb = c.nb;
     const size_t b = wgrad_workspace_bytes(m, c.nb, c.n);
     if (b > wg) wg = b;
     const size_t f = fenerf_siren_film_sums_floats(m, c.nb, c.n) * sizeof(float);
     if (f > sums) sums = f;
   }
+  const size_t n_chunks = p.chunks.size(), slots = dump_slots < 1 ? 1 : ((size_t)dump_slots > n_chunks ? n_chunks : (size_t)dump_slots);
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
-  w.d_out2 = take((size_t)2 * B * Pp * m->C * sizeof(float));
-  w.d_fc = take(Pp != P ? (size_t)2 * B * P * m->C * sizeof(float) : 0);
-  w.dump_stride = align_up(film16 ? sums : fenerf_siren_dtheta_floats(m, w.max_chunk_points) * sizeof(float), 256);
-  {
-    const size_t slots = (size_t)(dump_slots < 1 ? 1 : (dump_slots > (int)chunks.size() ? (int)chunks.size() : dump_slots));
-    w.dump = take(w.dump_stride * (slots < 1 ? 1 : slots));
-  }
-  // deterministic grid gradient: d(grid features) of every row of both passes, reduced once into the int64 grid of `det`
-  const bool det = grid_det(m) && !film_only;
-  w.d_grid_cl = take(m->grid_ch && !film_only && !det ? (size_t)m->gd * m->gh * m->gw * 32 * sizeof(float) : 0);
-  w.d_e = take(det ? (size_t)2 * B * Pp * 32 * sizeof(float)
-                   : (m->grid_ch && !chain_scatters(m) ? (size_t)w.max_chunk_points * 32 * sizeof(float) : 0));
-  w.det = take(det ? grid_det_workspace_bytes(m) : 0);
-  w.wgrad = take(align_up(wg, 256));
-  w.film_row = (long long)2 * (m->n_geo + m->n_color) * m->H;
-  w.film2 = take((size_t)2 * B * w.film_row * sizeof(float));
+  p.d_out2 = take((size_t)2 * B * Pp * m->C * sizeof(float));
+  p.d_fc = take(Pp != P ? (size_t)2 * B * P * m->C * sizeof(float) : 0);
+  p.dump_stride = align_up(p.film16 ? sums : fenerf_siren_dtheta_floats(m, p.max_chunk_points) * sizeof(float), 256);
+  p.dump = take(p.dump_stride * (slots < 1 ? 1 : slots));
+  p.d_grid_cl = take(p.grid_cl ? (size_t)m->gd * m->gh * m->gw * 32 * sizeof(float) : 0);
+  p.d_e = take(!p.has_d_e ? 0 : (p.det ? (size_t)2 * B * Pp : (size_t)p.max_chunk_points) * 32 * sizeof(float));
+  p.det_ws = take(p.det ? grid_det_workspace_bytes(m) : 0);
+  p.wgrad = take(align_up(wg, 256));
+  p.film_row = (long long)2 * (m->n_geo + m->n_color) * m->H;
+  p.film2 = take((size_t)2 * B * p.film_row * sizeof(float));
   // a later chunk's gradients before they are added to the first one's: every weight tensor + the FiLM rows of the chunk's images
-  w.scratch = take(chunks.size() > 1 ? ((size_t)(film_only ? 0 : grad_sizes(m).total) + (size_t)w.max_nb * w.film_row) * sizeof(float) : 0);
+  p.scratch = take(n_chunks > 1 ? ((size_t)(film_only ? 0 : grad_sizes(m).total) + (size_t)p.max_nb * p.film_row) * sizeof(float) : 0);
   // (behind everything else: the layout of a backward without ray gradients is what it was)
-  w.d_pts2 = take(rays ? (size_t)2 * B * Pp * 3 * sizeof(float) : 0);
-  w.d_rd2 = take(rays == 1 ? (size_t)2 * B * Pp * 3 * sizeof(float) : 0);
-  w.total = off;
-  return w;
+  p.d_pts2 = take(ray_mode ? (size_t)2 * B * Pp * 3 * sizeof(float) : 0);
+  p.d_rd2 = take(ray_mode == 1 ? (size_t)2 * B * Pp * 3 * sizeof(float) : 0);
+  p.total = off;
+  return p;
 }
 }  // namespace
 
@@ -1518,11 +1506,8 @@ extern "C" int fenerf_render_forward_save(const FenerfModel* m, int B, int R, in
   { PhaseScope ph(PH_FILM_PREP, stream); if ((rc = launch_film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, fp2, pp2, stream, false, true))) return rc; }
   // ---- coarse pass (generators.py:468-479)
   { PhaseScope ph(PH_OTHER, stream); if ((rc = launch_render_points(B, R, N, Pp, origins, dirs, z_coarse, pts2, rd, stream))) return rc; }
-  SirenParams sp;
-  fill_common(m, sp, fp2, pp2);
-  sp.points = pts2; sp.pdirs = rd;
-  sp.P = (long long)B * Pp; sp.pts_per_image = Pp; sp.n_per_ray = 1;
-  sp.out = out2; sp.tape = (float*)tape2; sp.tape_e = tape_e2; sp.tape_format = tape_format;
+  SirenParams sp = point_params(m, fp2, pp2, B, Pp, pts2, rd, out2);
+  sp.tape = (float*)tape2; sp.tape_e = tape_e2; sp.tape_format = tape_format;
   if ((rc = run_siren(m, sp, stream))) return rc;
   const float* coarse = out2;
   const float* fine = out2 + (size_t)B * Pp * C;
@@ -1564,229 +1549,276 @@ extern "C" int fenerf_render_forward_save(const FenerfModel* m, int B, int R, in
 extern "C" size_t fenerf_render_backward_workspace_bytes(const FenerfModel* m, int B, int R, int N, int film_only, int64_t chunk_points,
                                                          int64_t film_sums_budget_bytes) {
   if (!m || B <= 0 || R <= 0 || N <= 0) return 0;
-  return backward_ws(m, B, R, N, film_only, chunk_points, film_sums_budget_bytes).total;
+  return backward_plan(m, B, R, N, film_only, chunk_points, film_sums_budget_bytes, 1, 0).total;
 }
 
+namespace {
 // what fenerf_render_backward_rays asks for beside fenerf_render_backward's gradients (stage 0 only)
 struct RayGrads { const float* w_geo0; const float* w_color0; int w_color0_ld; float* d_origins; float* d_dirs; };
 
-// stage 0: the whole backward in one call (fenerf_render_backward).  stage 1 / 2: the same launches cut in two (fenerf_render_backward_stage):
-// 1 = composite backward, chain AND weight gradients of every chunk but the last `keep_chunks`, the chains of those last chunks -- each
-// into its own dump slot -- and the finished grid gradient; 2 = the weight gradients of the last chunks, the sums, the FiLM fold.  Same
-// kernels on the same chunks in the same order per gradient tensor: stage 1 + stage 2 = stage 0 bit for bit (atomics of the grid aside).
-static int render_backward_impl(const FenerfModel* m, int B, int R, int N, int lock_view, const void* save, size_t save_bytes,
-                                int tape_format, const float* z_coarse, const float* noise_final, const FenerfCompositeOpts* opts,
-                                const float* g_rgb, const FenerfSirenGrads* grads, float* d_grid_ncdhw, const FenerfSirenGrads* weights,
-                                int64_t chunk_points, int64_t film_sums_budget_bytes, void* workspace, size_t workspace_bytes,
-                                void* stream, int keep_chunks, int stage, const RayGrads* rays = nullptr, const float* g_depth = nullptr) {
+// One render backward: the call's arguments, in the entries' order, then what bwd_validate derives from them.
+// stage 0: the whole backward in one call (fenerf_render_backward).  stage 1 / 2: the same launches cut in two (fenerf_render_backward_stage),
+// see bwd_runs.  Same kernels on the same chunks in the same order per gradient tensor: stage 1 + stage 2 = stage 0 bit for bit (atomics
+// of the grid aside).
+struct RenderBwd {
+  const FenerfModel* m; int B, R, N, lock_view; const void* save; size_t save_bytes; int tape_format; const float* z_coarse; const float* noise_final;
+  const FenerfCompositeOpts* opts; const float* g_rgb; const FenerfSirenGrads* grads; float* d_grid_ncdhw; const FenerfSirenGrads* weights;
+  int64_t chunk_points, film_sums_budget_bytes; void* workspace; size_t workspace_bytes; void* stream;
+  int keep_chunks, stage; const RayGrads* rays; const float* g_depth;
+  // ---- derived
+  bool film_only;
+  RenderSave sv;
+  BackwardPlan plan;
+  const char* sb; char* wb;                                    // save / workspace as bytes
+  const float *fp2, *pp2, *pts2, *rd, *out2, *tape_e2, *zf;    // the forward's save block (pass-major: coarse | fine)
+  const char* tape2;
+  float *d_out2, *d_pts2, *d_rd2, *d_grid_cl, *d_e;
+  float* f2[4]; long long frow[4];      // FiLM gradient rows of all 2B (pass, image) pairs: [d_freq_geo | d_phase_geo: nB x ng H each][d_freq_app | d_phase_app: nB x nc H each]
+  GradSizes gz;
+  int n_early;                          // chunks [n_early, n) are the late ones of a two-stage backward: each chain into its own dump slot
+  bool first;                           // does the next weight-gradient call write the output buffers (or a scratch set that is then added)?
+};
+
+// ---- which steps a stage runs.  1 = composite backward, chain AND weight gradients of every chunk but the last `keep_chunks`, the chains of
+// those last chunks and the finished grid gradient; 2 = the weight gradients of the last chunks, the sums, the FiLM fold.
+enum BwdStep { BWD_COMPOSITE, BWD_CHAIN, BWD_WGRAD, BWD_GRID_FINISH, BWD_FILM_FOLD };
+bool bwd_runs(const RenderBwd& c, BwdStep step, int chunk = 0) {
+  const bool late = chunk >= c.n_early;
+  switch (step) {
+    case BWD_WGRAD: return c.stage == 0 || (c.stage == 1 && !late) || (c.stage == 2 && late);
+    case BWD_FILM_FOLD: return c.stage != 1;
+    default: return c.stage != 2;
+  }
+}
+
+int bwd_validate(RenderBwd& c) {
+  const FenerfModel* m = c.m;
   if (!m) return fail(FENERF_E_INVALID, "model is NULL");
   if (!m->differentiable || !m->d_bwd_stream) return fail(FENERF_E_UNSUPPORTED, "model was not created with differentiable != 0");
-  int rc = check_opts(opts);
+  int rc = check_opts(c.opts);
   if (rc) return rc;
-  if ((rc = check_tape_format(m, tape_format))) return rc;
-  if (B <= 0 || R <= 0 || N < 3 || 2 * N > FENERF_MAX_RAY_SAMPLES) return fail(FENERF_E_INVALID, "need B, R > 0 and 3 <= num_steps <= 512 (hierarchical render; FENERF_MAX_RAY_SAMPLES / 2)");
-  if (!save || !grads || !workspace || (stage != 2 && (!z_coarse || (!g_rgb && !g_depth)))) return fail(FENERF_E_INVALID, "NULL pointer");
-  if (!grads->d_freq_geo || !grads->d_phase_geo || !grads->d_freq_app || !grads->d_phase_app) return fail(FENERF_E_INVALID, "grads: film pointer is NULL");
-  int have = 0, want = 0;
-  for (int i = 0; i < m->n_geo; ++i) { want += 2; have += (grads->geo_w[i] != nullptr) + (grads->geo_b[i] != nullptr); }
-  for (int i = 0; i < m->n_color; ++i) { want += 2; have += (grads->color_w[i] != nullptr) + (grads->color_b[i] != nullptr); }
-  want += 4; have += (grads->head_w != nullptr) + (grads->head_b != nullptr) + (grads->rgb_w != nullptr) + (grads->rgb_b != nullptr);
-  if (have != 0 && have != want) return fail(FENERF_E_INVALID, "grads: give every weight / bias buffer or none (FiLM gradients only)");
-  const bool film_only = have == 0;
-  if (stage != 0 && (film_only || keep_chunks < 1)) return fail(FENERF_E_INVALID, "the two-stage backward takes weight gradients and keeps at least one chunk");
-  if (film_only && tape_format != FENERF_TAPE_F32) return fail(FENERF_E_INVALID, "FiLM-only gradients need FENERF_TAPE_F32 (the chain kernel's second FiLM sum)");
-  if (tape_format != FENERF_TAPE_F32 && !weights) return fail(FENERF_E_INVALID, "FENERF_TAPE_U16 / _F32_W: the FiLM layers' weights are required");
-  if (!film_only && m->grid_ch && !d_grid_ncdhw && stage != 2) return fail(FENERF_E_INVALID, "d_grid_ncdhw is NULL");
-  const RenderSave sv = render_save(m, B, R, N, tape_format, lock_view);
-  if (save_bytes < sv.total) return fail(FENERF_E_INVALID, "save buffer too small (see fenerf_render_save_bytes)");
-  const int ray_mode = rays ? (lock_view ? 2 : 1) : 0;
-  const BackwardWs wsz = backward_ws(m, B, R, N, film_only, chunk_points, film_sums_budget_bytes, stage == 0 ? 1 : keep_chunks, ray_mode);
-  if (workspace_bytes < wsz.total)
-    return fail(FENERF_E_INVALID, rays ? "workspace too small (see fenerf_render_backward_rays_workspace_bytes)"
-                                       : "workspace too small (see fenerf_render_backward_workspace_bytes / _split_workspace_bytes)");
-  if (rays) {       // refusals before the first launch
-    const std::vector<Chunk> chunks = plan_chunks(2 * B, sv.Pp, backward_max_points(m, sv.Pp, false, chunk_points, 0));
+  if ((rc = check_tape_format(m, c.tape_format))) return rc;
+  if (c.B <= 0 || c.R <= 0 || c.N < 3 || 2 * c.N > FENERF_MAX_RAY_SAMPLES) return fail(FENERF_E_INVALID, "need B, R > 0 and 3 <= num_steps <= 512 (hierarchical render; FENERF_MAX_RAY_SAMPLES / 2)");
+  if (!c.save || !c.grads || !c.workspace || (c.stage != 2 && (!c.z_coarse || (!c.g_rgb && !c.g_depth)))) return fail(FENERF_E_INVALID, "NULL pointer");
+  if ((rc = check_grads(m, c.grads, false, &c.film_only))) return rc;
+  if (c.stage != 0 && (c.film_only || c.keep_chunks < 1)) return fail(FENERF_E_INVALID, "the two-stage backward takes weight gradients and keeps at least one chunk");
+  if (c.film_only && c.tape_format != FENERF_TAPE_F32) return fail(FENERF_E_INVALID, "FiLM-only gradients need FENERF_TAPE_F32 (the chain kernel's second FiLM sum)");
+  if (c.tape_format != FENERF_TAPE_F32 && !c.weights) return fail(FENERF_E_INVALID, "FENERF_TAPE_U16 / _F32_W: the FiLM layers' weights are required");
+  if (!c.film_only && m->grid_ch && !c.d_grid_ncdhw && c.stage != 2) return fail(FENERF_E_INVALID, "d_grid_ncdhw is NULL");
+  c.sv = render_save(m, c.B, c.R, c.N, c.tape_format, c.lock_view);
+  if (c.save_bytes < c.sv.total) return fail(FENERF_E_INVALID, "save buffer too small (see fenerf_render_save_bytes)");
+  c.plan = backward_plan(m, c.B, c.R, c.N, c.film_only, c.chunk_points, c.film_sums_budget_bytes, c.stage == 0 ? 1 : c.keep_chunks,
+                         c.rays ? (c.lock_view ? 2 : 1) : 0);
+  const BackwardPlan& pl = c.plan;
+  if (c.workspace_bytes < pl.total)
+    return fail(FENERF_E_INVALID, c.rays ? "workspace too small (see fenerf_render_backward_rays_workspace_bytes)"
+                                         : "workspace too small (see fenerf_render_backward_workspace_bytes / _split_workspace_bytes)");
+  if (c.rays) {       // refusals before the first launch
     if (m->grid_ch != 0 && m->grid_ch != 32) return fail(FENERF_E_UNSUPPORTED, "fenerf_render_backward_rays: feature grids of 32 channels only");
-    for (const Chunk& c : chunks) {
-      if (c.nb > 65535) return fail(FENERF_E_UNSUPPORTED, "fenerf_render_backward_rays: at most 65535 images per backward chunk (lower chunk_points)");
-      if (use_bf16_dump(m, (long long)c.nb * c.n))
+    for (const Chunk& k : pl.chunks) {
+      if (k.nb > 65535) return fail(FENERF_E_UNSUPPORTED, "fenerf_render_backward_rays: at most 65535 images per backward chunk (lower chunk_points)");
+      if (use_bf16_dump(m, (long long)k.nb * k.n))
         return fail(FENERF_E_UNSUPPORTED, "fenerf_render_backward_rays: the input-gradient pass reads the fp32 d(theta) dump; a backward chunk of this "
                                           "model writes the bf16 dump (wgrad_bf16_min_points: AMP-class gradients)");
     }
   }
-  const char* sb = (const char*)save;
-  char* wb = (char*)workspace;
-  hipStream_t st = (hipStream_t)stream;
-  const long long P = sv.P, Pp = sv.Pp, BR = (long long)B * R;
-  const int C = m->C, H = m->H, L = m->L, ng = m->n_geo, nc = m->n_color, nB = 2 * B;
-  const float* fp2 = (const float*)(sb + sv.fp2);
-  const float* pp2 = (const float*)(sb + sv.pp2);
-  const float* pts2 = (const float*)(sb + sv.pts2);
-  const float* rd = lock_view ? nullptr : (const float*)(sb + sv.rd);
-  const float* out2 = (const float*)(sb + sv.out2);
-  const char* tape2 = sb + sv.tape2;
-  const float* tape_e2 = m->grid_ch ? (const float*)(sb + sv.tape_e2) : nullptr;
-  const float* zf = (const float*)(sb + sv.zf);
-  float* d_out2 = (float*)(wb + wsz.d_out2);
-  // ---- composite backward: the gradient wrt the two passes' rows, written where the chain reads it (coarse | fine halves, pass-major)
-  if (stage != 2) {
-    CompositeParams cp;
-    memset(&cp, 0, sizeof(cp));
-    cp.BR = BR; cp.M = 2 * N; cp.C = C; cp.N = N;
-    cp.rows_a = Pp == P ? out2 + (size_t)B * Pp * C : (const float*)(sb + sv.rows_f);
-    cp.rows_b = Pp == P ? out2 : (const float*)(sb + sv.rows_c);
-    cp.z_a = zf; cp.z_b = z_coarse; cp.noise = noise_final; cp.o = *opts;
-    cp.g_rgb = g_rgb;
-    float* d_f = Pp == P ? d_out2 + (size_t)B * Pp * C : (float*)(wb + wsz.d_fc);
-    float* d_c = Pp == P ? d_out2 : (float*)(wb + wsz.d_fc) + (size_t)B * P * C;
-    cp.d_rows_a = d_f; cp.d_rows_b = d_c;
-    {         // a depth gradient (fenerf_render_backward_outputs) takes the kernel variant; without one, the launch this always was
-      PhaseScope ph(PH_COMPOSITE_BWD, stream);
-      if ((rc = g_depth ? launch_composite_backward_outputs(cp, CompositeOutGrads{g_depth, nullptr, nullptr}, true, stream)
-                        : launch_composite_backward(cp, true, stream)))
-        return rc;
-    }
-    if (Pp != P) {
-      PhaseScope ph(PH_OTHER, stream);
-      if ((rc = launch_pad_rows(d_c, d_out2, B, P, Pp, C, true, stream))) return rc;
-      if ((rc = launch_pad_rows(d_f, d_out2 + (size_t)B * Pp * C, B, P, Pp, C, true, stream))) return rc;
-    }
+  const RenderSave& sv = c.sv;
+  const int H = m->H, ng = m->n_geo, nc = m->n_color, nB = 2 * c.B;
+  c.sb = (const char*)c.save; c.wb = (char*)c.workspace;
+  c.fp2 = (const float*)(c.sb + sv.fp2);
+  c.pp2 = (const float*)(c.sb + sv.pp2);
+  c.pts2 = (const float*)(c.sb + sv.pts2);
+  c.rd = c.lock_view ? nullptr : (const float*)(c.sb + sv.rd);
+  c.out2 = (const float*)(c.sb + sv.out2);
+  c.tape2 = c.sb + sv.tape2;
+  c.tape_e2 = m->grid_ch ? (const float*)(c.sb + sv.tape_e2) : nullptr;
+  c.zf = (const float*)(c.sb + sv.zf);
+  c.d_out2 = (float*)(c.wb + pl.d_out2);
+  c.d_pts2 = c.rays ? (float*)(c.wb + pl.d_pts2) : nullptr;
+  c.d_rd2 = (c.rays && !c.lock_view && c.rays->d_dirs) ? (float*)(c.wb + pl.d_rd2) : nullptr;
+  c.d_grid_cl = pl.grid_cl ? (float*)(c.wb + pl.d_grid_cl) : nullptr;
+  c.d_e = pl.has_d_e ? (float*)(c.wb + pl.d_e) : nullptr;
+  float* film2 = (float*)(c.wb + pl.film2);
+  c.f2[0] = film2; c.f2[1] = film2 + (size_t)nB * ng * H; c.f2[2] = film2 + (size_t)2 * nB * ng * H; c.f2[3] = c.f2[2] + (size_t)nB * nc * H;
+  c.frow[0] = c.frow[1] = (long long)ng * H; c.frow[2] = c.frow[3] = (long long)nc * H;
+  c.gz = grad_sizes(m);
+  const int n_chunks = (int)pl.chunks.size();
+  c.n_early = n_chunks - (c.stage == 0 ? 0 : (c.keep_chunks < n_chunks ? c.keep_chunks : n_chunks));
+  c.first = c.stage != 2 || c.n_early == 0;
+  return FENERF_OK;
+}
+
+// the gradient wrt the two passes' rows, written where the chain reads it (coarse | fine halves, pass-major), then the grid gradient cleared
+int bwd_composite(const RenderBwd& c) {
+  const FenerfModel* m = c.m;
+  const long long P = c.sv.P, Pp = c.sv.Pp;
+  const int B = c.B, C = m->C;
+  CompositeParams cp;
+  memset(&cp, 0, sizeof(cp));
+  cp.BR = (long long)B * c.R; cp.M = 2 * c.N; cp.C = C; cp.N = c.N;
+  cp.rows_a = Pp == P ? c.out2 + (size_t)B * Pp * C : (const float*)(c.sb + c.sv.rows_f);
+  cp.rows_b = Pp == P ? c.out2 : (const float*)(c.sb + c.sv.rows_c);
+  cp.z_a = c.zf; cp.z_b = c.z_coarse; cp.noise = c.noise_final; cp.o = *c.opts;
+  cp.g_rgb = c.g_rgb;
+  float* d_f = Pp == P ? c.d_out2 + (size_t)B * Pp * C : (float*)(c.wb + c.plan.d_fc);
+  float* d_c = Pp == P ? c.d_out2 : (float*)(c.wb + c.plan.d_fc) + (size_t)B * P * C;
+  cp.d_rows_a = d_f; cp.d_rows_b = d_c;
+  int rc;
+  {         // a depth gradient (fenerf_render_backward_outputs) takes the kernel variant; without one, the launch this always was
+    PhaseScope ph(PH_COMPOSITE_BWD, c.stream);
+    if ((rc = c.g_depth ? launch_composite_backward_outputs(cp, CompositeOutGrads{c.g_depth, nullptr, nullptr}, true, c.stream)
+                        : launch_composite_backward(cp, true, c.stream)))
+      return rc;
   }
-  // ---- chunks of whole (pass, image) pairs -- or point ranges of one -- : chain, then the weight / FiLM gradients of the chunk
-  // (with ray gradients a FiLM-only step takes the dumping chain too: the no-dump chain leaves nothing for the input-gradient pass to read)
-  const bool film16 = film_only && m->precision == FENERF_PREC_F16X3 && !rays;
-  const std::vector<Chunk> chunks = plan_chunks(nB, Pp, backward_max_points(m, Pp, film16, chunk_points, film_sums_budget_bytes));
-  float* const d_pts2 = rays ? (float*)(wb + wsz.d_pts2) : nullptr;
-  float* const d_rd2 = (rays && !lock_view && rays->d_dirs) ? (float*)(wb + wsz.d_rd2) : nullptr;
-  float* const dump0 = (float*)(wb + wsz.dump);
-  const bool det = grid_det(m) && !film_only;          // d_e of every row (pass-major, [2B][Pp][32]), one order-independent reduction
-  float* d_grid_cl = (m->grid_ch && !film_only && !det) ? (float*)(wb + wsz.d_grid_cl) : nullptr;
-  float* d_e = (m->grid_ch && (det || !chain_scatters(m))) ? (float*)(wb + wsz.d_e) : nullptr;
-  if (d_grid_cl && stage != 2) HIP_TRY(hipMemsetAsync(d_grid_cl, 0, (size_t)m->gd * m->gh * m->gw * 32 * sizeof(float), st));
-  float* film2 = (float*)(wb + wsz.film2);      // [d_freq_geo | d_phase_geo: nB x ng H each][d_freq_app | d_phase_app: nB x nc H each]
-  float* f2[4] = {film2, film2 + (size_t)nB * ng * H, film2 + (size_t)2 * nB * ng * H, film2 + (size_t)2 * nB * ng * H + (size_t)nB * nc * H};
-  const long long frow[4] = {(long long)ng * H, (long long)ng * H, (long long)nc * H, (long long)nc * H};
-  const GradSizes gz = grad_sizes(m);
-  const size_t LHw = (size_t)(tape_format == FENERF_TAPE_U16 ? 2 : 4) * L * H;      // tape bytes per point
-  const int n_chunks = (int)chunks.size();
-  const int n_late = stage == 0 ? 0 : (keep_chunks < n_chunks ? keep_chunks : n_chunks), n_early = n_chunks - n_late;
-  bool first = stage != 2 || n_early == 0;      // does the next weight-gradient call write the output buffers (or a scratch set that is then added)?
-  for (int ci = 0; ci < n_chunks; ++ci) {
-    const Chunk& c = chunks[ci];
-    const bool late = ci >= n_early;
-    if (stage == 2 && !late) continue;
-    const bool do_chain = stage != 2, do_wgrad = stage == 0 || (stage == 1 && !late) || (stage == 2 && late);
-    float* const dump = dump0 + (late ? (size_t)(ci - n_early) * (wsz.dump_stride / sizeof(float)) : 0);
-    const long long g0 = (long long)c.b * Pp + c.s, npts = (long long)c.nb * c.n;
-    const float* fp_c = fp2 + (size_t)c.b * L * H;
-    const float* pp_c = pp2 + (size_t)c.b * L * H;
-    const float* out_c = out2 + (size_t)g0 * C;
-    const float* dout_c = d_out2 + (size_t)g0 * C;
-    const float* pts_c = pts2 + (size_t)g0 * 3;
-    const char* tape_c = tape2 + (size_t)g0 * LHw;
-    SirenBwdParams bp;
-    memset(&bp, 0, sizeof(bp));
-    bp.stream = m->d_bwd_stream;
-    bp.ring_offset_floats = (long long)m->bsh.ht_entries * 256;
-    bp.fp = fp_c; bp.pp = pp_c;
-    bp.P = npts; bp.pts_per_image = c.n;
-    bp.out = out_c; bp.d_out = dout_c; bp.tape = (const float*)tape_c; bp.tape_format = tape_format;
-    const float* film_sums = nullptr;
-    if (film16) {
-      bp.d_t = nullptr; bp.d_e = nullptr; bp.film_tiles = dump; film_sums = dump;
-    } else {
-      bp.d_t = dump; bp.film_tiles = dump + (size_t)L * H * (size_t)npts;
-      bp.bf16_dump = use_bf16_dump(m, npts);
-      if (m->grid_ch && !film_only) {
-        if (det) bp.d_e = d_e + (size_t)g0 * 32;
-        else if (chain_scatters(m)) { bp.points = pts_c; bp.d_grid_cl = d_grid_cl; bp.box_scale = m->box_scale; bp.gd = m->gd; bp.gh = m->gh; bp.gw = m->gw; }
-        else bp.d_e = d_e;
-      } else if (m->grid_ch) {
-        bp.d_e = d_e;      // FiLM-only on an exact-fp32 model: the chain still writes d(grid features); nobody reads them
-      }
-    }
-    if (do_chain) {
-      PhaseScope ph(PH_CHAIN, stream);
-      rc = m->precision == FENERF_PREC_F16X3 ? launch_siren_backward16w(m, bp, stream) : launch_siren_backward(m, bp, stream);
-      if (rc) return rc;
-    }
-    if (do_chain && m->grid_ch && !film_only && !det && !chain_scatters(m)) {
-      PhaseScope ph(PH_GRID, stream);
-      if ((rc = launch_grid_backward(m, npts, pts_c, d_e, d_grid_cl, stream))) return rc;
-    }
-    if (rays) {       // this chunk's rows of the per-sample d points / d view directions, from the dump its chain has just left
-      PhaseScope ph(PH_OTHER, stream);
-      if ((rc = launch_siren_input_grads(m, c.nb, c.n, pts_c, fp_c, dump, rays->w_geo0, rays->w_color0, rays->w_color0_ld, d_pts2 + (size_t)g0 * 3,
-                                         d_rd2 ? d_rd2 + (size_t)g0 * 3 : nullptr, stream)))
-        return rc;
-    }
-    if (!do_wgrad) continue;
-    // where this chunk's gradients go: the first chunk writes the outputs, later ones a scratch set that is then added (chunk order:
-    // the sums of rounds 2-4, bit for bit); FiLM rows of an image's first point range are written in place, later ranges added
-    FenerfSirenGrads gc;
-    memset(&gc, 0, sizeof(gc));
-    float* scratch = (float*)(wb + wsz.scratch);
-    float* film_scratch = scratch + (film_only ? 0 : gz.total);
-    const bool film_direct = c.s == 0;
-    float* fdst[4];
-    {
-      size_t o = 0;
-      for (int k = 0; k < 4; ++k) {
-        fdst[k] = film_direct ? f2[k] + (size_t)c.b * frow[k] : film_scratch + o;
-        o += (size_t)c.nb * frow[k];
-      }
-    }
-    if (!film_only) {
-      if (first) gc = *grads;
-      else carve_grads(m, gz, scratch, &gc);
-    }
-    gc.d_freq_geo = fdst[0]; gc.d_phase_geo = fdst[1]; gc.d_freq_app = fdst[2]; gc.d_phase_app = fdst[3];
-    const float* dirs_c = rd ? rd + (size_t)g0 * 3 : nullptr;
-    rc = launch_param_grads(m, c.nb, c.n, pts_c, dirs_c, fp_c, pp_c, out_c, dout_c, (const float*)tape_c, tape_e2 ? tape_e2 + (size_t)g0 * 32 : nullptr,
-                            film16 ? nullptr : dump, gc, film_only, wb + wsz.wgrad, stream, film_sums, tape_format, weights);
-    if (rc) return rc;
-    if (!film_direct || (!first && !film_only)) {
-      MultiAdd J;
-      memset(&J, 0, sizeof(J));
-      int k = 0;
-      auto add = [&](float* dst, const float* src, long long n) { if (dst && src && n > 0) { J.dst[k] = dst; J.src[k] = src; J.n[k] = n; ++k; } };
-      if (!first && !film_only) {
-        for (int i = 0; i < ng; ++i) { add(grads->geo_w[i], gc.geo_w[i], gz.geo_w[i]); add(grads->geo_b[i], gc.geo_b[i], gz.geo_b[i]); }
-        for (int i = 0; i < nc; ++i) { add(grads->color_w[i], gc.color_w[i], gz.color_w[i]); add(grads->color_b[i], gc.color_b[i], gz.color_b[i]); }
-        add(grads->head_w, gc.head_w, gz.head_w); add(grads->head_b, gc.head_b, gz.head_b); add(grads->rgb_w, gc.rgb_w, gz.rgb_w); add(grads->rgb_b, gc.rgb_b, gz.rgb_b);
-      }
-      if (!film_direct)
-        for (int q = 0; q < 4; ++q) add(f2[q] + (size_t)c.b * frow[q], fdst[q], (long long)c.nb * frow[q]);
-      J.count = k;
-      PhaseScope ph(PH_OTHER, stream);
-      if ((rc = launch_multi_add(J, stream))) return rc;
-    }
-    first = false;
+  if (Pp != P) {
+    PhaseScope ph(PH_OTHER, c.stream);
+    if ((rc = launch_pad_rows(d_c, c.d_out2, B, P, Pp, C, true, c.stream))) return rc;
+    if ((rc = launch_pad_rows(d_f, c.d_out2 + (size_t)B * Pp * C, B, P, Pp, C, true, c.stream))) return rc;
   }
-  // ---- the two passes of an image share its FiLM parameters: row b + row B + b
-  if (stage != 1) {
-    FilmFold F;
-    F.B = B;
-    F.out[0] = grads->d_freq_geo; F.out[1] = grads->d_phase_geo; F.out[2] = grads->d_freq_app; F.out[3] = grads->d_phase_app;
-    for (int q = 0; q < 4; ++q) { F.in[q] = f2[q]; F.row[q] = (int)frow[q]; }
-    PhaseScope ph(PH_OTHER, stream);
-    if ((rc = launch_film_fold(F, stream))) return rc;
+  if (c.d_grid_cl) HIP_TRY(hipMemsetAsync(c.d_grid_cl, 0, (size_t)m->gd * m->gh * m->gw * 32 * sizeof(float), (hipStream_t)c.stream));
+  return FENERF_OK;
+}
+
+// a chunk of whole (pass, image) pairs -- or a point range of one --: where its rows begin in every buffer
+struct ChunkRows {
+  Chunk k; long long g0;
+  const float *fp, *pp, *out, *d_out, *pts; const char* tape;
+  float* dump;
+};
+ChunkRows chunk_rows(const RenderBwd& c, int ci) {
+  const FenerfModel* m = c.m;
+  ChunkRows r;
+  r.k = c.plan.chunks[ci];
+  r.g0 = (long long)r.k.b * c.sv.Pp + r.k.s;
+  r.fp = c.fp2 + (size_t)r.k.b * m->L * m->H;
+  r.pp = c.pp2 + (size_t)r.k.b * m->L * m->H;
+  r.out = c.out2 + (size_t)r.g0 * m->C;
+  r.d_out = c.d_out2 + (size_t)r.g0 * m->C;
+  r.pts = c.pts2 + (size_t)r.g0 * 3;
+  r.tape = c.tape2 + (size_t)r.g0 * (c.tape_format == FENERF_TAPE_U16 ? 2 : 4) * m->L * m->H;
+  r.dump = (float*)(c.wb + c.plan.dump) + (ci >= c.n_early ? (size_t)(ci - c.n_early) * (c.plan.dump_stride / sizeof(float)) : 0);
+  return r;
+}
+
+// the chunk's chain, its grid scatter where the chain does not scatter itself, and -- with ray gradients -- its rows of the per-sample
+// d points / d view directions from the dump the chain has just left
+int bwd_chunk_chain(const RenderBwd& c, const ChunkRows& r) {
+  const FenerfModel* m = c.m;
+  const BackwardPlan& pl = c.plan;
+  int rc;
+  SirenBwdParams bp = chain_params(m, r.fp, r.pp, r.k.nb, r.k.n, r.out, r.d_out, r.tape, c.tape_format);
+  if (pl.film16) {
+    chain_film_sums_only(bp, r.dump);
+  } else {
+    chain_dump_to(m, bp, r.dump);
+    if (pl.det) bp.d_e = c.d_e + (size_t)r.g0 * 32;
+    else if (pl.scatters) chain_scatter_into(m, bp, r.pts, c.d_grid_cl);
+    else bp.d_e = c.d_e;      // (FiLM-only on an exact-fp32 model with a grid: the chain still writes d(grid features); nobody reads them)
   }
-  if (d_grid_cl && stage != 2) {
-    PhaseScope ph(PH_GRID, stream);
-    if ((rc = launch_grid_unlayout(d_grid_cl, d_grid_ncdhw, m->gd, m->gh, m->gw, stream))) return rc;
+  if ((rc = run_chain(m, bp, c.stream))) return rc;
+  if (pl.grid_cl && !pl.scatters) {
+    PhaseScope ph(PH_GRID, c.stream);
+    if ((rc = launch_grid_backward(m, bp.P, r.pts, c.d_e, c.d_grid_cl, c.stream))) return rc;
   }
-  if (det && stage != 2) {        // every chain has run: all rows at once, finished straight into the parameter's layout
-    PhaseScope ph(PH_GRID, stream);
-    const long long rows = (long long)nB * Pp;
-    if ((rc = launch_grid_backward_det(m, rows, rows, pts2, d_e, d_grid_ncdhw, true, wb + wsz.det, stream))) return rc;
-  }
-  if (rays) {       // every chunk has left its rows: one reduction over both passes' samples per ray
-    PhaseScope ph(PH_OTHER, stream);
-    if ((rc = launch_ray_grads(B, R, N, Pp, 2, d_pts2, d_rd2, z_coarse, zf, rays->d_origins, rays->d_dirs, stream))) return rc;
+  if (c.rays) {
+    PhaseScope ph(PH_OTHER, c.stream);
+    if ((rc = launch_siren_input_grads(m, r.k.nb, r.k.n, r.pts, r.fp, r.dump, c.rays->w_geo0, c.rays->w_color0, c.rays->w_color0_ld,
+                                       c.d_pts2 + (size_t)r.g0 * 3, c.d_rd2 ? c.d_rd2 + (size_t)r.g0 * 3 : nullptr, c.stream)))
+      return rc;
   }
   return FENERF_OK;
 }
+
+// the chunk's weight / FiLM gradients.  The first chunk writes the outputs, later ones a scratch set that is then added (chunk order: the
+// sums of rounds 2-4, bit for bit); FiLM rows of an image's first point range are written in place, later ranges added
+int bwd_chunk_wgrad(RenderBwd& c, const ChunkRows& r) {
+  const FenerfModel* m = c.m;
+  const BackwardPlan& pl = c.plan;
+  const Chunk& k = r.k;
+  const FenerfSirenGrads* grads = c.grads;
+  FenerfSirenGrads gc;
+  memset(&gc, 0, sizeof(gc));
+  float* scratch = (float*)(c.wb + pl.scratch);
+  float* film_scratch = scratch + (c.film_only ? 0 : c.gz.total);
+  const bool film_direct = k.s == 0, add_weights = !c.first && !c.film_only;
+  float* fdst[4];
+  for (int q = 0; q < 4; ++q) {
+    fdst[q] = film_direct ? c.f2[q] + (size_t)k.b * c.frow[q] : film_scratch;
+    film_scratch += (size_t)k.nb * c.frow[q];
+  }
+  if (!c.film_only) {
+    if (c.first) gc = *grads;
+    else carve_grads(m, c.gz, scratch, &gc);
+  }
+  gc.d_freq_geo = fdst[0]; gc.d_phase_geo = fdst[1]; gc.d_freq_app = fdst[2]; gc.d_phase_app = fdst[3];
+  int rc = launch_param_grads(m, k.nb, k.n, r.pts, c.rd ? c.rd + (size_t)r.g0 * 3 : nullptr, r.fp, r.pp, r.out, r.d_out, (const float*)r.tape,
+                              c.tape_e2 ? c.tape_e2 + (size_t)r.g0 * 32 : nullptr, pl.film16 ? nullptr : r.dump, gc, c.film_only, c.wb + pl.wgrad, c.stream,
+                              pl.film16 ? r.dump : nullptr, c.tape_format, c.weights);
+  if (rc) return rc;
+  if (!film_direct || add_weights) {
+    const GradSizes& gz = c.gz;
+    MultiAdd J;
+    memset(&J, 0, sizeof(J));
+    int n = 0;
+    auto add = [&](float* dst, const float* src, long long cnt) { if (dst && src && cnt > 0) { J.dst[n] = dst; J.src[n] = src; J.n[n] = cnt; ++n; } };
+    if (add_weights) {
+      for (int i = 0; i < m->n_geo; ++i) { add(grads->geo_w[i], gc.geo_w[i], gz.geo_w[i]); add(grads->geo_b[i], gc.geo_b[i], gz.geo_b[i]); }
+      for (int i = 0; i < m->n_color; ++i) { add(grads->color_w[i], gc.color_w[i], gz.color_w[i]); add(grads->color_b[i], gc.color_b[i], gz.color_b[i]); }
+      add(grads->head_w, gc.head_w, gz.head_w); add(grads->head_b, gc.head_b, gz.head_b); add(grads->rgb_w, gc.rgb_w, gz.rgb_w); add(grads->rgb_b, gc.rgb_b, gz.rgb_b);
+    }
+    if (!film_direct)
+      for (int q = 0; q < 4; ++q) add(c.f2[q] + (size_t)k.b * c.frow[q], fdst[q], (long long)k.nb * c.frow[q]);
+    J.count = n;
+    PhaseScope ph(PH_OTHER, c.stream);
+    if ((rc = launch_multi_add(J, c.stream))) return rc;
+  }
+  c.first = false;
+  return FENERF_OK;
+}
+
+// FiLM fold (the two passes of an image share its FiLM parameters: row b + row B + b), the grid gradient in the parameter's layout --
+// unlayout of the accumulated grid, or the one deterministic reduction of all rows -- and the reduction to per-ray gradients
+int bwd_finish(const RenderBwd& c) {
+  const FenerfModel* m = c.m;
+  int rc;
+  if (bwd_runs(c, BWD_FILM_FOLD)) {
+    FilmFold F;
+    F.B = c.B;
+    F.out[0] = c.grads->d_freq_geo; F.out[1] = c.grads->d_phase_geo; F.out[2] = c.grads->d_freq_app; F.out[3] = c.grads->d_phase_app;
+    for (int q = 0; q < 4; ++q) { F.in[q] = c.f2[q]; F.row[q] = (int)c.frow[q]; }
+    PhaseScope ph(PH_OTHER, c.stream);
+    if ((rc = launch_film_fold(F, c.stream))) return rc;
+  }
+  if (c.d_grid_cl && bwd_runs(c, BWD_GRID_FINISH)) {
+    PhaseScope ph(PH_GRID, c.stream);
+    if ((rc = launch_grid_unlayout(c.d_grid_cl, c.d_grid_ncdhw, m->gd, m->gh, m->gw, c.stream))) return rc;
+  }
+  if (c.plan.det && bwd_runs(c, BWD_GRID_FINISH)) {        // every chain has run: all rows at once, finished straight into the parameter's layout
+    PhaseScope ph(PH_GRID, c.stream);
+    const long long rows = (long long)2 * c.B * c.sv.Pp;
+    if ((rc = launch_grid_backward_det(m, rows, rows, c.pts2, c.d_e, c.d_grid_ncdhw, true, c.wb + c.plan.det_ws, c.stream))) return rc;
+  }
+  if (c.rays) {       // every chunk has left its rows: one reduction over both passes' samples per ray
+    PhaseScope ph(PH_OTHER, c.stream);
+    if ((rc = launch_ray_grads(c.B, c.R, c.N, c.sv.Pp, 2, c.d_pts2, c.d_rd2, c.z_coarse, c.zf, c.rays->d_origins, c.rays->d_dirs, c.stream))) return rc;
+  }
+  return FENERF_OK;
+}
+
+int render_backward_impl(RenderBwd& c) {
+  int rc = bwd_validate(c);
+  if (rc) return rc;
+  if (bwd_runs(c, BWD_COMPOSITE) && (rc = bwd_composite(c))) return rc;
+  for (int ci = 0; ci < (int)c.plan.chunks.size(); ++ci) {
+    const bool chain = bwd_runs(c, BWD_CHAIN, ci), wgrad = bwd_runs(c, BWD_WGRAD, ci);
+    if (!chain && !wgrad) continue;
+    const ChunkRows r = chunk_rows(c, ci);
+    if (chain && (rc = bwd_chunk_chain(c, r))) return rc;
+    if (wgrad && (rc = bwd_chunk_wgrad(c, r))) return rc;
+  }
+  return bwd_finish(c);
+}
+}  // namespace
 
 // replaces: the `origins.grad` / `dirs.grad` torch autograd leaves behind transformed_points = origins + dirs * z and the expanded view
 // directions of a render (generators.py:468-476, :504) when the rays carry a graph -- the reference never asks (its rays are built under
@@ -1806,7 +1838,7 @@ extern "C" int fenerf_ray_grads(int B, int R, int N, int passes, const float* d_
 extern "C" size_t fenerf_render_backward_rays_workspace_bytes(const FenerfModel* m, int B, int R, int N, int film_only, int lock_view,
                                                               int64_t chunk_points, int64_t film_sums_budget_bytes) {
   if (!m || B <= 0 || R <= 0 || N <= 0) return 0;
-  return backward_ws(m, B, R, N, film_only, chunk_points, film_sums_budget_bytes, 1, lock_view ? 2 : 1).total;
+  return backward_plan(m, B, R, N, film_only, chunk_points, film_sums_budget_bytes, 1, lock_view ? 2 : 1).total;
 }
 
 // replaces: loss.backward() through a render whose rays carry a graph (see fenerf_ray_grads) -- fenerf_render_backward plus, per backward
@@ -1822,8 +1854,9 @@ extern "C" int fenerf_render_backward_rays(const FenerfModel* m, int B, int R, i
   if (!w_geo0 || !w_color0) return fail(FENERF_E_INVALID, "w_geo0 / w_color0 is NULL");
   if (w_color0_ld < 3 + m->grid_ch) return fail(FENERF_E_INVALID, "w_color0_ld < 3 + grid channels");
   const RayGrads rays{w_geo0, w_color0, w_color0_ld, d_origins, d_dirs};
-  return render_backward_impl(m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
-                              chunk_points, film_sums_budget_bytes, workspace, workspace_bytes, stream, 1, 0, &rays);
+  RenderBwd c{m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
+              chunk_points, film_sums_budget_bytes, workspace, workspace_bytes, stream, 1, 0, &rays, nullptr};
+  return render_backward_impl(c);
 }
 
 // replaces: loss.backward() through a render whose loss reads the depth map beside (or instead of) the pixels -- one entry for a depth
@@ -1840,8 +1873,9 @@ extern "C" int fenerf_render_backward_outputs(const FenerfModel* m, int B, int R
   if (want_rays && (!w_geo0 || !w_color0)) return fail(FENERF_E_INVALID, "w_geo0 / w_color0 is NULL");
   if (want_rays && w_color0_ld < 3 + m->grid_ch) return fail(FENERF_E_INVALID, "w_color0_ld < 3 + grid channels");
   const RayGrads rays{w_geo0, w_color0, w_color0_ld, d_origins, d_dirs};
-  return render_backward_impl(m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
-                              chunk_points, film_sums_budget_bytes, workspace, workspace_bytes, stream, 1, 0, want_rays ? &rays : nullptr, g_depth);
+  RenderBwd c{m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
+              chunk_points, film_sums_budget_bytes, workspace, workspace_bytes, stream, 1, 0, want_rays ? &rays : nullptr, g_depth};
+  return render_backward_impl(c);
 }
 
 extern "C" int fenerf_render_backward(const FenerfModel* m, int B, int R, int N, int lock_view, const void* save, size_t save_bytes,
@@ -1849,13 +1883,14 @@ extern "C" int fenerf_render_backward(const FenerfModel* m, int B, int R, int N,
                                       const float* g_rgb, const FenerfSirenGrads* grads, float* d_grid_ncdhw, const FenerfSirenGrads* weights,
                                       int64_t chunk_points, int64_t film_sums_budget_bytes, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-  return render_backward_impl(m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
-                              chunk_points, film_sums_budget_bytes, workspace, workspace_bytes, stream, 1, 0);
+  RenderBwd c{m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
+              chunk_points, film_sums_budget_bytes, workspace, workspace_bytes, stream, 1, 0, nullptr, nullptr};
+  return render_backward_impl(c);
 }
 
 extern "C" size_t fenerf_render_backward_split_workspace_bytes(const FenerfModel* m, int B, int R, int N, int64_t chunk_points, int keep_chunks) {
   if (!m || B <= 0 || R <= 0 || N <= 0 || keep_chunks < 1) return 0;
-  return backward_ws(m, B, R, N, 0, chunk_points, 0, keep_chunks).total;
+  return backward_plan(m, B, R, N, 0, chunk_points, 0, keep_chunks, 0).total;
 }
 
 extern "C" int fenerf_render_backward_stage(const FenerfModel* m, int stage, int keep_chunks, int B, int R, int N, int lock_view, const void* save,
@@ -1864,6 +1899,29 @@ extern "C" int fenerf_render_backward_stage(const FenerfModel* m, int stage, int
                                             const FenerfSirenGrads* weights, int64_t chunk_points, void* workspace, size_t workspace_bytes,
                                             void* stream) {
   if (stage != 1 && stage != 2) return fail(FENERF_E_INVALID, "stage must be 1 (render stage) or 2 (weight stage)");
-  return render_backward_impl(m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
-                              chunk_points, 0, workspace, workspace_bytes, stream, keep_chunks, stage);
+  RenderBwd c{m, B, R, N, lock_view, save, save_bytes, tape_format, z_coarse, noise_final, opts, g_rgb, grads, d_grid_ncdhw, weights,
+              chunk_points, 0, workspace, workspace_bytes, stream, keep_chunks, stage, nullptr, nullptr};
+  return render_backward_impl(c);
+}
+
+// Test hook (not part of include/fenerf.h): backward_plan on the CPU, for a model given by plain dimensions -- no device pointer, no HIP
+// call.  dims = {H, n_geo, n_color, C, grid_ch, grid_d, grid_h, grid_w, precision, differentiable, grid_grad_mode, wgrad_bf16_min_points,
+// num_cus}.  chunks receives up to max_chunks rows (b, nb, s, n); offsets the 11 region offsets in BackwardPlan's order, then total and
+// dump_stride.  Returns the number of chunks of the plan, or -1.
+extern "C" int fenerf_internal_backward_plan(const int* dims, int B, int R, int N, int film_only, int64_t chunk_points, int64_t film_sums_budget_bytes,
+                                             int dump_slots, int ray_mode, int64_t* chunks, int max_chunks, uint64_t* offsets) {
+  if (!dims || !chunks || !offsets || B <= 0 || R <= 0 || N <= 0 || max_chunks < 0) return -1;
+  FenerfModel m{};
+  m.H = dims[0]; m.n_geo = dims[1]; m.n_color = dims[2]; m.C = dims[3]; m.n_lab = m.C - 4; m.L = m.n_geo + m.n_color;
+  m.grid_ch = dims[4]; m.gd = dims[5]; m.gh = dims[6]; m.gw = dims[7];
+  m.precision = dims[8]; m.differentiable = dims[9]; m.grid_grad_mode = dims[10]; m.wgrad_bf16_min_points = dims[11]; m.num_cus = dims[12];
+  const BackwardPlan p = backward_plan(&m, B, R, N, film_only, chunk_points, film_sums_budget_bytes, dump_slots, ray_mode);
+  const int n = (int)p.chunks.size();
+  for (int i = 0; i < n && i < max_chunks; ++i) {
+    const Chunk& c = p.chunks[i];
+    chunks[4 * i] = c.b; chunks[4 * i + 1] = c.nb; chunks[4 * i + 2] = c.s; chunks[4 * i + 3] = c.n;
+  }
+  const size_t off[13] = {p.d_out2, p.d_fc, p.dump, p.d_grid_cl, p.d_e, p.det_ws, p.wgrad, p.film2, p.scratch, p.d_pts2, p.d_rd2, p.total, p.dump_stride};
+  for (int i = 0; i < 13; ++i) offsets[i] = off[i];
+  return n;
 }

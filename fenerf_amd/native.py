@@ -900,67 +900,22 @@ class NativeModel:
         return w0, wc0
 
     def render_backward(self, B, R, N, save, z_coarse, noise_final, opts, g_rgb, film_only, lock_view=False, tape_format=0, weights=None,
-                        chunk_points=0, film_sums_budget_bytes=0, ray_grads=None, g_depth=None):
+                        chunk_points=0, film_sums_budget_bytes=0, ray_grads=None, g_depth=None, entry=None):
         """fenerf_render_backward: every gradient of the render in ONE call -> (dict like siren_param_grads -- FiLM gradients [B, n*H], both
         passes summed; weight / bias gradients unless film_only --, d_grid [1,32,D,H,W] or None).
         ray_grads: None, or (w_geo0, w_color0, want_origins, want_dirs) -- layer 0's [H,3] and colour layer 0's [H,3+G+H] nn.Linear weights
         and which of the two ray gradients to deliver: fenerf_render_backward_rays, and the result dict gains d_origins / d_dirs [B,R,3]
         (None for the one not asked for).
         g_depth [B,R]: the gradient wrt the render's depth map -- fenerf_render_backward_outputs, with or without ray_grads; g_rgb may then
-        be None (a loss that reads the depth only)."""
+        be None (a loss that reads the depth only).
+        entry: the C entry is chosen by what is asked for ("plain", "rays" without a depth gradient, "outputs" with one); "outputs" here
+        takes fenerf_render_backward_outputs whatever is asked for (with nothing optional it is fenerf_render_backward)."""
         dev = self.device
-        if g_depth is not None:
-            return self._render_backward_outputs(B, R, N, save, z_coarse, noise_final, opts, g_rgb, g_depth, film_only, lock_view, tape_format,
-                                                 weights, chunk_points, film_sums_budget_bytes, ray_grads)
-        if ray_grads is not None:
-            return self._render_backward_rays(B, R, N, save, z_coarse, noise_final, opts, g_rgb, film_only, lock_view, tape_format, weights,
-                                              chunk_points, film_sums_budget_bytes, ray_grads)
-        if self.spec["grid_ch"] and not film_only and self.grid_grad_mode == _lib.GRID_GRAD_ATOMIC:
-            alert_not_deterministic("NativeModel.render_backward (atomic grid-gradient mode)")
-        res, g, d_grid = self._render_grad_buffers(B, film_only)
-        wts, keep = self._film_weight_struct(weights)
-        l = _lib.lib()
-        with torch.cuda.device(dev):
-            ws = self._workspace("render_bwd", l.fenerf_render_backward_workspace_bytes(self._h, B, R, N, int(film_only), int(chunk_points),
-                                                                                        int(film_sums_budget_bytes)))
-            _lib.check(l.fenerf_render_backward(self._h, B, R, N, int(lock_view), C.c_void_p(save.data_ptr()), C.c_size_t(save.numel()), int(tape_format),
-                                                _ptr(_f32(z_coarse, dev)), _ptr(_f32(noise_final, dev)) if noise_final is not None else None,
-                                                C.byref(opts), _ptr(_f32(g_rgb, dev)), C.byref(g), _ptr(d_grid), C.byref(wts) if wts is not None else None,
-                                                int(chunk_points), int(film_sums_budget_bytes), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream()))
-        return self._unpad_grads(res), d_grid
-
-    def _render_backward_rays(self, B, R, N, save, z_coarse, noise_final, opts, g_rgb, film_only, lock_view, tape_format, weights, chunk_points,
-                              film_sums_budget_bytes, ray_grads):
-        dev = self.device
-        w_geo0, w_color0, want_o, want_d = ray_grads
-        if not (want_o or want_d):
-            raise ValueError("ray_grads: neither d_origins nor d_dirs is asked for (pass ray_grads=None)")
-        if self.spec["grid_ch"] and not film_only and self.grid_grad_mode == _lib.GRID_GRAD_ATOMIC:
-            alert_not_deterministic("NativeModel.render_backward (atomic grid-gradient mode)")
-        res, g, d_grid = self._render_grad_buffers(B, film_only)
-        wts, keep = self._film_weight_struct(weights)
-        w0, wc0 = self._input_grad_weights(w_geo0, w_color0)
-        d_o = torch.empty((B, R, 3), dtype=torch.float32, device=dev) if want_o else None
-        d_d = torch.empty((B, R, 3), dtype=torch.float32, device=dev) if want_d else None
-        l = _lib.lib()
-        with torch.cuda.device(dev):
-            ws = self._workspace("render_bwd", l.fenerf_render_backward_rays_workspace_bytes(self._h, B, R, N, int(film_only), int(lock_view),
-                                                                                             int(chunk_points), int(film_sums_budget_bytes)))
-            _lib.check(l.fenerf_render_backward_rays(self._h, B, R, N, int(lock_view), C.c_void_p(save.data_ptr()), C.c_size_t(save.numel()),
-                                                     int(tape_format), _ptr(_f32(z_coarse, dev)),
-                                                     _ptr(_f32(noise_final, dev)) if noise_final is not None else None, C.byref(opts),
-                                                     _ptr(_f32(g_rgb, dev)), C.byref(g), _ptr(d_grid), C.byref(wts) if wts is not None else None,
-                                                     int(chunk_points), int(film_sums_budget_bytes), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
-                                                     _ptr(w0), _ptr(wc0), int(wc0.shape[1]), _ptr(d_o), _ptr(d_d), _stream()))
-        res = self._unpad_grads(res)
-        res["d_origins"], res["d_dirs"] = d_o, d_d
-        return res, d_grid
-
-    def _render_backward_outputs(self, B, R, N, save, z_coarse, noise_final, opts, g_rgb, g_depth, film_only, lock_view, tape_format, weights,
-                                 chunk_points, film_sums_budget_bytes, ray_grads):
-        dev = self.device
+        entry = entry or ("outputs" if g_depth is not None else "rays" if ray_grads is not None else "plain")
         w_geo0, w_color0, want_o, want_d = ray_grads if ray_grads is not None else (None, None, False, False)
         rays = bool(want_o or want_d)
+        if entry == "rays" and not rays:
+            raise ValueError("ray_grads: neither d_origins nor d_dirs is asked for (pass ray_grads=None)")
         if self.spec["grid_ch"] and not film_only and self.grid_grad_mode == _lib.GRID_GRAD_ATOMIC:
             alert_not_deterministic("NativeModel.render_backward (atomic grid-gradient mode)")
         res, g, d_grid = self._render_grad_buffers(B, film_only)
@@ -979,13 +934,17 @@ class NativeModel:
             else:
                 nbytes = l.fenerf_render_backward_workspace_bytes(self._h, B, R, N, int(film_only), int(chunk_points), int(film_sums_budget_bytes))
             ws = self._workspace("render_bwd", nbytes)
-            _lib.check(l.fenerf_render_backward_outputs(self._h, B, R, N, int(lock_view), C.c_void_p(save.data_ptr()), C.c_size_t(save.numel()),
-                                                        int(tape_format), _ptr(_f32(z_coarse, dev)),
-                                                        _ptr(_f32(noise_final, dev)) if noise_final is not None else None, C.byref(opts),
-                                                        _ptr(_f32(g_rgb, dev)) if g_rgb is not None else None, _ptr(gd), C.byref(g), _ptr(d_grid),
-                                                        C.byref(wts) if wts is not None else None, int(chunk_points), int(film_sums_budget_bytes),
-                                                        C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _ptr(w0), _ptr(wc0),
-                                                        int(wc0.shape[1]) if rays else 0, _ptr(d_o), _ptr(d_d), _stream()))
+            head = (self._h, B, R, N, int(lock_view), C.c_void_p(save.data_ptr()), C.c_size_t(save.numel()), int(tape_format), _ptr(_f32(z_coarse, dev)),
+                    _ptr(_f32(noise_final, dev)) if noise_final is not None else None, C.byref(opts), _ptr(_f32(g_rgb, dev)) if g_rgb is not None else None)
+            mid = (C.byref(g), _ptr(d_grid), C.byref(wts) if wts is not None else None, int(chunk_points), int(film_sums_budget_bytes),
+                   C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()))
+            ray_args = (_ptr(w0), _ptr(wc0), int(wc0.shape[1]) if rays else 0, _ptr(d_o), _ptr(d_d))
+            if entry == "outputs":
+                _lib.check(l.fenerf_render_backward_outputs(*head, _ptr(gd), *mid, *ray_args, _stream()))
+            elif entry == "rays":
+                _lib.check(l.fenerf_render_backward_rays(*head, *mid, *ray_args, _stream()))
+            else:
+                _lib.check(l.fenerf_render_backward(*head, *mid, _stream()))
         res = self._unpad_grads(res)
         if ray_grads is not None:
             res["d_origins"], res["d_dirs"] = d_o, d_d

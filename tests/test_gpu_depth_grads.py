@@ -487,12 +487,12 @@ def test_render_backward_outputs_entry_point():
     common = dict(lock_view=lock, tape_format=fmt, weights=weights)
     a, _ = nat.render_backward(B, R, N, save, z_c, noise_f, opts, w.contiguous(), False, **common)
     a = {k: v.clone() if torch.is_tensor(v) else [t.clone() for t in v] for k, v in a.items()}
-    b, _ = nat._render_backward_outputs(B, R, N, save, z_c, noise_f, opts, w.contiguous(), None, False, lock, fmt, weights, 0, 0, None)
+    b, _ = nat.render_backward(B, R, N, save, z_c, noise_f, opts, w.contiguous(), False, entry="outputs", **common)
     flat = lambda r: [t for k in sorted(r) for t in (r[k] if isinstance(r[k], (list, tuple)) else [r[k]]) if torch.is_tensor(t)]
     fa, fb = flat(a), flat(b)
     assert len(fa) == len(fb) > 20 and all(torch.equal(x, y) for x, y in zip(fa, fb))
     with pytest.raises(_lib.FenerfError, match="both NULL"):
-        nat._render_backward_outputs(B, R, N, save, z_c, noise_f, opts, None, None, False, lock, fmt, weights, 0, 0, None)
+        nat.render_backward(B, R, N, save, z_c, noise_f, opts, None, False, entry="outputs", **common)
     # a depth gradient with NO rgb gradient is a valid call
     c, _ = nat.render_backward(B, R, N, save, z_c, noise_f, opts, None, False, g_depth=_depth_weights(B, R), **common)
     assert all(torch.isfinite(t).all() for t in flat(c))

@@ -548,6 +548,73 @@ def test_backward_chunk_plan_and_grid_digest():
     assert native.NativeModel._grid_checksum(odd).shape == (45,)
 
 
+def test_backward_plan_of_the_c_abi_matches_the_python_planner_and_tiles_its_workspace():
+    """backward_plan of fenerf_api.cpp -- the one object the render backward's workspace sizes, pointers and chunk loop come from --
+    through its test hook, on the CPU: the chunk list is siren.autograd.plan_chunks' for the same arguments, and the regions start
+    256-aligned, tile [0, total) in the declared order without gaps beyond the alignment, and are empty exactly where their rule says.
+    The rows are those of test_backward_chunk_plan_and_grid_digest; the C entry plans 2 B (pass, image) pairs, so a row's nB is 2 B
+    where it is even and B where it is odd.  A FiLM-only step of an f16x3 model plans by the FiLM-sums budget without ray gradients
+    and by the dump's with them (the input-gradient pass reads the dump): there the ray modes are compared with each other only."""
+    import ctypes as C
+    from fenerf_amd.siren import autograd as SA
+    hook = _lib.lib().fenerf_internal_backward_plan
+    hook.restype = C.c_int
+    hook.argtypes = [C.POINTER(C.c_int)] + [C.c_int] * 4 +[C.c_int64] * 2 + [C.c_int] * 2 + [C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_uint64)]
+    names = ("d_out2", "d_fc", "dump", "d_grid_cl", "d_e", "det_ws", "wgrad", "film2", "scratch", "d_pts2", "d_rd2")
+    H, ng, nc, ch, F16X3 = 64, 3, 2, 4, _lib.PRECISION["f16x3"]
+    L = ng + nc
+    chunks_buf, off_buf = (C.c_int64 * (4 * 256))(), (C.c_uint64 * 13)()
+
+    def plan(prec, grid, det, B, R, N, film_only, chunk_points, budget, slots, ray):
+        dims = (C.c_int * 13)(H, ng, nc, ch, 32 if grid else 0, *((8, 8, 8) if grid else (0, 0, 0)), prec, 1, int(det), 0, 256)
+        n = hook(dims, B, R, N, film_only, chunk_points, budget, slots, ray, chunks_buf, 256, off_buf)
+        assert 0 < n <= 256
+        return [tuple(chunks_buf[4 * i:4 * i + 4]) for i in range(n)], list(off_buf)
+
+    calls = 0
+    for nB, Pp_row, cap in ((12, 393216, 393216), (2, 393216, 196608), (8, 24576, 196608), (3, 544, 128), (4, 1700, 1700), (1, 786432, 1 << 30)):
+        B = nB // 2 if nB % 2 == 0 else nB
+        R, N = (Pp_row // 4, 4) if Pp_row % 24 else (Pp_row // 24, 24)
+        P, Pp = R * N, (R * N + 31) // 32 * 32
+        assert P == Pp_row
+        sums_bytes_pp = 4.0 * ((Pp + 127) // 128 * L * 2 * H) / Pp          # fenerf_siren_film_sums_floats(m, 1, Pp): one unit per 128 points
+        budget = int(cap * sums_bytes_pp) + 64
+        for prec, grid, det in ((p, g, d) for p in (_lib.PRECISION["f32"], F16X3) for g in (False, True) for d in ((False, True) if g else (False,))):
+            for film_only in (0, 1):
+                film16_possible = bool(film_only) and prec == F16X3
+                for slots in (1, 2):
+                    by_ray = {}
+                    for ray in (0, 1, 2):
+                        chunks, off = plan(prec, grid, det, B, R, N, film_only, cap, budget, slots, ray)
+                        calls += 1
+                        film16 = film16_possible and ray == 0
+                        # (a) the chunk list
+                        limit = int(min(float(1 << 24), budget / sums_bytes_pp)) if film16 else cap
+                        assert chunks == SA.plan_chunks(2 * B, Pp, limit), (nB, Pp, cap, prec, film_only, ray)
+                        # (b), (c) aligned, in order, disjoint, ending at total
+                        starts, total, stride = off[:11], off[11], off[12]
+                        assert all(s % 256 == 0 for s in starts) and total % 256 == 0 and stride % 256 == 0
+                        assert starts[0] == 0 and all(a <= b for a, b in zip(starts, starts[1:] + [total]))
+                        size = dict(zip(names, (b - a for a, b in zip(starts, starts[1:] + [total]))))
+                        assert size["dump"] == stride * min(slots, len(chunks))
+                        # (e) which regions are empty
+                        det_on = grid and det and not film_only
+                        scatters = prec == F16X3          # the f16x3 chain scatters d(grid features) itself
+                        want = dict(d_out2=True, d_fc=Pp != P, dump=True, d_grid_cl=grid and not film_only and not det_on,
+                                    d_e=det_on or (grid and not scatters), det_ws=det_on, wgrad=True, film2=True, scratch=len(chunks) > 1,
+                                    d_pts2=ray != 0, d_rd2=ray == 1)
+                        assert {k: v > 0 for k, v in size.items()} == {k: bool(v) for k, v in want.items()}, (size, want)
+                        assert size["d_out2"] >= 2 * B * Pp * ch * 4 and size["film2"] >= 2 * B * 2 * L * H * 4
+                        if ray:
+                            assert size["d_pts2"] >= 2 * B * Pp * 3 * 4
+                        by_ray[ray] = (chunks, starts[:10])
+                    # (d) the ray regions lie behind everything else: nothing in front of them moves
+                    assert by_ray[1] == by_ray[2]
+                    if not film16_possible:
+                        assert by_ray[0] == by_ray[1]
+    assert calls == 6 * 6 * 2 * 2 * 3
+
+
 def test_backward_gradient_sum_over_chunks_is_the_sequential_sum():
     """siren/autograd.py GradSum, the one sum of per-chunk gradients of the Python backward, over fake per-chunk results for plans from
     plan_chunks -- a plan is whole-image chunks (here 2 + 2 + 1 images) or point ranges of single images (here 4 x 128 + 32 points of
