@@ -174,6 +174,13 @@ _SIGS = {
     "fenerf_mesh_workspace_bytes": (_sz, [_i, _i, _i]),
     "fenerf_mesh_count": (_i, [_vp, _i, _i, _i, C.c_float, _vp, _vp, _vp]),
     "fenerf_mesh_emit": (_i, [_vp, _i, _i, _i, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _i64, _i64, _vp, _vp, _vp]),
+    # mesh cleaning (fenerf_mesh_clean.hip): components of the inside set, vertex clustering
+    "fenerf_volume_components_workspace_bytes": (_sz, [_i, _i, _i]),
+    "fenerf_volume_components": (_i, [_vp, _i, _i, _i, C.c_float, _vp, _vp, _vp, _vp]),
+    "fenerf_volume_keep_components": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i64, _vp, _vp]),
+    "fenerf_mesh_cluster_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i, _i]),
+    "fenerf_mesh_cluster_count": (_i, [_vp, _i64, _vp, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _i, _vp, _vp, _vp]),
+    "fenerf_mesh_cluster_emit": (_i, [_vp, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
     "fenerf_composite_backward": (_i, [_i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(FenerfCompositeOpts), _vp, _vp, _vp, _vp]),
     "fenerf_render_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "fenerf_render_forward": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 10 + [C.POINTER(FenerfCompositeOpts)] + [_vp] * 4 + [_vp, _sz, _vp]),
@@ -183,6 +190,7 @@ N_PHASES = 17        # include/fenerf.h FENERF_N_PHASES
 FUSION_AUTO, FUSION_OFF, FUSION_FORCE = 0, 1, 2      # include/fenerf.h fenerf_set_render_fusion
 TAPE_F32, TAPE_U16, TAPE_F32_W = 0, 1, 2             # include/fenerf.h FENERF_TAPE_*
 GRID_GRAD_ATOMIC, GRID_GRAD_DETERMINISTIC = 0, 1     # include/fenerf.h FENERF_GRID_GRAD_*
+KEEP_LARGEST, KEEP_MIN_POINTS = 0, 1                 # include/fenerf.h FENERF_KEEP_*
 
 _lib = None
 

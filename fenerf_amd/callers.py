@@ -184,7 +184,7 @@ MESH_NORMAL_CHUNK = 262144       # vertices per differentiable SIREN call of ext
 
 
 def extract_mesh(generator, z_geo, z_app=None, *, film=None, voxel_resolution=256, voxel_origin=(0, 0, 0), cube_length=2.0, psi=0.5, iso=10.0,
-                 attributes=("normal", "label", "rgb")):
+                 attributes=("normal", "label", "rgb"), keep="all", simplify=None):
     """Labelled, coloured iso-surface of one identity: the step the reference leaves to skimage.measure.marching_cubes + plyfile
     (extract_shapes.py, extract_double_semantic_shapes.py).  The lattice is evaluated exactly as sample_generator does (truncated FiLM
     parameters, locked view direction, one fused launch) -- or, with film= (the meta dict of
@@ -196,6 +196,11 @@ def extract_mesh(generator, z_geo, z_app=None, *, film=None, voxel_resolution=25
     differentiable bare-SIREN route in chunks of at most MESH_NORMAL_CHUNK vertices.
     -> dict of numpy arrays: vertices [V,3] float32, faces [F,3] int32 and the requested attributes (normal [V,3] float32, label [V] uint8,
     rgb [V,3] uint8).  iso = 10.0 is this project's choice: the reference's scripts name no level.
+    keep = "largest" | a number of lattice points: detached blobs of density go before meshing -- only the largest connected component of
+    {sigma >= iso}, or every component of at least that many points, stays (native.filter_volume); the dict gains `components`, the count
+    before filtering.  simplify = an integer factor >= 2: the vertices of every factor^3 block of cells merge into their mean
+    (native.cluster_mesh) after meshing and before the attribute pass, so label, rgb and normal are evaluated at the vertices that survive
+    (a merged vertex lies near the surface, not on it).  With the defaults neither runs.
     Like sample_generator, the z_geo route calls generate_avg_frequencies, whose 2 x 10,000 draws start from the generator state the caller
     leaves: for the surface of a volume sample_generator returned, restore that state first (tools/extract_shapes.py re-seeds)."""
     from . import imageio_lite
@@ -203,6 +208,10 @@ def extract_mesh(generator, z_geo, z_app=None, *, film=None, voxel_resolution=25
     unknown = set(attributes) - {"normal", "label", "rgb"}
     if unknown:
         raise ValueError(f"extract_mesh: unknown attributes {sorted(unknown)}")
+    if not (keep in ("all", "largest") or (isinstance(keep, int) and not isinstance(keep, bool) and keep >= 1)):
+        raise ValueError(f'extract_mesh: keep is "all", "largest" or a number of points >= 1, not {keep!r}')
+    if not (simplify is None or (isinstance(simplify, int) and not isinstance(simplify, bool) and simplify >= 2)):
+        raise ValueError(f"extract_mesh: simplify is None or an integer factor >= 2, not {simplify!r}")
     N = voxel_resolution
     siren = generator.siren
     with torch.no_grad():
@@ -223,10 +232,19 @@ def extract_mesh(generator, z_geo, z_app=None, *, film=None, voxel_resolution=25
         out = nat.siren_forward(samples, None, fg, pg, fa, pa)          # None = locked view dir
         sigma = out[..., -1].reshape(N, N, N).contiguous()
         del out
+        components = None
+        if keep != "all":
+            sigma, stats = native.filter_volume(sigma, iso, keep, out=sigma)
+            components = int(native.to_host(stats)[1])
         # samples[:, k] = (lattice index along axis k) * voxel_size + origin[2 - k]  (create_samples)
-        vertices, faces = native.mesh_from_volume(sigma, iso, origin=(origin[2], origin[1], origin[0]), spacing=(voxel_size,) * 3)
+        frame = dict(origin=(origin[2], origin[1], origin[0]), spacing=(voxel_size,) * 3)
+        vertices, faces = native.mesh_from_volume(sigma, iso, **frame)
+        if simplify is not None:
+            vertices, faces = native.cluster_mesh(vertices, faces, shape=(N, N, N), factor=simplify, **frame)
         V = vertices.shape[0]
         mesh = dict(vertices=native.to_host(vertices).numpy(), faces=native.to_host(faces).numpy())
+        if components is not None:
+            mesh["components"] = components
         if V and ("label" in attributes or "rgb" in attributes):
             pad = (-V) % 32
             pts = torch.cat([vertices, vertices[-1:].expand(pad, -1)])[None] if pad else vertices[None]

@@ -1213,6 +1213,70 @@ extern "C" int fenerf_mesh_emit(const float* vol, int n0, int n1, int n2, float 
   { PhaseScope ph(PH_OTHER, stream); return launch_mesh_emit(vol, n0, n1, n2, iso, origin, spacing, workspace, n_vertices, n_faces, vertices, faces, stream); }
 }
 
+// ---- mesh cleaning (fenerf_mesh_clean.hip) ----
+extern "C" size_t fenerf_volume_components_workspace_bytes(int n0, int n1, int n2) {
+  if (check_lattice("fenerf_volume_components_workspace_bytes", n0, n1, n2) != FENERF_OK) return 0;
+  return components_workspace_bytes(n0, n1, n2);
+}
+
+extern "C" int fenerf_volume_components(const float* vol, int n0, int n1, int n2, float iso, void* workspace, int32_t* labels_dev, int64_t* stats_dev,
+                                        void* stream) {
+  if (int rc = check_lattice("fenerf_volume_components", n0, n1, n2)) return rc;
+  if (!vol || !workspace || !labels_dev || !stats_dev)
+    return fail(FENERF_E_INVALID, "fenerf_volume_components: vol / workspace / labels_dev / stats_dev is NULL");
+  { PhaseScope ph(PH_OTHER, stream); return launch_volume_components(vol, n0, n1, n2, iso, workspace, labels_dev, (long long*)stats_dev, stream); }
+}
+
+extern "C" int fenerf_volume_keep_components(const float* vol, const int32_t* labels, const void* workspace, int n0, int n1, int n2, int mode,
+                                             int64_t min_points, float* vol_out, void* stream) {
+  if (int rc = check_lattice("fenerf_volume_keep_components", n0, n1, n2)) return rc;
+  if (!vol || !labels || !workspace || !vol_out) return fail(FENERF_E_INVALID, "fenerf_volume_keep_components: vol / labels / workspace / vol_out is NULL");
+  if (mode != FENERF_KEEP_LARGEST && mode != FENERF_KEEP_MIN_POINTS) return fail(FENERF_E_INVALID, "fenerf_volume_keep_components: unknown mode");
+  if (min_points < 1) return fail(FENERF_E_INVALID, "fenerf_volume_keep_components: min_points < 1");
+  const int mp = (int)std::min<int64_t>(min_points, INT32_MAX);      // a component has at most 2^31 - 1 points
+  { PhaseScope ph(PH_OTHER, stream); return launch_volume_keep_components(vol, labels, workspace, n0, n1, n2, mode == FENERF_KEEP_LARGEST, mp, vol_out, stream); }
+}
+
+namespace {
+int check_cluster(const char* who, int64_t V, int64_t F, int n0, int n1, int n2, int factor) {
+  if (int rc = check_lattice(who, n0, n1, n2)) return rc;
+  if (factor < 2) return fail(FENERF_E_INVALID, std::string(who) + ": factor < 2");
+  if (V < 0 || F < 0 || V > INT32_MAX || F > INT32_MAX) return fail(FENERF_E_INVALID, std::string(who) + ": V and F must be in [0, 2^31 - 1]");
+  return FENERF_OK;
+}
+}  // namespace
+
+extern "C" size_t fenerf_mesh_cluster_workspace_bytes(int64_t V, int64_t F, int n0, int n1, int n2, int factor) {
+  if (check_cluster("fenerf_mesh_cluster_workspace_bytes", V, F, n0, n1, n2, factor) != FENERF_OK) return 0;
+  return cluster_workspace_bytes(V, F, n0, n1, n2, factor);
+}
+
+extern "C" int fenerf_mesh_cluster_count(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const float origin[3], const float spacing[3],
+                                         int n0, int n1, int n2, int factor, void* workspace, int64_t* counts_dev, void* stream) {
+  if (int rc = check_cluster("fenerf_mesh_cluster_count", V, F, n0, n1, n2, factor)) return rc;
+  if (!workspace || !counts_dev || !origin || !spacing || (V > 0 && !vertices) || (F > 0 && !faces))
+    return fail(FENERF_E_INVALID, "fenerf_mesh_cluster_count: vertices / faces / origin / spacing / workspace / counts_dev is NULL");
+  { PhaseScope ph(PH_OTHER, stream); return launch_mesh_cluster_count(vertices, V, faces, F, origin, spacing, n0, n1, n2, factor, workspace, (long long*)counts_dev, stream); }
+}
+
+extern "C" int fenerf_mesh_cluster_emit(const int32_t* faces, int64_t V, int64_t F, const float origin[3], const float spacing[3], int n0, int n1, int n2,
+                                        int factor, const void* workspace, int64_t n_vertices, int64_t n_faces, float* vertices_out, int32_t* faces_out,
+                                        void* stream) {
+  if (int rc = check_cluster("fenerf_mesh_cluster_emit", V, F, n0, n1, n2, factor)) return rc;
+  if (!workspace || !origin || !spacing || (F > 0 && !faces)) return fail(FENERF_E_INVALID, "fenerf_mesh_cluster_emit: faces / origin / spacing / workspace is NULL");
+  if (n_vertices < 0 || n_faces < 0 || n_vertices > INT32_MAX || n_faces > INT32_MAX) return fail(FENERF_E_INVALID, "fenerf_mesh_cluster_emit: a count outside [0, 2^31 - 1]");
+  if ((n_vertices > 0 && !vertices_out) || (n_faces > 0 && !faces_out)) return fail(FENERF_E_INVALID, "fenerf_mesh_cluster_emit: vertices_out / faces_out is NULL");
+  long long held[3] = {-1, -1, -1};       // what fenerf_mesh_cluster_count left in the workspace: the one host read of this call
+  if (hipError_t e = hipMemcpyAsync(held, cluster_workspace_totals(workspace), sizeof(held), hipMemcpyDeviceToHost, (hipStream_t)stream)) return hip_fail(e, "mesh cluster counts copy");
+  if (hipError_t e = hipStreamSynchronize((hipStream_t)stream)) return hip_fail(e, "mesh cluster counts copy");
+  if (held[2] != 0)
+    return fail(FENERF_E_INVALID, "fenerf_mesh_cluster_emit: " + std::to_string(held[2]) + " faces have an index outside [0, V)");
+  if (held[0] != n_vertices || held[1] != n_faces)
+    return fail(FENERF_E_INVALID, "fenerf_mesh_cluster_emit: the workspace holds " + std::to_string(held[0]) + " vertices and " + std::to_string(held[1]) +
+                                      " faces, the call says " + std::to_string((long long)n_vertices) + " and " + std::to_string((long long)n_faces));
+  { PhaseScope ph(PH_OTHER, stream); return launch_mesh_cluster_emit(faces, V, F, origin, spacing, n0, n1, n2, factor, workspace, n_vertices, n_faces, vertices_out, faces_out, stream); }
+}
+
 // workspace layout of fenerf_render_forward
 namespace {
 struct RenderWs {

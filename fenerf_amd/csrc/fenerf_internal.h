@@ -233,6 +233,17 @@ const long long* mesh_workspace_totals(const void* workspace);      // [dev] ver
 int launch_mesh_count(const float* vol, int n0, int n1, int n2, float iso, void* workspace, long long* counts_dev, void* stream);
 int launch_mesh_emit(const float* vol, int n0, int n1, int n2, float iso, const float* origin, const float* spacing, const void* workspace,
                      long long n_vertices, long long n_faces, float* vertices, int* faces, void* stream);
+// fenerf_mesh_clean.hip: connected components of the inside set, and vertex clustering
+size_t components_workspace_bytes(int n0, int n1, int n2);
+int launch_volume_components(const float* vol, int n0, int n1, int n2, float iso, void* workspace, int* labels, long long* stats_dev, void* stream);
+int launch_volume_keep_components(const float* vol, const int* labels, const void* workspace, int n0, int n1, int n2, int largest_only, int min_points,
+                                  float* vol_out, void* stream);
+size_t cluster_workspace_bytes(long long V, long long F, int n0, int n1, int n2, int factor);
+const long long* cluster_workspace_totals(const void* workspace);   // [dev] vertices, faces, faces with an index out of range
+int launch_mesh_cluster_count(const float* vertices, long long V, const int* faces, long long F, const float* origin, const float* spacing, int n0, int n1,
+                              int n2, int factor, void* workspace, long long* counts_dev, void* stream);
+int launch_mesh_cluster_emit(const int* faces, long long V, long long F, const float* origin, const float* spacing, int n0, int n1, int n2, int factor,
+                             const void* workspace, long long n_vertices, long long n_faces, float* vertices_out, int* faces_out, void* stream);
 int launch_pad_rows(const float* src, float* dst, long long nb, long long P, long long Pp, int C, bool to_padded, void* stream);
 int launch_multi_add(const MultiAdd& J, void* stream);
 int launch_film_fold(const FilmFold& J, void* stream);

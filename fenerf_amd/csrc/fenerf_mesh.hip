@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fenerf_internal.h"
+#include "fenerf_scan.h"
 
 namespace fenerf {
 
@@ -78,28 +79,6 @@ constexpr TetTable make_tet_table() {
 
 __device__ const TetTable kTet = make_tet_table();
 
-// exclusive prefix of v over the workgroup's 256 threads; *total = their sum.  Every thread of the workgroup calls it.
-__device__ __forceinline__ int block_scan_256(int v, int* total) {
-  __shared__ int wave_total[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int incl = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(incl, o);
-    if (lane >= o) incl += u;
-  }
-  if (lane == 63) wave_total[w] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-  for (int k = 0; k < 4; ++k) {
-    const int s = wave_total[k];
-    if (k < w) before += s;
-    all += s;
-  }
-  __syncthreads();
-  *total = all;
-  return before + incl - v;
-}
-
 struct Lattice {
   int n0, n1, n2;
   long long n, cells;      // points, cells
@@ -164,41 +143,6 @@ __global__ void __launch_bounds__(256) mesh_classify_cells_kernel(const float* _
   int total;
   block_scan_256(f, &total);
   if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
-}
-
-// Workgroup 0 / 1: the block counts of the points / of the cells become their exclusive prefix sums in place, with a running int64
-// carry over pieces of 1024 blocks; totals[blockIdx.x] (the workspace's copy) and counts_dev[blockIdx.x] (the caller's) = the sum.  A
-// prefix is kept as int32: it is only used when the total is below 2^31 (fenerf_mesh_emit refuses anything else).
-__global__ void __launch_bounds__(1024) mesh_scan_kernel(int* __restrict__ counts_v, long long nblk_v, int* __restrict__ counts_f, long long nblk_f,
-                                                         long long* __restrict__ totals, long long* __restrict__ counts_dev) {
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  int* bc = blockIdx.x == 0 ? counts_v : counts_f;
-  const long long nblk = blockIdx.x == 0 ? nblk_v : nblk_f;
-  __shared__ long long wave_sum[16];
-  __shared__ long long carry_s;
-  if (t == 0) carry_s = 0;
-  __syncthreads();
-  for (long long base = 0; base < nblk; base += 1024) {
-    const long long j = base + t;
-    const long long v = j < nblk ? bc[j] : 0;
-    long long incl = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const long long u = __shfl_up(incl, o);
-      if (lane >= o) incl += u;
-    }
-    if (lane == 63) wave_sum[w] = incl;
-    __syncthreads();
-    long long before = carry_s;
-    for (int k = 0; k < w; ++k) before += wave_sum[k];
-    if (j < nblk) bc[j] = (int)(before + incl - v);
-    __syncthreads();
-    if (t == 1023) carry_s = before + incl;
-    __syncthreads();
-  }
-  if (t == 0) {
-    totals[blockIdx.x] = carry_s;
-    counts_dev[blockIdx.x] = carry_s;
-  }
 }
 
 // One lane per lattice point: prefix[i] = crossing edges of all points before i
@@ -318,7 +262,7 @@ int launch_mesh_count(const float* vol, int n0, int n1, int n2, float iso, void*
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(mesh_classify_points_kernel, dim3((unsigned)w.nblk_v), dim3(256), 0, s, vol, L, iso, mask, blocks_v);
   hipLaunchKernelGGL(mesh_classify_cells_kernel, dim3((unsigned)w.nblk_f), dim3(256), 0, s, vol, L, iso, (unsigned char*)(ws + w.nfaces), blocks_f);
-  hipLaunchKernelGGL(mesh_scan_kernel, dim3(2), dim3(1024), 0, s, blocks_v, w.nblk_v, blocks_f, w.nblk_f, (long long*)(ws + w.totals), counts_dev);
+  hipLaunchKernelGGL(block_counts_scan_kernel, dim3(2), dim3(1024), 0, s, blocks_v, w.nblk_v, blocks_f, w.nblk_f, (long long*)(ws + w.totals), counts_dev);
   hipLaunchKernelGGL(mesh_point_prefix_kernel, dim3((unsigned)w.nblk_v), dim3(256), 0, s, mask, blocks_v, w.n, (int*)(ws + w.prefix));
   return check_launch("mesh count launch");
 }

@@ -10,7 +10,9 @@ Conventions (include/fenerf.h states the same):
     whose endpoints differ in `inside` carries one vertex; vertices are numbered in ascending (i, k).
   - position: t = (iso - vol[p]) / (vol[q] - vol[p]); coordinate j = origin[j] + (p_j + t * d_kj) * spacing[j], every operation fp32.
   - a tet emits 0, 1 or 2 triangles over its crossing edges; a quad is split along the diagonal through its smallest vertex number;
-    (v1 - v0) x (v2 - v0) points to the not-inside side; faces are ordered by cell, tet, triangle."""
+    (v1 - v0) x (v2 - v0) points to the not-inside side; faces are ordered by cell, tet, triangle.
+
+Further down: components / keep_components / cluster restate the mesh-cleaning calls (fenerf_amd/csrc/fenerf_mesh_clean.hip) the same way."""
 import numpy as np
 
 PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
@@ -156,3 +158,116 @@ def canonical_faces(faces):
     r = np.arange(f.shape[0])
     f = np.stack([f[r, m], f[r, (m + 1) % 3], f[r, (m + 2) % 3]], -1)
     return f[np.lexsort((f[:, 2], f[:, 1], f[:, 0]))]
+
+
+# ---- mesh cleaning (fenerf_amd/csrc/fenerf_mesh_clean.hip): components of the inside set, vertex clustering --------------------------------
+KEEP_LARGEST = "largest"
+
+
+def components(vol, iso):
+    """-> (labels int32 [n0,n1,n2], stats int64 [4]), what fenerf_volume_components writes.  Two inside points are adjacent when they differ
+    by +-d_k, k = 1 .. 7 (the Kuhn tetrahedra's edges: 14 neighbours); a component's label is its smallest linear index, -1 outside.
+    stats = inside points, components, label of the largest component (a tie: the smaller label; -1 with no inside point), its point count.
+    The kernels reach the labels by union-find with atomicMin; the result does not depend on the route, so this walks another one: every
+    inside point takes the smallest label among itself and its neighbours, then jumps to its label's label, until nothing changes."""
+    vol = np.asarray(vol, dtype=np.float32)
+    n0, n1, n2 = vol.shape
+    with np.errstate(invalid="ignore"):
+        inside = vol >= np.float32(iso)
+    n = vol.size
+    big = np.int64(n)
+    lab = np.where(inside, np.arange(n, dtype=np.int64).reshape(vol.shape), big)
+    while True:
+        new = lab.copy()
+        for k in range(1, 8):
+            d = (k & 1, (k >> 1) & 1, (k >> 2) & 1)
+            lo = (slice(0, n0 - d[0]), slice(0, n1 - d[1]), slice(0, n2 - d[2]))
+            hi = (slice(d[0], n0), slice(d[1], n1), slice(d[2], n2))
+            both = inside[lo] & inside[hi]
+            m = np.minimum(new[lo], new[hi])
+            new[lo] = np.where(both, m, new[lo])
+            new[hi] = np.where(both, np.minimum(m, new[hi]), new[hi])       # lo and hi overlap: never raise what the line above lowered
+        flat = new.reshape(-1)
+        ins = inside.reshape(-1)
+        flat[ins] = flat[flat[ins]]              # a label is the index of a point of the same component
+        if np.array_equal(new, lab):
+            break
+        lab = new
+    labels = np.where(inside, lab, -1).astype(np.int32)
+    counts = component_counts(labels)
+    roots = np.nonzero(counts)[0]
+    stats = np.array([int(inside.sum()), roots.size, -1, 0], dtype=np.int64)
+    if roots.size:
+        best = roots[np.argmax(counts[roots])]      # argmax takes the first of equal counts: the smaller label
+        stats[2], stats[3] = best, counts[best]
+    return labels, stats
+
+
+def component_counts(labels):
+    """int64 [n]: the point count of every component at its label's own index (what the kernels keep in the workspace), 0 elsewhere"""
+    flat = np.asarray(labels).reshape(-1)
+    return np.bincount(flat[flat >= 0], minlength=flat.size).astype(np.int64)
+
+
+def keep_components(vol, labels, keep):
+    """-> vol with every inside point of a dropped component replaced by -inf, everything else bit for bit (fenerf_volume_keep_components).
+    keep = "largest" (by point count, a tie to the smaller label), or an int: every component of at least that many points stays."""
+    vol = np.asarray(vol, dtype=np.float32)
+    labels = np.asarray(labels).reshape(vol.shape)
+    counts = component_counts(labels)
+    if keep == KEEP_LARGEST:
+        kept = np.zeros(counts.size, dtype=bool)
+        if counts.any():
+            kept[np.argmax(counts)] = True
+    else:
+        if int(keep) < 1:
+            raise ValueError("keep_components: min_points < 1")
+        kept = counts >= int(keep)
+    out = vol.copy()
+    drop = (labels >= 0) & ~kept[np.maximum(labels, 0)]
+    out[drop] = -np.inf
+    return out
+
+
+def cluster(vertices, faces, origin, spacing, shape, factor):
+    """-> (vertices [V',3] float32, faces [F',3] int32), what fenerf_mesh_cluster_count + fenerf_mesh_cluster_emit write.  Per vertex and axis:
+    u = (x - origin) / spacing in fp32, cell = clamp(floor(u / factor), 0, ceil((n - 1) / factor) - 1), cluster id = linear index of the
+    cell; the representative is the members' mean in 2^-16 lattice units summed as int64; new vertices in ascending cluster id over the
+    clusters a surviving face references; a face with two equal new indices is dropped, the others keep order and winding; duplicate faces
+    are not searched for.  A face index outside [0, V) raises ValueError (the library: FENERF_E_INVALID)."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    factor = int(factor)
+    if factor < 2:
+        raise ValueError("cluster: factor < 2")
+    origin, spacing = np.asarray(origin, dtype=np.float32), np.asarray(spacing, dtype=np.float32)
+    m = np.array([(int(n) - 1 + factor - 1) // factor for n in shape], dtype=np.int64)
+    V = v.shape[0]
+    if ((f < 0) | (f >= V)).any():
+        raise ValueError("cluster: a face index outside [0, V)")
+    empty = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32))
+    if not f.shape[0]:
+        return empty
+    with np.errstate(all="ignore"):
+        u = ((v - origin[None, :]).astype(np.float32) / spacing[None, :]).astype(np.float32)
+        fl = np.floor((u / np.float32(factor)).astype(np.float32))
+        top = (m - 1).astype(np.float32)[None, :]
+        cell = np.where(fl >= top, top, np.where(fl > 0, fl, np.float32(0))).astype(np.int64)      # a NaN falls into cell 0
+        qd = u.astype(np.float64) * 65536.0
+        ok = np.abs(qd) < 2.0 ** 62
+        q = np.where(ok, np.rint(np.where(ok, qd, 0.0)), 0.0).astype(np.int64)
+    cid = (cell[:, 0] * m[1] + cell[:, 1]) * m[2] + cell[:, 2]
+    ncl = int(m.prod())
+    sums = np.zeros((ncl, 3), dtype=np.int64)
+    np.add.at(sums, cid, q)
+    members = np.bincount(cid, minlength=ncl).astype(np.int64)
+    fc = cid[f]                                                                                     # [F, 3] cluster ids
+    keep = (fc[:, 0] != fc[:, 1]) & (fc[:, 1] != fc[:, 2]) & (fc[:, 0] != fc[:, 2])
+    used = np.zeros(ncl, dtype=bool)
+    used[fc[keep].reshape(-1)] = True
+    newid = np.cumsum(used) - 1
+    ids = np.nonzero(used)[0]
+    mean = sums[ids].astype(np.float64) / (members[ids].astype(np.float64) * 65536.0)[:, None]
+    v_out = (origin.astype(np.float64)[None, :] + mean * spacing.astype(np.float64)[None, :]).astype(np.float32)
+    f_out = newid[fc[keep]].astype(np.int32)
+    return v_out.reshape(-1, 3), f_out.reshape(-1, 3)

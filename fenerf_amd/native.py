@@ -1411,3 +1411,81 @@ def mesh_from_volume(vol, iso, origin=(0, 0, 0), spacing=(1, 1, 1)):
                                                C.c_void_p(vertices.data_ptr()) if vertices.numel() else None,
                                                C.c_void_p(faces.data_ptr()) if faces.numel() else None, _stream()))
     return vertices, faces
+
+
+def _components(v, iso):
+    """fenerf_volume_components on a contiguous fp32 device volume -> (labels int32 [n0,n1,n2], stats int64 [4], workspace)"""
+    n0, n1, n2 = v.shape
+    dev = v.device
+    nbytes = _lib.lib().fenerf_volume_components_workspace_bytes(n0, n1, n2)
+    ws = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
+    labels = torch.empty((n0, n1, n2), dtype=torch.int32, device=dev)
+    stats = torch.empty((4,), dtype=torch.int64, device=dev)
+    _lib.check(_lib.lib().fenerf_volume_components(_ptr(v), n0, n1, n2, float(iso), C.c_void_p(ws.data_ptr()), C.c_void_p(labels.data_ptr()),
+                                                   C.c_void_p(stats.data_ptr()), _stream()))
+    return labels, stats, ws
+
+
+def volume_components(vol, iso):
+    """Connected components of the inside set {vol >= iso} of a device volume [n0,n1,n2] under the 14-neighbourhood of the Kuhn tetrahedra's
+    edges (fenerf_volume_components, include/fenerf.h; mesh_emulation.components) -> (labels int32 [n0,n1,n2]: the smallest linear index of
+    the point's component, -1 outside; stats int64 [4]: inside points, components, label of the largest, its point count), on the device."""
+    assert vol.is_cuda and vol.dim() == 3
+    v = _f32(vol, vol.device)
+    with torch.cuda.device(vol.device):
+        labels, stats, _ = _components(v, iso)
+    return labels, stats
+
+
+def filter_volume(vol, iso, keep, out=None):
+    """vol with every inside point of a dropped component replaced by -inf (fenerf_volume_components + fenerf_volume_keep_components):
+    keep = "largest", or an int: every component of at least that many points stays.  -> (filtered volume, stats as volume_components), on
+    the device.  out = a contiguous fp32 device tensor of vol's shape to write into (it may be vol itself)."""
+    assert vol.is_cuda and vol.dim() == 3
+    if keep == "largest":
+        mode, min_points = _lib.KEEP_LARGEST, 1
+    elif isinstance(keep, int) and not isinstance(keep, bool):
+        mode, min_points = _lib.KEEP_MIN_POINTS, keep
+    else:
+        raise ValueError(f'filter_volume: keep is "largest" or a number of points, not {keep!r}')
+    dev = vol.device
+    v = _f32(vol, dev)
+    n0, n1, n2 = v.shape
+    if out is None:
+        out = torch.empty_like(v)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == v.shape
+    with torch.cuda.device(dev):
+        labels, stats, ws = _components(v, iso)
+        _lib.check(_lib.lib().fenerf_volume_keep_components(_ptr(v), C.c_void_p(labels.data_ptr()), C.c_void_p(ws.data_ptr()), n0, n1, n2, mode,
+                                                            int(min_points), C.c_void_p(out.data_ptr()), _stream()))
+    return out, stats
+
+
+def cluster_mesh(vertices, faces, origin, spacing, shape, factor):
+    """Vertex clustering of a device mesh (fenerf_mesh_cluster_count / fenerf_mesh_cluster_emit, include/fenerf.h; mesh_emulation.cluster): the
+    vertices of every factor^3 block of cells of the lattice `shape` in the frame origin / spacing merge into their mean; collapsed faces and
+    unreferenced vertices go.  -> (vertices [V',3] float32, faces [F',3] int32) on the device.  One host read (the counts) between the calls;
+    a face index outside [0, V) comes back with them and raises FenerfError (E_INVALID)."""
+    assert vertices.is_cuda and faces.is_cuda and vertices.dim() == 2 and vertices.shape[1] == 3 and faces.dim() == 2 and faces.shape[1] == 3
+    dev = vertices.device
+    v = _f32(vertices, dev)
+    f = faces.to(dtype=torch.int32).contiguous()
+    V, F = v.shape[0], f.shape[0]
+    n0, n1, n2 = (int(x) for x in shape)
+    factor = int(factor)
+    l = _lib.lib()
+    o3, s3 = (C.c_float * 3)(*(float(x) for x in origin)), (C.c_float * 3)(*(float(x) for x in spacing))
+    nbytes = l.fenerf_mesh_cluster_workspace_bytes(V, F, n0, n1, n2, factor)
+    ws = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
+    counts = torch.empty((3,), dtype=torch.int64, device=dev)
+    pv, pf = (C.c_void_p(v.data_ptr()) if V else None), (C.c_void_p(f.data_ptr()) if F else None)
+    with torch.cuda.device(dev):
+        _lib.check(l.fenerf_mesh_cluster_count(pv, V, pf, F, o3, s3, n0, n1, n2, factor, C.c_void_p(ws.data_ptr()), C.c_void_p(counts.data_ptr()), _stream()))
+        nv, nf, bad = (int(x) for x in to_host(counts))
+        if bad:
+            raise _lib.FenerfError(_lib.E_INVALID, f"fenerf_mesh_cluster_count: {bad} faces have an index outside [0, {V})")
+        v_out = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        f_out = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        _lib.check(l.fenerf_mesh_cluster_emit(pf, V, F, o3, s3, n0, n1, n2, factor, C.c_void_p(ws.data_ptr()), nv, nf,
+                                              C.c_void_p(v_out.data_ptr()) if nv else None, C.c_void_p(f_out.data_ptr()) if nf else None, _stream()))
+    return v_out, f_out

@@ -754,6 +754,56 @@ int fenerf_mesh_count(const float* vol, int n0, int n1, int n2, float iso, void*
 int fenerf_mesh_emit(const float* vol, int n0, int n1, int n2, float iso, const float origin[3], const float spacing[3], const void* workspace,
                      int64_t n_vertices, int64_t n_faces, float* vertices, int32_t* faces, void* stream);
 
+/* ---- mesh cleaning: connected components of the inside set, and vertex clustering (no model handle) ----
+ * replaces: the external step (skimage.measure.label, MeshLab) between the reference's density volume and a mesh one can open or print.
+ * Lattice conventions are those of the iso-surface section above: vol [dev] [n0][n1][n2] fp32, linear index i = (a * n1 + b) * n2 + c,
+ * inside(p) := vol[p] >= iso (a NaN is not inside), owned-edge directions d_k = (k & 1, (k >> 1) & 1, (k >> 2) & 1), k = 1 .. 7.
+ *
+ * Components.  Two inside points are adjacent when they differ by +d_k or -d_k for some k: the edges of the Kuhn tetrahedra, a
+ * 14-neighbourhood.  A component is a class of the transitive closure; its label is the smallest linear index in it (independent of the
+ * order of execution); an outside point has label -1.
+ * fenerf_volume_components_workspace_bytes: [dev] scratch for one lattice, about 4 bytes per point (0 for an invalid lattice).
+ * fenerf_volume_components: labels_dev [dev] int32 [n]; stats_dev [dev] int64 [4] = inside points, components, label of the largest
+ *   component (by point count; a tie goes to the smaller label; -1 without an inside point), its point count.  The workspace keeps the
+ *   stats and the point count of every component (exact integer sums, at the label's own index) for fenerf_volume_keep_components.
+ *   Enqueues only; no kernel waits for another workgroup, and the host iterates nothing.
+ * fenerf_volume_keep_components: vol, labels and workspace as fenerf_volume_components saw / left them.  mode FENERF_KEEP_LARGEST keeps the
+ *   largest component alone (min_points is checked and otherwise unused); FENERF_KEEP_MIN_POINTS keeps every component of at least
+ *   min_points points.  vol_out [dev] [n] = vol with every inside point of a dropped component replaced by -inf, everything else copied
+ *   bit for bit; vol_out may be vol.  Two components are never adjacent, so no edge of a dropped point crosses afterwards and the -inf
+ *   enters no arithmetic: fenerf_mesh_count / fenerf_mesh_emit on vol_out give exactly the sub-mesh of vol's mesh whose vertices sit on
+ *   edges with a kept inside end -- the same coordinate bits, renumbered in order, the faces in order.
+ * FENERF_E_INVALID: an axis below 2 points, more than 2^31 - 1 points, a NULL pointer, an unknown mode, min_points < 1.  Nothing is launched.
+ *
+ * Clustering.  vertices [dev] [V][3] fp32 and faces [dev] [F][3] int32 of a mesh in the frame origin / spacing [host] [3] of an
+ * n0 x n1 x n2 lattice; factor >= 2.  Per vertex and axis j: u_j = (x_j - origin_j) / spacing_j (an fp32 subtract, then an fp32 divide);
+ * cell_j = clamp(int(floorf(u_j / (float)factor)), 0, ceil((n_j - 1) / factor) - 1) (a NaN falls into cell 0); the cluster id is the
+ * linear index of (cell_0, cell_1, cell_2).  The representative of a cluster is the mean of its members, formed without float sums:
+ * q_j = llrint((double)u_j * 65536.0) (0 when |q_j| would reach 2^62 or u_j is not finite) is added into int64 sums, and
+ * x_j = (float)((double)origin_j + ((double)sum_j / ((double)count * 65536.0)) * (double)spacing_j): the same bits on every run.
+ * A face is re-indexed to its vertices' clusters and dropped when two of them are equal; the others keep their order and winding.
+ * Duplicate faces are NOT searched for: two faces that collapse onto the same three clusters both stay.  Clusters that no surviving face
+ * references are dropped; the new vertices are numbered by ascending cluster id.
+ * fenerf_mesh_cluster_workspace_bytes: [dev] scratch, about 36 bytes per cluster cell + 4 per vertex (0 for invalid arguments).
+ * fenerf_mesh_cluster_count: counts_dev [dev] int64 [3] = vertices out, faces out, faces with an index outside [0, V) (such a face is
+ *   never dereferenced).  Enqueues only; with F = 0 nothing is launched and the counts are 0.
+ * fenerf_mesh_cluster_emit: faces, V, F, the frame, factor and workspace as fenerf_mesh_cluster_count saw / left them; n_vertices / n_faces =
+ *   the first two counts (the caller reads them to size vertices_out [dev] [n_vertices][3] fp32 and faces_out [dev] [n_faces][3] int32;
+ *   either may be NULL when its count is 0).  This call WAITS for the stream once to compare them with what the workspace holds:
+ *   FENERF_E_INVALID if they differ, or if the third count is not 0.  An empty result launches nothing and returns FENERF_OK.
+ * FENERF_E_INVALID also: factor < 2, V or F outside [0, 2^31 - 1], the lattice refusals above, a NULL pointer. */
+#define FENERF_KEEP_LARGEST 0
+#define FENERF_KEEP_MIN_POINTS 1
+size_t fenerf_volume_components_workspace_bytes(int n0, int n1, int n2);
+int fenerf_volume_components(const float* vol, int n0, int n1, int n2, float iso, void* workspace, int32_t* labels_dev, int64_t* stats_dev, void* stream);
+int fenerf_volume_keep_components(const float* vol, const int32_t* labels, const void* workspace, int n0, int n1, int n2, int mode, int64_t min_points,
+                                  float* vol_out, void* stream);
+size_t fenerf_mesh_cluster_workspace_bytes(int64_t V, int64_t F, int n0, int n1, int n2, int factor);
+int fenerf_mesh_cluster_count(const float* vertices, int64_t V, const int32_t* faces, int64_t F, const float origin[3], const float spacing[3], int n0, int n1,
+                              int n2, int factor, void* workspace, int64_t* counts_dev, void* stream);
+int fenerf_mesh_cluster_emit(const int32_t* faces, int64_t V, int64_t F, const float origin[3], const float spacing[3], int n0, int n1, int n2, int factor,
+                             const void* workspace, int64_t n_vertices, int64_t n_faces, float* vertices_out, int32_t* faces_out, void* stream);
+
 /* Bytes of [dev] scratch fenerf_render_forward needs. */
 size_t fenerf_render_workspace_bytes(const FenerfModel* m, int B, int R, int N, int hierarchical);
 

@@ -16,6 +16,11 @@ callers.extract_mesh (marching tetrahedra at the density level --iso, default 10
 vertices) -> <output_dir>/<seed>.ply beside the .mrc.  `<prefix>ema.pth` next to the generator pickle is loaded and copied in (:103-104).
 
     python tools/extract_shapes.py <path/to/generator.pth> --seeds 3 --mesh --iso 10
+    python tools/extract_shapes.py <path/to/generator.pth> --seeds 3 --mesh --keep_largest --simplify 2
+
+--keep_largest / --min_component N drop detached blobs of density before meshing (only the largest connected component of
+{sigma >= iso}, or every component of at least N lattice points, stays); --simplify K merges the vertices of every K^3 block of cells
+(vertex clustering) before labels, colours and normals are evaluated.  All three are off by default and need --mesh.
 """
 import argparse
 import os
@@ -35,13 +40,30 @@ def build_parser():
     parser.add_argument('--no_ema', action='store_true', help='use the raw generator weights (not in the reference: it always loads <prefix>ema.pth)')
     parser.add_argument('--mesh', action='store_true', help='also write <seed>.ply: the labelled, coloured iso-surface (not in the reference)')
     parser.add_argument('--iso', type=float, default=10.0, help='density level of the --mesh surface')
+    parser.add_argument('--keep_largest', action='store_true', help='--mesh: keep only the largest connected component of {sigma >= iso}')
+    parser.add_argument('--min_component', type=int, default=None, metavar='N', help='--mesh: drop components of fewer than N lattice points')
+    parser.add_argument('--simplify', type=int, default=None, metavar='K', help='--mesh: merge the vertices of every K^3 block of cells (K >= 2)')
     return parser
 
 
+def mesh_options(opt):
+    """the keep= / simplify= arguments of callers.extract_mesh the flags ask for"""
+    if opt.keep_largest and opt.min_component is not None:
+        raise SystemExit("--keep_largest and --min_component exclude each other")
+    if opt.min_component is not None and opt.min_component < 1:
+        raise SystemExit("--min_component needs N >= 1")
+    if opt.simplify is not None and opt.simplify < 2:
+        raise SystemExit("--simplify needs K >= 2")
+    keep = "largest" if opt.keep_largest else (opt.min_component if opt.min_component is not None else "all")
+    return dict(keep=keep, simplify=opt.simplify)
+
+
 def write_mesh(callers, imageio_lite, path, generator, opt, **latent):
-    mesh = callers.extract_mesh(generator, latent.pop('z', None), cube_length=opt.cube_size, voxel_resolution=opt.voxel_resolution, iso=opt.iso, **latent)
+    mesh = callers.extract_mesh(generator, latent.pop('z', None), cube_length=opt.cube_size, voxel_resolution=opt.voxel_resolution, iso=opt.iso,
+                                **mesh_options(opt), **latent)
     imageio_lite.write_ply(path, mesh['vertices'], mesh['faces'], normal=mesh['normal'], rgb=mesh['rgb'], label=mesh['label'])
-    print(f"  mesh at sigma = {opt.iso:g}: {len(mesh['vertices'])} vertices, {len(mesh['faces'])} faces -> {path}")
+    cleaned = f" ({mesh['components']} components before filtering)" if 'components' in mesh else ""
+    print(f"  mesh at sigma = {opt.iso:g}: {len(mesh['vertices'])} vertices, {len(mesh['faces'])} faces{cleaned} -> {path}")
 
 
 def main(argv=None):
