@@ -27,7 +27,9 @@ import numpy as np
 # ---------------------------------------------------------------------------
 def get_initial_rays_trig(n, num_steps, fov, resolution, ray_start, ray_end, dtype=np.float32):
     W, H = resolution
-    # torch.linspace in fp32: start + i*step for the first half, end - (N-1-i)*step for the second
+    # torch.linspace in fp32: start + i*step for the first half, end - (N-1-i)*step for the second.  The pixel grid rounds the product on
+    # its own, as the ray-setup kernel does, and so differs from torch (which fuses it) by one ulp at about half of its values; the sample
+    # depths below are fused like torch's (see _torch_linspace)
     xs = _torch_linspace(-1.0, 1.0, W, dtype)
     ys = _torch_linspace(1.0, -1.0, H, dtype)
     # meshgrid(indexing='ij') then .T.flatten(): ray p = i*W + j has x = xs[j], y = ys[i]
@@ -36,7 +38,7 @@ def get_initial_rays_trig(n, num_steps, fov, resolution, ray_start, ray_end, dty
     z = -np.ones_like(x) / dtype(np.tan((2 * math.pi * fov / 360) / 2))
     d = np.stack([x, y, z], -1).astype(dtype)
     d = d / np.sqrt((d * d).sum(-1, keepdims=True, dtype=dtype))
-    z_vals = _torch_linspace(ray_start, ray_end, num_steps, dtype).reshape(1, num_steps, 1).repeat(W * H, 0)
+    z_vals = _torch_linspace(ray_start, ray_end, num_steps, dtype, fused=True).reshape(1, num_steps, 1).repeat(W * H, 0)
     points = d[:, None, :] * z_vals
     points = np.broadcast_to(points, (n,) + points.shape).copy()
     z_vals = np.broadcast_to(z_vals, (n,) + z_vals.shape).copy()
@@ -44,16 +46,20 @@ def get_initial_rays_trig(n, num_steps, fov, resolution, ray_start, ray_end, dty
     return points, z_vals, rays_d
 
 
-def _torch_linspace(start, end, steps, dtype=np.float32):
-    """torch.linspace's CPU kernel: step=(end-start)/(steps-1); i<steps/2 ? start+step*i : end-step*(steps-1-i)."""
+def _torch_linspace(start, end, steps, dtype=np.float32, fused=False):
+    """torch.linspace's CPU kernel: step=(end-start)/(steps-1); i<steps/2 ? start+step*i : end-step*(steps-1-i).
+    fused: each of the two as ONE fused multiply-add, as torch's AVX2 / AVX-512 builds contract them -- the product and the sum formed in
+    fp64 (exact for fp32 operands of these magnitudes) and rounded once.  The sample depths are fused: the depths the reference recorded
+    (tests/golden, 24 samples) are those bits, a separately rounded product is one ulp off at sample 9."""
     start, end = dtype(start), dtype(end)
     if steps == 1:
         return np.array([start], dtype=dtype)
     step = dtype((end - start) / dtype(steps - 1))
     i = np.arange(steps)
     half = steps // 2
-    lo = (start + step * i.astype(dtype)).astype(dtype)
-    hi = (end - step * (steps - 1 - i).astype(dtype)).astype(dtype)
+    wide = np.float64 if fused else dtype
+    lo = (wide(start) + wide(step) * i.astype(wide)).astype(dtype)
+    hi = (wide(end) - wide(step) * (steps - 1 - i).astype(wide)).astype(dtype)
     return np.where(i < half, lo, hi).astype(dtype)
 
 
