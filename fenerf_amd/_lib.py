@@ -181,6 +181,12 @@ _SIGS = {
     "fenerf_mesh_cluster_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i, _i]),
     "fenerf_mesh_cluster_count": (_i, [_vp, _i64, _vp, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _i, _vp, _vp, _vp]),
     "fenerf_mesh_cluster_emit": (_i, [_vp, _i64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
+    # baked radiance lattice (fenerf_volume.hip): trilinear rows of a channels-last lattice, and the render that reads them
+    "fenerf_volume_sample": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _i64, _vp, _vp, _vp]),
+    "fenerf_volume_sample_rays": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "fenerf_volume_render_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "fenerf_volume_render": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _i, _i, _i, _i] + [_vp] * 6 +
+                             [C.POINTER(FenerfCompositeOpts)] + [_vp] * 4 + [_vp, _sz, _vp]),
     "fenerf_composite_backward": (_i, [_i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(FenerfCompositeOpts), _vp, _vp, _vp, _vp]),
     "fenerf_render_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "fenerf_render_forward": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 10 + [C.POINTER(FenerfCompositeOpts)] + [_vp] * 4 + [_vp, _sz, _vp]),

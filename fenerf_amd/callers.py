@@ -97,14 +97,17 @@ def _latent_dims(generator, default=256):
 
 
 def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.25, 0.0, 0.25, 0.5), image_size=256,
-                     ray_step_multiplier=2, lock_view_dependence=False, z_dim=None, latents=None):
+                     ray_step_multiplier=2, lock_view_dependence=False, z_dim=None, latents=None, baked=None):
     """Five yaw angles of one identity (render_multiview_images_double_semantic.py:66-85).
     -> (images [V,3,S,S] in [-1,1], segmaps [V,3,S,S] in [0,1]) on the CPU.
-    latents: optional (z_geo, z_app) instead of the seeded draws (tests teacher-force the reference's CPU-generator values)."""
+    latents: optional (z_geo, z_app) instead of the seeded draws (tests teacher-force the reference's CPU-generator values).
+    baked: a lattice resolution -- the identity is baked once (bake_field, view direction locked) and every view is rendered from the
+    lattice by BakedField.render with the exact route's rays and draws: an approximation.  None = the exact renders."""
     kw = multiview_kwargs(curriculum, image_size, ray_step_multiplier, lock_view_dependence)
     h_mean = kw["h_mean"]
     zg_dim, za_dim = (z_dim, z_dim) if z_dim is not None else _latent_dims(generator)
     images, segmaps = [], []
+    field = None
     for a in face_angles:
         kw["h_mean"] = a + h_mean
         torch.manual_seed(seed)
@@ -113,7 +116,13 @@ def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.
         if latents is not None:
             z_geo, z_app = (torch.as_tensor(t, dtype=torch.float32, device=device) for t in latents)
         with torch.no_grad():
-            img, _ = generator.staged_forward(z_geo, z_app, **kw)
+            if baked is None:
+                img, _ = generator.staged_forward(z_geo, z_app, **kw)
+            else:
+                avg = generator.generate_avg_frequencies()          # staged_forward's draws before its render, per view
+                if field is None:
+                    field = _baked_multiview_field(generator, z_geo, z_app, avg, kw, baked)
+                img, _, _ = field.render(generator, **kw)
         images.append(img[:, -3:])
         segmaps.append(mask2color(img[:, :-3], device, scale=255.0))
     return torch.cat(images), torch.cat(segmaps)
@@ -276,6 +285,143 @@ def extract_mesh(generator, z_geo, z_app=None, *, film=None, voxel_resolution=25
     return mesh
 
 
+# ---- many views of one identity: bake the field into a lattice once, render every view by trilinear lookup -----------
+BAKED_LD = 24                     # floats per lattice point: the 22 channels padded to whole 16-byte pieces (include/fenerf.h)
+BAKED_OUTSIDE_SIGMA = -1e30       # density of a sample outside the lattice: finite, and weight exactly 0 under relu and softplus alike
+
+
+def baked_cube_length(fov, ray_start, ray_end, radius=1.0, num_steps=None):
+    """Side of the smallest origin-centred cube that holds every sample of every ray for ANY yaw and pitch of a camera on the sphere of
+    `radius` looking at the origin: two times the largest distance from the origin of a sample on a corner ray (the pixel grid spans
+    [-1, 1]^2 at depth 1 / tan(fov / 2), so tan(theta_c) = sqrt(2) tan(fov / 2)) at depth ray_start or ray_end.  Pure host arithmetic.
+    num_steps: the stratified jitter moves a sample by up to half a bin, (ray_end - ray_start) / (num_steps - 1) / 2, beyond either end
+    (perturb_points); given the coarse sample count the cube holds the jittered samples too (the resampled depths lie between coarse
+    samples).  Without it the cube holds the unjittered depths; a sample the jitter pushes past it renders as empty space."""
+    import math
+    margin = 0.0 if num_steps is None or num_steps < 2 else (ray_end - ray_start) / (num_steps - 1) / 2
+    cos_c = 1.0 / math.sqrt(1.0 + 2.0 * math.tan(math.radians(fov) / 2) ** 2)
+    far = max(math.sqrt(radius * radius + z * z - 2.0 * radius * z * cos_c) for z in (ray_start - margin, ray_end + margin))
+    return 2.0 * far
+
+
+class BakedField:
+    """One identity's radiance field on a lattice (bake_field): vol [n0,n1,n2,ld] on the device, the first C floats of a lattice point =
+    the SIREN's row [labels | rgb | sigma] under a locked view direction; lattice point i_k of axis k lies at origin[k] + i_k * spacing[k]
+    (coordinate column k).  film = the (freq_geo, phase_geo, freq_app, phase_app) it was baked from.  An approximation: trilinear
+    interpolation at the lattice's resolution stands in for the network."""
+
+    def __init__(self, vol, origin, spacing, C, film, outside_last=BAKED_OUTSIDE_SIGMA):
+        self.vol, self.origin, self.spacing = vol, tuple(float(x) for x in origin), tuple(float(x) for x in spacing)
+        self.C, self.ld = int(C), int(vol.shape[-1])
+        self.film = film
+        self.outside_last = float(outside_last)
+
+    def sample(self, points):
+        """points [..., 3] on the device -> rows [..., C] (native.volume_sample)"""
+        if torch.is_grad_enabled() and points.requires_grad:
+            raise RuntimeError("BakedField.sample: the baked route is no-grad only")
+        return native.volume_sample(self.vol, self.origin, self.spacing, points, self.outside_last, self.C)
+
+    def _field_render(self, origins, dirs, z_coarse, u, noise_coarse, noise_final, fg, pg, fa, pa, opts, hierarchical=True, lock_view=False,
+                      want_weights=False, want_wsum=False):
+        """NativeModel.render's signature: the FiLM parameters and the view direction are baked in"""
+        return native.volume_render(self.vol, self.origin, self.spacing, origins, dirs, z_coarse, u, noise_coarse, noise_final, opts,
+                                    self.outside_last, self.C, hierarchical=hierarchical, want_weights=want_weights, want_wsum=want_wsum)
+
+    def render(self, generator, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean, hierarchical_sample=True,
+               sample_dist=None, **kwargs):
+        """staged_forward_with_frequencies(lock_view_dependence=True) of the baked identity with the two SIREN passes replaced by lattice
+        lookups: the generator's own _render (the same rays, draws in the same order, composite options, fill modes) and image epilogue.
+        -> (pixels [B,C',S,S], depth [B,S,S], third) on the CPU, as staged_forward_with_frequencies returns them.  No-grad only."""
+        tensors = [t for t in (*self.film, h_mean, v_mean) if isinstance(t, torch.Tensor)]
+        if any(t.requires_grad for t in tensors):
+            raise RuntimeError("BakedField.render: the baked route is no-grad only (a FiLM tensor or a pose requires grad)")
+        for k in ("psi", "lock_view_dependence", "max_batch_size", "depth_map", "near_clip", "far_clip"):      # staged_forward's own arguments
+            kwargs.pop(k, None)
+        B = self.film[0].shape[0]
+        with torch.no_grad():
+            pixels, depth, third, _, _ = generator._render(self.film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean,
+                                                           v_mean, hierarchical_sample, sample_dist, True, kwargs, use_fill=True, third="auto",
+                                                           field_render=self._field_render)
+            depth_map = native.to_host(depth.reshape(B, img_size, img_size).contiguous())
+            third = native.to_host(third.reshape((B, img_size, img_size, -1)).permute(0, 3, 1, 2).contiguous() * 2 - 1)
+            pixels = native.to_host(generator._finish_scaled(pixels, B, img_size))
+        return pixels, depth_map, third
+
+
+def bake_field(generator, z_geo, z_app=None, *, film=None, resolution=256, center=(0, 0, 0), cube_length, psi=0.5, max_points=1 << 24):
+    """Evaluates one identity's field ONCE on a resolution^3 lattice of the cube of side cube_length around `center` (baked_cube_length
+    gives the side that holds a camera's samples) and keeps all C channels -> BakedField.  FiLM parameters exactly as extract_mesh: the
+    truncated z route (generate_avg_frequencies, psi), or film= (the meta dict of sample_generator_wth_frequencies_phase_shifts; z_geo /
+    z_app / psi are then ignored).  View direction locked to (0, 0, -1).  Lattice points are origin + i * spacing per coordinate column
+    (one fp32 multiply, one fp32 add): the statement the sampler inverts.  Evaluated in slabs of at most max_points points along axis 0,
+    padded to whole 32-point tiles.  Memory: resolution^3 x 96 bytes."""
+    n = int(resolution)
+    if n < 2:
+        raise ValueError("bake_field: resolution must be at least 2")
+    siren = generator.siren
+    with torch.no_grad():
+        if film is None:
+            z_app = z_geo if z_app is None else z_app
+            device = z_geo.device
+            avg_fg, avg_pg, avg_fa, avg_pa = generator.generate_avg_frequencies()
+            raw_fg, raw_pg = siren.geo_mapping_network(z_geo)
+            raw_fa, raw_pa = siren.app_mapping_network(z_app)
+            fg, pg = avg_fg + psi * (raw_fg - avg_fg), avg_pg + psi * (raw_pg - avg_pg)
+            fa, pa = avg_fa + psi * (raw_fa - avg_fa), avg_pa + psi * (raw_pa - avg_pa)
+        else:
+            device = generator.device
+            fg, pg = film["truncated_frequencies_geo"], film["truncated_phase_shifts_geo"]
+            fa, pa = film["truncated_frequencies_app"], film["truncated_phase_shifts_app"]
+        if any(t.requires_grad for t in (fg, pg, fa, pa)):
+            raise RuntimeError("bake_field: the baked route is no-grad only (a FiLM tensor requires grad)")
+        if fg.shape[0] != 1:
+            raise ValueError("bake_field: one identity per lattice (FiLM batch of 1)")
+        device = torch.device(device)
+        spacing = float(cube_length) / (n - 1)
+        origin = tuple(float(c) - float(cube_length) / 2 for c in center)
+        nat = siren.native(device)
+        C_out = int(siren.output_dim)
+        ld = max(BAKED_LD, (C_out + 3) // 4 * 4)
+        vol = torch.zeros((n, n, n, ld), dtype=torch.float32, device=device)
+        idx = torch.arange(n, dtype=torch.float32, device=device)
+        sp = torch.tensor(spacing, dtype=torch.float32, device=device)
+        axis = [idx * sp + torch.tensor(origin[k], dtype=torch.float32, device=device) for k in range(3)]      # origin + i * spacing
+        slab = max(1, min(n, int(max_points) // (n * n)))
+        for a0 in range(0, n, slab):
+            a1 = min(n, a0 + slab)
+            pts = torch.stack(torch.meshgrid(axis[0][a0:a1], axis[1], axis[2], indexing="ij"), dim=-1).reshape(-1, 3)
+            P = pts.shape[0]
+            pad = (-P) % 32
+            if pad:
+                pts = torch.cat([pts, pts[-1:].expand(pad, -1)])
+            rows = nat.siren_forward(pts[None].contiguous(), None, fg, pg, fa, pa)[0, :P]          # None = locked view dir
+            vol[a0:a1, :, :, :C_out] = rows.reshape(a1 - a0, n, n, C_out)
+            del rows, pts
+    return BakedField(vol, origin, (spacing,) * 3, C_out, (fg, pg, fa, pa))
+
+
+def _baked_multiview_field(generator, z_geo, z_app, avg, kw, resolution):
+    """the lattice render_multiview's views read: staged_forward's truncated FiLM parameters (psi of the kwargs bag; avg = what
+    generate_avg_frequencies returned for this view's generator state), in the cube that holds the camera's samples"""
+    avg_fg, avg_pg, avg_fa, avg_pa = avg
+    with torch.no_grad():
+        raw_fg, raw_pg = generator.siren.geo_mapping_network(z_geo)
+        raw_fa, raw_pa = generator.siren.app_mapping_network(z_app)
+        psi = kw.get("psi", 1)
+        film = dict(truncated_frequencies_geo=avg_fg + psi * (raw_fg - avg_fg), truncated_phase_shifts_geo=avg_pg + psi * (raw_pg - avg_pg),
+                    truncated_frequencies_app=avg_fa + psi * (raw_fa - avg_fa), truncated_phase_shifts_app=avg_pa + psi * (raw_pa - avg_pa))
+    cube = baked_cube_length(kw["fov"], kw["ray_start"], kw["ray_end"], num_steps=kw["num_steps"])
+    return bake_field(generator, None, film=film, resolution=resolution, cube_length=cube)
+
+
+def _baked_inversion_field(generator, film, render_options, resolution):
+    """the lattice the inversion renders read: film = film_from_inversion's (freq_geo, freq_app, phase_geo, phase_app)"""
+    meta = dict(truncated_frequencies_geo=film[0], truncated_frequencies_app=film[1], truncated_phase_shifts_geo=film[2], truncated_phase_shifts_app=film[3])
+    cube = baked_cube_length(render_options["fov"], render_options["ray_start"], render_options["ray_end"], num_steps=render_options["num_steps"])
+    return bake_field(generator, None, film=meta, resolution=resolution, cube_length=cube)
+
+
 # ---- the inversion script's host pieces (inverse_render_double_semantic.py) ------------------------------------------------------------
 COLOR_MAP_COMPLETE_KEYS = 19      # labels 0 (background) .. 18 of the script's COLOR_MAP_COMPLETE (:50-69); COLOR_MAP has 1 .. 18
 
@@ -382,9 +528,11 @@ def _inversion_pose(pose):
     return None if pose is None else (float(pose[0]), float(pose[1]))
 
 
-def render_inversion_views(generator, meta, render_options, angles=(0.0,), max_batch_size=2400000, lock_view_dependence=False, pose=None):
+def render_inversion_views(generator, meta, render_options, angles=(0.0,), max_batch_size=2400000, lock_view_dependence=False, pose=None, baked=None):
     """staged_forward_with_frequencies of an inversion state at yaws pi/2 + angle (:419-431, :441-446) -> [(angle, frame [1,22,S,S])].
-    pose: (yaw, pitch) to centre the angles on instead -- what inverse_render(optimize_pose=True) recovered."""
+    pose: (yaw, pitch) to centre the angles on instead -- what inverse_render(optimize_pose=True) recovered.
+    baked: a lattice resolution -- bake the inverted identity once (view direction locked) and render every view from the lattice
+    (BakedField.render: an approximation).  None = the exact renders."""
     import math
     film = film_from_inversion(meta)
     pose = _inversion_pose(pose)
@@ -393,19 +541,23 @@ def render_inversion_views(generator, meta, render_options, angles=(0.0,), max_b
     centre = math.pi / 2 if pose is None else pose[0]
     out = []
     with torch.no_grad():
+        field = None if baked is None else _baked_inversion_field(generator, film, render_options, baked)
         for angle in angles:
-            img, _, _ = generator.staged_forward_with_frequencies(*film, h_mean=centre + angle, max_batch_size=max_batch_size,
-                                                                  lock_view_dependence=lock_view_dependence, **render_options)
+            if field is not None:
+                img, _, _ = field.render(generator, h_mean=centre + angle, **render_options)
+            else:
+                img, _, _ = generator.staged_forward_with_frequencies(*film, h_mean=centre + angle, max_batch_size=max_batch_size,
+                                                                      lock_view_dependence=lock_view_dependence, **render_options)
             out.append((angle, img))
     return out
 
 
-def render_inversion_recon(generator, meta, render_options, trajectory, max_batch_size=2400000, lock_view_dependence=False, pose=None):
+def render_inversion_recon(generator, meta, render_options, trajectory, max_batch_size=2400000, lock_view_dependence=False, pose=None, baked=None):
     """The frames of run_render_recon_video (:462-501): per trajectory entry one staged render of the inverted identity at (pitch, yaw) --
     the trajectory's fov is NOT applied (the reference sets only h_mean / v_mean) -- as uint8 [S, 3 S, 3] RGB panels
     [image | label colours | 0.5 / 0.5 blend] (the reference hands them to cv2 as BGR).
     pose: (yaw, pitch) the trajectory -- written around the frontal (pi / 2, pi / 2) -- is moved to: what inverse_render(optimize_pose=True)
-    recovered."""
+    recovered.  baked: a lattice resolution -- bake once, render every frame from the lattice (as render_inversion_views)."""
     import math
     from . import imageio_lite
     film = film_from_inversion(meta)
@@ -415,9 +567,13 @@ def render_inversion_recon(generator, meta, render_options, trajectory, max_batc
     frames = []
     to_u8 = lambda t: imageio_lite.to_uint8_hwc(imageio_lite.make_grid(t, normalize=True))     # tensor_to_PIL (:114-119)
     with torch.no_grad():
+        field = None if baked is None else _baked_inversion_field(generator, film, kw, baked)
         for _, pitch, yaw, _ in trajectory:
             kw.update(h_mean=float(yaw) + d_yaw, v_mean=float(pitch) + d_pitch)
-            frame, _, _ = generator.staged_forward_with_frequencies(*film, max_batch_size=max_batch_size, lock_view_dependence=lock_view_dependence, **kw)
+            if field is not None:
+                frame, _, _ = field.render(generator, **kw)
+            else:
+                frame, _, _ = generator.staged_forward_with_frequencies(*film, max_batch_size=max_batch_size, lock_view_dependence=lock_view_dependence, **kw)
             image, sem = to_u8(frame[:, -3:].cpu()), to_u8(mask2color(frame[:, :-3], generator.device))
             blend = image * 0.5 + sem * 0.5
             frames.append(np.concatenate([image, sem, blend], axis=1).astype("uint8"))

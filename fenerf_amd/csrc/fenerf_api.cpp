@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -1275,6 +1276,126 @@ extern "C" int fenerf_mesh_cluster_emit(const int32_t* faces, int64_t V, int64_t
     return fail(FENERF_E_INVALID, "fenerf_mesh_cluster_emit: the workspace holds " + std::to_string(held[0]) + " vertices and " + std::to_string(held[1]) +
                                       " faces, the call says " + std::to_string((long long)n_vertices) + " and " + std::to_string((long long)n_faces));
   { PhaseScope ph(PH_OTHER, stream); return launch_mesh_cluster_emit(faces, V, F, origin, spacing, n0, n1, n2, factor, workspace, n_vertices, n_faces, vertices_out, faces_out, stream); }
+}
+
+// ---- baked radiance lattice (fenerf_volume.hip) ----
+namespace {
+// the lattice arguments every fenerf_volume_* entry shares: checked, then copied into the kernel's parameter block
+int volume_params(const char* who, const float* vol, int n0, int n1, int n2, int C, int ld, const float* origin, const float* spacing, float outside_last,
+                  VolumeParams* p) {
+  if (int rc = check_lattice(who, n0, n1, n2)) return rc;
+  if (!vol || !origin || !spacing) return fail(FENERF_E_INVALID, std::string(who) + ": vol / origin / spacing is NULL");
+  if (C < 1 || C > 64 || ld < C) return fail(FENERF_E_INVALID, std::string(who) + ": need 1 <= C <= 64 and ld >= C");
+  for (int k = 0; k < 3; ++k)
+    if (!(std::isfinite(spacing[k]) && spacing[k] > 0.f)) return fail(FENERF_E_INVALID, std::string(who) + ": spacing must be finite and positive");
+  memset(p, 0, sizeof(*p));
+  p->vol = vol; p->n0 = n0; p->n1 = n1; p->n2 = n2; p->C = C; p->ld = ld;
+  for (int k = 0; k < 3; ++k) { p->origin[k] = origin[k]; p->spacing[k] = spacing[k]; }
+  p->outside_last = outside_last;
+  return FENERF_OK;
+}
+int run_volume_rays(VolumeParams p, long long BR, int N, const float* origins, const float* dirs, const float* z, float* rows, void* stream) {
+  p.P = BR * N; p.N = N; p.origins = origins; p.dirs = dirs; p.z = z; p.rows = rows;
+  PhaseScope ph(PH_OTHER, stream);
+  return launch_volume_sample(p, stream);
+}
+struct VolumeRenderWs {
+  size_t coarse, fine, wts, zf, total;
+};
+VolumeRenderWs volume_render_ws(int B, int R, int N, int C, int hier) {
+  VolumeRenderWs w;
+  const size_t pts = (size_t)B * R * N;
+  size_t off = 0;
+  w.coarse = off; off += align_up(pts * C * sizeof(float), 256);
+  w.fine = off; off += hier ? align_up(pts * C * sizeof(float), 256) : 0;
+  w.wts = off; off += hier ? align_up(pts * sizeof(float), 256) : 0;
+  w.zf = off; off += hier ? align_up(pts * sizeof(float), 256) : 0;
+  w.total = off;
+  return w;
+}
+}  // namespace
+
+extern "C" int fenerf_volume_sample(const float* vol, int n0, int n1, int n2, int C, int ld, const float origin[3], const float spacing[3],
+                                    float outside_last, int64_t P, const float* points, float* rows, void* stream) {
+  VolumeParams p;
+  if (int rc = volume_params("fenerf_volume_sample", vol, n0, n1, n2, C, ld, origin, spacing, outside_last, &p)) return rc;
+  if (P < 0) return fail(FENERF_E_INVALID, "fenerf_volume_sample: negative count");
+  if (P == 0) return FENERF_OK;
+  if (!points || !rows) return fail(FENERF_E_INVALID, "fenerf_volume_sample: points / rows is NULL");
+  p.P = P; p.points = points; p.rows = rows;
+  { PhaseScope ph(PH_OTHER, stream); return launch_volume_sample(p, stream); }
+}
+
+extern "C" int fenerf_volume_sample_rays(const float* vol, int n0, int n1, int n2, int C, int ld, const float origin[3], const float spacing[3],
+                                         float outside_last, int B, int R, int N, const float* origins, const float* dirs, const float* z,
+                                         float* rows, void* stream) {
+  VolumeParams p;
+  if (int rc = volume_params("fenerf_volume_sample_rays", vol, n0, n1, n2, C, ld, origin, spacing, outside_last, &p)) return rc;
+  if (B < 0 || R < 0 || N < 0) return fail(FENERF_E_INVALID, "fenerf_volume_sample_rays: negative count");
+  if ((long long)B * R * N == 0) return FENERF_OK;
+  if (!origins || !dirs || !z || !rows) return fail(FENERF_E_INVALID, "fenerf_volume_sample_rays: origins / dirs / z / rows is NULL");
+  return run_volume_rays(p, (long long)B * R, N, origins, dirs, z, rows, stream);
+}
+
+extern "C" size_t fenerf_volume_render_workspace_bytes(int B, int R, int N, int C, int hierarchical) {
+  if (B <= 0 || R <= 0 || N <= 0 || C < 2 || C > 64) return 0;
+  return volume_render_ws(B, R, N, C, hierarchical).total;
+}
+
+extern "C" int fenerf_volume_render(const float* vol, int n0, int n1, int n2, int C, int ld, const float origin[3], const float spacing[3],
+                                    float outside_last, int B, int R, int N, int hierarchical, const float* origins, const float* dirs,
+                                    const float* z_coarse, const float* u, const float* noise_coarse, const float* noise_final,
+                                    const FenerfCompositeOpts* opts, float* out_rgb, float* out_depth, float* out_weights, float* out_wsum,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  VolumeParams vp;
+  if (int rc = volume_params("fenerf_volume_render", vol, n0, n1, n2, C, ld, origin, spacing, outside_last, &vp)) return rc;
+  if (int rc = check_opts(opts)) return rc;
+  if (C < 2) return fail(FENERF_E_INVALID, "fenerf_volume_render: need C >= 2 (colour channels and a density)");
+  if (B < 0 || R < 0 || N < 0) return fail(FENERF_E_INVALID, "fenerf_volume_render: negative count");
+  const int M = hierarchical ? 2 * N : N;
+  if (N < 1 || M > FENERF_MAX_RAY_SAMPLES)
+    return fail(FENERF_E_INVALID, "fenerf_volume_render: 1 to 1024 samples per ray (512 + 512 hierarchical; FENERF_MAX_RAY_SAMPLES)");
+  if (hierarchical && N < 3) return fail(FENERF_E_INVALID, "fenerf_volume_render: hierarchical sampling needs num_steps >= 3");
+  if (!origins || !dirs || !z_coarse || !out_rgb) return fail(FENERF_E_INVALID, "fenerf_volume_render: origins / dirs / z_coarse / out_rgb is NULL");
+  if (hierarchical && !u) return fail(FENERF_E_INVALID, "fenerf_volume_render: hierarchical sampling needs u");
+  if (opts->fill_mode == FENERF_FILL_EVAL_WHITE_BACK && C != 4) return fail(FENERF_E_INVALID, "eval_white_back needs a 3-channel model");
+  const long long BR = (long long)B * R;
+  if (BR == 0) return FENERF_OK;
+  const VolumeRenderWs ws = volume_render_ws(B, R, N, C, hierarchical);
+  if (!workspace || workspace_bytes < ws.total) return fail(FENERF_E_INVALID, "fenerf_volume_render: workspace too small (see fenerf_volume_render_workspace_bytes)");
+  char* base = (char*)workspace;
+  float* coarse = (float*)(base + ws.coarse);
+  int rc = run_volume_rays(vp, BR, N, origins, dirs, z_coarse, coarse, stream);      // coarse pass
+  if (rc) return rc;
+  CompositeParams cp;
+  memset(&cp, 0, sizeof(cp));
+  if (!hierarchical) {
+    cp.BR = BR; cp.M = N; cp.C = C; cp.N = N;
+    cp.rows_a = coarse; cp.z_a = z_coarse; cp.noise = noise_final; cp.o = *opts;
+    cp.out_rgb = out_rgb; cp.out_depth = out_depth; cp.out_weights = out_weights; cp.out_wsum = out_wsum;
+    cp.out_ch = out_channels(C, opts);
+    return run_composite(cp, false, stream);
+  }
+  float* fine = (float*)(base + ws.fine);
+  float* wts = (float*)(base + ws.wts);
+  float* zf = (float*)(base + ws.zf);
+  cp.BR = BR; cp.M = N; cp.C = C; cp.N = N;                  // coarse weights: fenerf_composite without a colour output
+  cp.rows_a = coarse; cp.z_a = z_coarse; cp.noise = noise_coarse;
+  cp.o.clamp_mode = opts->clamp_mode; cp.o.noise_std = opts->noise_std;
+  cp.out_weights = wts;
+  cp.out_ch = C - 1; cp.sigma_only = 1;
+  rc = run_composite(cp, false, stream);
+  if (rc) return rc;
+  { PhaseScope ph(PH_RESAMPLE, stream); rc = launch_resample(BR, N, z_coarse, wts, u, zf, stream); }
+  if (rc) return rc;
+  rc = run_volume_rays(vp, BR, N, origins, dirs, zf, fine, stream);                  // fine pass
+  if (rc) return rc;
+  memset(&cp, 0, sizeof(cp));                                // merge + final composite
+  cp.BR = BR; cp.M = 2 * N; cp.C = C; cp.N = N;
+  cp.rows_a = fine; cp.rows_b = coarse; cp.z_a = zf; cp.z_b = z_coarse; cp.noise = noise_final; cp.o = *opts;
+  cp.out_rgb = out_rgb; cp.out_depth = out_depth; cp.out_weights = out_weights; cp.out_wsum = out_wsum;
+  cp.out_ch = out_channels(C, opts);
+  return run_composite(cp, true, stream);
 }
 
 // workspace layout of fenerf_render_forward

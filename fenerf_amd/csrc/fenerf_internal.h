@@ -244,6 +244,22 @@ int launch_mesh_cluster_count(const float* vertices, long long V, const int* fac
                               int n2, int factor, void* workspace, long long* counts_dev, void* stream);
 int launch_mesh_cluster_emit(const int* faces, long long V, long long F, const float* origin, const float* spacing, int n0, int n1, int n2, int factor,
                              const void* workspace, long long n_vertices, long long n_faces, float* vertices_out, int* faces_out, void* stream);
+// fenerf_volume.hip: trilinear rows of a channels-last lattice vol [n0][n1][n2][ld] at explicit points (points != nullptr) or at
+// origins + dirs * z (include/fenerf.h "baked radiance lattice")
+struct VolumeParams {
+  const float* vol;
+  int n0, n1, n2, C, ld;
+  float origin[3], spacing[3];
+  float outside_last;      // channel C - 1 of a point outside the lattice (its other channels are 0)
+  long long P;             // rows: points, or B * R * N ray samples
+  const float* points;     // [P][3] or nullptr
+  const float* origins;    // [B*R][3]
+  const float* dirs;       // [B*R][3]
+  const float* z;          // [B*R][N]
+  int N;
+  float* rows;             // [P][C]
+};
+int launch_volume_sample(const VolumeParams& p, void* stream);
 int launch_pad_rows(const float* src, float* dst, long long nb, long long P, long long Pp, int C, bool to_padded, void* stream);
 int launch_multi_add(const MultiAdd& J, void* stream);
 int launch_film_fold(const FilmFold& J, void* stream);

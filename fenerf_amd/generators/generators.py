@@ -93,9 +93,11 @@ class _Generator3dBase(nn.Module):
         return super().train(mode)
 
     def _render(self, film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
-                hierarchical_sample, sample_dist, lock_view_dependence, kwargs, use_fill, third):
+                hierarchical_sample, sample_dist, lock_view_dependence, kwargs, use_fill, third, field_render=None):
         """film = (freq_geo, phase_geo, freq_app, phase_app) raw mapping outputs.
         third: None | 'weights' | 'auto' (what fancy_integration would have returned third for this fill_mode).
+        field_render: a callable with NativeModel.render's signature that stands in for it (callers.BakedField: lookups in a baked lattice
+        instead of the two SIREN passes); rays, draws, options and everything behind the call are the same.
         Returns (pixels [B,R,C'], depth [B,R], third tensor or None, pitch, yaw)."""
         B = film[0].shape[0]
         dev = self.device
@@ -120,8 +122,8 @@ class _Generator3dBase(nn.Module):
         fill_mode = kwargs.get("fill_mode", None) if use_fill else None
         want_w = third == "weights" or (third == "auto" and fill_mode not in ("weight", "eval_seg_padding_background", "eval_white_back"))
         want_ws = third == "auto" and not want_w
-        nat = self.siren.native(dev)
-        rgb, depth, weights, wsum = nat.render(
+        render = self.siren.native(dev).render if field_render is None else field_render
+        rgb, depth, weights, wsum = render(
             origins, dirs, z_vals, u, noise_c.reshape(B, R, N) if (use_noise and noise_c is not None) else None,
             noise_f.reshape(B, R, M) if use_noise else None, film[0], film[1], film[2], film[3], opts,
             hierarchical=bool(hierarchical_sample), lock_view=bool(lock_view_dependence), want_weights=want_w, want_wsum=want_ws)

@@ -1489,3 +1489,69 @@ def cluster_mesh(vertices, faces, origin, spacing, shape, factor):
         _lib.check(l.fenerf_mesh_cluster_emit(pf, V, F, o3, s3, n0, n1, n2, factor, C.c_void_p(ws.data_ptr()), nv, nf,
                                               C.c_void_p(v_out.data_ptr()) if nv else None, C.c_void_p(f_out.data_ptr()) if nf else None, _stream()))
     return v_out, f_out
+
+
+def _lattice_args(vol, C_, origin, spacing, outside_last):
+    """the lattice arguments every fenerf_volume_* entry shares, from a device lattice [n0,n1,n2,ld]"""
+    assert vol.is_cuda and vol.dim() == 4 and vol.dtype == torch.float32 and vol.is_contiguous(), "expected a contiguous fp32 device lattice [n0,n1,n2,ld]"
+    n0, n1, n2, ld = vol.shape
+    C_ = ld if C_ is None else int(C_)
+    o3, s3 = (C.c_float * 3)(*(float(x) for x in origin)), (C.c_float * 3)(*(float(x) for x in spacing))
+    return (C.c_void_p(vol.data_ptr()), n0, n1, n2, C_, ld, o3, s3, float(outside_last)), C_
+
+
+def volume_sample(vol, origin, spacing, points, outside_last=0.0, C_=None):
+    """Trilinear rows of a channels-last device lattice vol [n0,n1,n2,ld] at points [..., 3] (fenerf_volume_sample, include/fenerf.h; restated
+    in numpy by fenerf_amd/volume_emulation.py) -> rows [..., C_] on the device.  Lattice point i_k of axis k lies at origin[k] + i_k *
+    spacing[k]; a point outside the lattice gets zeros with `outside_last` in the last channel.  C_: channels per row (ld unless given)."""
+    dev = vol.device
+    args, C_ = _lattice_args(vol, C_, origin, spacing, outside_last)
+    pts = _f32(points, dev)
+    lead = pts.shape[:-1]
+    pts = pts.reshape(-1, 3)
+    P = pts.shape[0]
+    rows = torch.empty((P, C_), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_volume_sample(*args, P, C.c_void_p(pts.data_ptr()), C.c_void_p(rows.data_ptr()), _stream()))
+    return rows.reshape(*lead, C_)
+
+
+def volume_sample_rays(vol, origin, spacing, origins, dirs, z, outside_last=0.0, C_=None):
+    """volume_sample at origins + dirs * z (fenerf_volume_sample_rays): origins / dirs [B,R,3], z [B,R,N] -> rows [B,R,N,C_]"""
+    dev = vol.device
+    args, C_ = _lattice_args(vol, C_, origin, spacing, outside_last)
+    B, R, N = z.shape
+    o, d, zz = _f32(origins, dev), _f32(dirs, dev), _f32(z, dev)
+    rows = torch.empty((B, R, N, C_), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_volume_sample_rays(*args, B, R, N, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(zz.data_ptr()),
+                                                        C.c_void_p(rows.data_ptr()), _stream()))
+    return rows
+
+
+def volume_render(vol, origin, spacing, origins, dirs, z_coarse, u, noise_coarse, noise_final, opts, outside_last=0.0, C_=None, hierarchical=True,
+                  want_weights=False, want_wsum=False):
+    """NativeModel.render with the two SIREN passes replaced by lookups in a baked lattice (fenerf_volume_render): sample coarse -> weights
+    -> resample -> sample fine -> merge-composite.  Returns (rgb [B,R,C'], depth [B,R], weights [B,R,M] or None, wsum [B,R] or None)."""
+    dev = vol.device
+    args, C_ = _lattice_args(vol, C_, origin, spacing, outside_last)
+    B, R, N = z_coarse.shape
+    origins, dirs, z_coarse = _f32(origins, dev), _f32(dirs, dev), _f32(z_coarse, dev)
+    u = _f32(u, dev) if u is not None else None
+    noise_coarse = _f32(noise_coarse, dev) if noise_coarse is not None else None
+    noise_final = _f32(noise_final, dev) if noise_final is not None else None
+    M = 2 * N if hierarchical else N
+    pad = opts.fill_mode in (_lib.FILL["seg_padding_background"], _lib.FILL["eval_seg_padding_background"])
+    Cout = C_ if pad else C_ - 1
+    rgb = torch.empty((B, R, Cout), dtype=torch.float32, device=dev)
+    depth = torch.empty((B, R), dtype=torch.float32, device=dev)
+    weights = torch.empty((B, R, M), dtype=torch.float32, device=dev) if want_weights else None
+    wsum = torch.empty((B, R), dtype=torch.float32, device=dev) if want_wsum else None
+    l = _lib.lib()
+    with torch.cuda.device(dev):
+        nbytes = l.fenerf_volume_render_workspace_bytes(B, R, N, C_, int(hierarchical))
+        ws = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
+        _lib.check(l.fenerf_volume_render(*args, B, R, N, int(hierarchical), _ptr(origins), _ptr(dirs), _ptr(z_coarse), _ptr(u), _ptr(noise_coarse),
+                                          _ptr(noise_final), C.byref(opts), _ptr(rgb), _ptr(depth), _ptr(weights), _ptr(wsum),
+                                          C.c_void_p(ws.data_ptr()), C.c_size_t(int(nbytes)), _stream()))
+    return rgb, depth, weights, wsum

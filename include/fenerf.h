@@ -804,6 +804,49 @@ int fenerf_mesh_cluster_count(const float* vertices, int64_t V, const int32_t* f
 int fenerf_mesh_cluster_emit(const int32_t* faces, int64_t V, int64_t F, const float origin[3], const float spacing[3], int n0, int n1, int n2, int factor,
                              const void* workspace, int64_t n_vertices, int64_t n_faces, float* vertices_out, int32_t* faces_out, void* stream);
 
+/* ---- baked radiance lattice: many views of one identity by trilinear lookup (no model handle, like fenerf_composite) ----
+ * replaces: nothing the reference writes down.  Its inference scripts evaluate the whole FiLM-SIREN for every view of a fixed identity;
+ * with the view direction locked (--lock_view_dependence; generators.py:474-476) the field is a fixed function of position.  It is
+ * evaluated ONCE on a lattice (the sampling extract_shapes.py does for sigma alone, kept for all channels) and every view reads the
+ * lattice.  An opt-in APPROXIMATION: the error is that of trilinear interpolation at the lattice's resolution.
+ *
+ * A lattice is vol [dev] [n0][n1][n2][ld] fp32, channels last: the first C of every ld floats are a SIREN output row [labels | rgb | sigma]
+ * (or any other C channels: the sampler does not interpret them).  origin / spacing [host] [3] in the convention of fenerf_mesh_emit:
+ * coordinate column k of a point belongs to lattice axis k, lattice point i_k lies at origin[k] + i_k * spacing[k].  For a point p:
+ *   1. t_k = (p_k - origin[k]) / spacing[k]: an fp32 subtraction, then an fp32 division, each rounded on its own.
+ *   2. p is INSIDE iff t_k >= 0 && t_k <= n_k - 1 on all three axes (ordered comparisons: a NaN or infinite coordinate is outside).
+ *   3. inside: i_k = min((int)floorf(t_k), n_k - 2), f_k = t_k - (float)i_k.  A point on the last plane has f = 1 and addresses no
+ *      corner outside the lattice.
+ *   4. inside: every channel is three levels of a * (1.f - f) + b * f, axis 2 (the fastest) first, then axis 1, then axis 0: seven lerps
+ *      in fp32, every operation rounded on its own (bit for bit fenerf_amd/volume_emulation.py).
+ *   5. outside: a row of zeros with `outside_last` in channel C - 1.  Interpolation never mixes an outside row into an inside one.
+ *   6. a non-finite lattice value propagates into the rows of the cells it touches (0 * inf = NaN, as in grid_sample); nothing else changes.
+ *   7. no loaded value ever reaches an address: addresses come from the clamped integer indices alone.
+ * fenerf_volume_sample: points [dev] [P][3] -> rows [dev] [P][C].
+ * fenerf_volume_sample_rays: p = origins[b,r] + dirs[b,r] * z[b,r,n], one fp32 multiply and one fp32 add per coordinate (torch's
+ *   `origins + dirs * z`), then as above; origins / dirs [B*R][3], z [B][R][N] -> rows [B*R][N][C].
+ * 16-byte pieces of a lattice row are loaded when ld % 4 == 0 and vol is 16-byte aligned, dwords otherwise: the same bits either way.
+ * No atomics: the same bytes on every run.  Each call enqueues only.
+ * fenerf_volume_render = fenerf_render_forward with its two SIREN passes replaced by fenerf_volume_sample_rays: sample coarse ->
+ *   composite (weights only) -> resample -> sample fine -> merge-composite, through the launchers the public entries use -- bit for bit
+ *   that chain of public calls.  Arguments and outputs as fenerf_render_forward (`opts` applies to the final composite, the coarse one
+ *   uses clamp_mode and noise_std only; at most FENERF_MAX_RAY_SAMPLES samples per ray, hierarchical needs N >= 3 and u).  workspace:
+ *   fenerf_volume_render_workspace_bytes bytes [dev] (0 for invalid arguments).
+ * FENERF_E_INVALID, before anything is launched: a NULL pointer; an axis below 2 points or more than 2^31 - 1 lattice points; C < 1,
+ *   C > 64 or ld < C; spacing[k] not finite or not positive; a negative count; for the render: C < 2, N outside the limits above, a
+ *   workspace that is too small.  P = 0 or B * R = 0 launches nothing and returns FENERF_OK. */
+int fenerf_volume_sample(const float* vol, int n0, int n1, int n2, int C, int ld, const float origin[3], const float spacing[3],
+                         float outside_last, int64_t P, const float* points, float* rows, void* stream);
+int fenerf_volume_sample_rays(const float* vol, int n0, int n1, int n2, int C, int ld, const float origin[3], const float spacing[3],
+                              float outside_last, int B, int R, int N, const float* origins, const float* dirs, const float* z, float* rows,
+                              void* stream);
+size_t fenerf_volume_render_workspace_bytes(int B, int R, int N, int C, int hierarchical);
+int fenerf_volume_render(const float* vol, int n0, int n1, int n2, int C, int ld, const float origin[3], const float spacing[3],
+                         float outside_last, int B, int R, int N, int hierarchical, const float* origins, const float* dirs,
+                         const float* z_coarse, const float* u, const float* noise_coarse, const float* noise_final,
+                         const FenerfCompositeOpts* opts, float* out_rgb, float* out_depth, float* out_weights, float* out_wsum,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Bytes of [dev] scratch fenerf_render_forward needs. */
 size_t fenerf_render_workspace_bytes(const FenerfModel* m, int B, int R, int N, int hierarchical);
 

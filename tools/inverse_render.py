@@ -85,6 +85,9 @@ def build_parser():
                         help='FILE.npy: a depth map [image_size, image_size] (camera distance along the ray, the units of ray_start / ray_end) for '
                              'a depth term on the render\'s differentiable depth; non-finite or non-positive entries are masked out')
     parser.add_argument('--lambda_depth', type=float, default=0., help='weight of mean(mask * |depth - target|); needs --depth_path')
+    parser.add_argument('--baked', type=int, default=None, metavar='RES',
+                        help='--recon: bake the inverted identity once into a RES^3 lattice (view direction locked) and render the frames by '
+                             'trilinear lookup: an approximation, RES^3 x 96 bytes of device memory (default: the exact renders)')
     return parser
 
 
@@ -155,7 +158,7 @@ def run_render_recon_video(opt, generator, checkpoint_path):
     render_options = callers.inversion_render_options(opt.fov, opt.fill_color, opt.preview_size, opt.preview_steps)
     frames = callers.render_inversion_recon(generator, meta, render_options, callers.inversion_trajectory(opt.trajectory, opt.num_frames, opt.fov),
                                             opt.max_batch_size, opt.lock_view_dependence,
-                                            pose=(meta['yaw'], meta['pitch']) if 'yaw' in meta else None)
+                                            pose=(meta['yaw'], meta['pitch']) if 'yaw' in meta else None, baked=opt.baked)
     out = os.path.join(opt.save_dir, f'reconstructed_debug_{opt.trajectory}_{opt.fill_color}.avi')
     writer = imageio_lite.AviWriter(out, fps=25)
     for f in frames:

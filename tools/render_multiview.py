@@ -30,6 +30,9 @@ def build_parser():
     parser.add_argument('--ray_step_multiplier', type=int, default=2)
     parser.add_argument('--curriculum', type=str, default='CelebA')
     parser.add_argument('--no_ema', action='store_true', help='render the raw generator weights (not in the reference: it always loads <prefix>ema.pth)')
+    parser.add_argument('--baked', type=int, default=None, metavar='RES',
+                        help='bake each identity once into a RES^3 lattice (view direction locked) and render its views by trilinear lookup: an '
+                             'approximation, RES^3 x 96 bytes of device memory (not in the reference; default: the exact renders)')
     return parser
 
 
@@ -61,7 +64,7 @@ def main(argv=None):
     for seed in opt.seeds:
         images, segmaps = callers.render_multiview(generator, curriculum, int(seed), device, image_size=opt.image_size,
                                                    ray_step_multiplier=opt.ray_step_multiplier,
-                                                   lock_view_dependence=opt.lock_view_dependence)
+                                                   lock_view_dependence=opt.lock_view_dependence, baked=opt.baked)
         imageio_lite.save_image(images, os.path.join(opt.output_dir, f'grid_{seed}_RGB.png'), normalize=True, value_range=(-1, 1))
         imageio_lite.save_image(segmaps, os.path.join(opt.output_dir, f'grid_{seed}_SEG.png'))
         print(f"seed {seed}: {tuple(images.shape)} -> {opt.output_dir}/grid_{seed}_RGB.png, grid_{seed}_SEG.png")
