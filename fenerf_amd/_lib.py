@@ -187,6 +187,10 @@ _SIGS = {
     "fenerf_volume_render_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "fenerf_volume_render": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _i, _i, _i, _i] + [_vp] * 6 +
                              [C.POINTER(FenerfCompositeOpts)] + [_vp] * 4 + [_vp, _sz, _vp]),
+    # geometry views (fenerf_geometry.hip): surface points of rays, the density gradient of a lattice, normals and Lambert shading
+    "fenerf_surface_points": (_i, [_i, _i, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp]),
+    "fenerf_volume_sample_grad": (_i, [_vp, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i64, _vp, _vp, _vp]),
+    "fenerf_shade_normals": (_i, [_i, _i, _i64, _vp, _vp, _vp, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, _vp, _vp, _vp]),
     "fenerf_composite_backward": (_i, [_i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(FenerfCompositeOpts), _vp, _vp, _vp, _vp]),
     "fenerf_render_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "fenerf_render_forward": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 10 + [C.POINTER(FenerfCompositeOpts)] + [_vp] * 4 + [_vp, _sz, _vp]),

@@ -97,16 +97,19 @@ def _latent_dims(generator, default=256):
 
 
 def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.25, 0.0, 0.25, 0.5), image_size=256,
-                     ray_step_multiplier=2, lock_view_dependence=False, z_dim=None, latents=None, baked=None):
+                     ray_step_multiplier=2, lock_view_dependence=False, z_dim=None, latents=None, baked=None, geometry=False):
     """Five yaw angles of one identity (render_multiview_images_double_semantic.py:66-85).
     -> (images [V,3,S,S] in [-1,1], segmaps [V,3,S,S] in [0,1]) on the CPU.
+    geometry: True, or a dict of render_geometry's options (light, ambient, background, alpha_min, space) -- every view goes through
+    render_geometry (the same render) and the result gains (normals [V,3,S,S] in [-1,1], shaded [V,1,S,S]).
     latents: optional (z_geo, z_app) instead of the seeded draws (tests teacher-force the reference's CPU-generator values).
     baked: a lattice resolution -- the identity is baked once (bake_field, view direction locked) and every view is rendered from the
     lattice by BakedField.render with the exact route's rays and draws: an approximation.  None = the exact renders."""
     kw = multiview_kwargs(curriculum, image_size, ray_step_multiplier, lock_view_dependence)
     h_mean = kw["h_mean"]
     zg_dim, za_dim = (z_dim, z_dim) if z_dim is not None else _latent_dims(generator)
-    images, segmaps = [], []
+    images, segmaps, normals, shadeds = [], [], [], []
+    geo = dict(geometry) if isinstance(geometry, dict) else {}
     field = None
     for a in face_angles:
         kw["h_mean"] = a + h_mean
@@ -116,15 +119,26 @@ def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.
         if latents is not None:
             z_geo, z_app = (torch.as_tensor(t, dtype=torch.float32, device=device) for t in latents)
         with torch.no_grad():
-            if baked is None:
+            if baked is None and not geometry:
                 img, _ = generator.staged_forward(z_geo, z_app, **kw)
+            elif baked is None:
+                view = render_geometry(generator, z_geo, z_app, **geo, **kw)
             else:
                 avg = generator.generate_avg_frequencies()          # staged_forward's draws before its render, per view
                 if field is None:
                     field = _baked_multiview_field(generator, z_geo, z_app, avg, kw, baked)
-                img, _, _ = field.render(generator, **kw)
+                if geometry:
+                    view = field.render_geometry(generator, **geo, **kw)
+                else:
+                    img, _, _ = field.render(generator, **kw)
+        if geometry:
+            img = view["pixels"]
+            normals.append(view["normal"])
+            shadeds.append(view["shaded"])
         images.append(img[:, -3:])
         segmaps.append(mask2color(img[:, :-3], device, scale=255.0))
+    if geometry:
+        return torch.cat(images), torch.cat(segmaps), torch.cat(normals), torch.cat(shadeds)
     return torch.cat(images), torch.cat(segmaps)
 
 
@@ -213,7 +227,6 @@ def extract_mesh(generator, z_geo, z_app=None, *, film=None, voxel_resolution=25
     Like sample_generator, the z_geo route calls generate_avg_frequencies, whose 2 x 10,000 draws start from the generator state the caller
     leaves: for the surface of a volume sample_generator returned, restore that state first (tools/extract_shapes.py re-seeds)."""
     from . import imageio_lite
-    from .siren import autograd as siren_autograd
     unknown = set(attributes) - {"normal", "label", "rgb"}
     if unknown:
         raise ValueError(f"extract_mesh: unknown attributes {sorted(unknown)}")
@@ -266,23 +279,32 @@ def extract_mesh(generator, z_geo, z_app=None, *, film=None, voxel_resolution=25
         elif not V:
             mesh.update({k: np.zeros(s, d) for k, s, d in (("label", (0,), np.uint8), ("rgb", (0, 3), np.uint8)) if k in attributes})
     if "normal" in attributes:
-        normal = torch.empty((V, 3), dtype=torch.float32, device=vertices.device)
-        # only the positions take a gradient: with every weight constant the backward is the chain and the input-gradient pass alone
-        params = [p for p in siren._render_params() if p.requires_grad]
-        for p in params:
-            p.requires_grad_(False)
-        try:
-            for s0 in range(0, V, MESH_NORMAL_CHUNK):
-                with torch.enable_grad():
-                    pts = vertices[None, s0:s0 + MESH_NORMAL_CHUNK].detach().clone().requires_grad_(True)
-                    sig = siren_autograd.siren_apply(siren, pts, None, fg.detach(), pg.detach(), fa.detach(), pa.detach())[..., -1]
-                    g, = torch.autograd.grad(sig.sum(), pts)
-                normal[s0:s0 + MESH_NORMAL_CHUNK] = -g[0] / g[0].norm(dim=-1, keepdim=True).clamp_min(1e-30)
-        finally:
-            for p in params:
-                p.requires_grad_(True)
+        g = _sigma_input_grads(siren, vertices[None], fg, pg, fa, pa, MESH_NORMAL_CHUNK)[0]
+        normal = -g / g.norm(dim=-1, keepdim=True).clamp_min(1e-30)
         mesh["normal"] = native.to_host(normal).numpy()
     return mesh
+
+
+def _sigma_input_grads(siren, points, fg, pg, fa, pa, chunk):
+    """d sigma / d position at points [B,P,3] on the device -> [B,P,3], through the differentiable bare-SIREN route (forward-save, chain,
+    input-gradient pass; locked view direction) in chunks of at most `chunk` points per image"""
+    from .siren import autograd as siren_autograd
+    grads = torch.empty(tuple(points.shape), dtype=torch.float32, device=points.device)
+    # only the positions take a gradient: with every weight constant the backward is the chain and the input-gradient pass alone
+    params = [p for p in siren._render_params() if p.requires_grad]
+    for p in params:
+        p.requires_grad_(False)
+    try:
+        for s0 in range(0, points.shape[1], chunk):
+            with torch.enable_grad():
+                pts = points[:, s0:s0 + chunk].detach().clone().requires_grad_(True)
+                sig = siren_autograd.siren_apply(siren, pts, None, fg.detach(), pg.detach(), fa.detach(), pa.detach())[..., -1]
+                g, = torch.autograd.grad(sig.sum(), pts)
+            grads[:, s0:s0 + chunk] = g
+    finally:
+        for p in params:
+            p.requires_grad_(True)
+    return grads
 
 
 # ---- many views of one identity: bake the field into a lattice once, render every view by trilinear lookup (INTEGRATION.md I) -----------
@@ -347,6 +369,12 @@ class BakedField:
             third = native.to_host(third.reshape((B, img_size, img_size, -1)).permute(0, 3, 1, 2).contiguous() * 2 - 1)
             pixels = native.to_host(generator._finish_scaled(pixels, B, img_size))
         return pixels, depth_map, third
+
+    def render_geometry(self, generator, *, light=(0, 0, 1), ambient=0.25, background=1.0, alpha_min=0.5, space="camera", details=False,
+                        **render_kwargs):
+        """render() plus the geometry of the view (callers.render_geometry, baked route): normals from the central difference of the
+        lattice's density (native.volume_sample_grad on channel C - 1) at the rays' surface points.  -> the dict of render_geometry."""
+        return _render_geometry(generator, self.film, self, True, render_kwargs, light, ambient, background, alpha_min, space, details)
 
 
 def bake_field(generator, z_geo, z_app=None, *, film=None, resolution=256, center=(0, 0, 0), cube_length, psi=0.5, max_points=1 << 24):
@@ -420,6 +448,116 @@ def _baked_inversion_field(generator, film, render_options, resolution):
     meta = dict(truncated_frequencies_geo=film[0], truncated_frequencies_app=film[1], truncated_phase_shifts_geo=film[2], truncated_phase_shifts_app=film[3])
     cube = baked_cube_length(render_options["fov"], render_options["ray_start"], render_options["ray_end"], num_steps=render_options["num_steps"])
     return bake_field(generator, None, film=meta, resolution=resolution, cube_length=cube)
+
+
+# ---- geometry views: surface normals and a shaded "shape" image for the pixels of a render --------------------------
+_RENDER_POSITIONALS = ("img_size", "fov", "ray_start", "ray_end", "num_steps", "h_stddev", "v_stddev", "h_mean", "v_mean")
+
+
+def _unit_light(light):
+    """the light direction normalised on the host (float64), as the three floats the kernel uses as given"""
+    l = np.asarray(light, dtype=np.float64).reshape(3)
+    norm = float(np.linalg.norm(l))
+    if not (np.isfinite(norm) and norm > 0):
+        raise ValueError(f"render_geometry: light must be a finite non-zero direction, not {light!r}")
+    return tuple(float(x) for x in (l / norm).astype(np.float32))
+
+
+def _render_geometry(generator, film, field, lock_view, render_kwargs, light, ambient, background, alpha_min, space, details):
+    """film = (freq_geo, phase_geo, freq_app, phase_app); field = a BakedField (lattice lookups and lattice normals) or None (the SIREN)"""
+    from .generators.volumetric_rendering import create_cam2world_matrix, normalize_vecs
+    if space not in ("camera", "world"):
+        raise ValueError(f'render_geometry: space is "camera" or "world", not {space!r}')
+    light = _unit_light(light)
+    kw = dict(render_kwargs)
+    missing = [k for k in _RENDER_POSITIONALS if k not in kw]
+    if missing:
+        raise TypeError(f"render_geometry: missing render arguments {missing}")
+    img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean = (kw.pop(k) for k in _RENDER_POSITIONALS)
+    hierarchical = kw.pop("hierarchical_sample", field is not None)          # the defaults of staged_forward* / BakedField.render
+    sample_dist = kw.pop("sample_dist", None)
+    for k in ("psi", "lock_view_dependence", "max_batch_size", "depth_map", "near_clip", "far_clip"):      # staged_forward's own arguments
+        kw.pop(k, None)
+    if any(isinstance(t, torch.Tensor) and t.requires_grad for t in (*film, h_mean, v_mean)):
+        raise RuntimeError("render_geometry: a geometry view is no-grad only (a FiLM tensor or a pose requires grad)")
+    B, R = film[0].shape[0], img_size * img_size
+    rays = {}
+    with torch.no_grad():
+        pixels, depth, _, _, _ = generator._render(film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
+                                                   hierarchical, sample_dist, lock_view, kw, use_fill=True, third="wsum",
+                                                   field_render=None if field is None else field._field_render, rays_out=rays)
+        wsum = rays["wsum"]
+        alpha = None if kw.get("last_back", False) else wsum          # last_back: the weights already sum to one
+        points = native.surface_points(rays["origins"], rays["dirs"], depth, alpha, alpha_min)
+    if field is None:
+        chunk = max(32, MESH_NORMAL_CHUNK // max(B, 1) // 32 * 32)
+        try:
+            grads = _sigma_input_grads(generator.siren, points, *film, chunk)
+        except native._lib.FenerfError as e:
+            if "bf16" in str(e):
+                raise RuntimeError("render_geometry: this model's precision tier writes the bf16 gradient dump at this size (wgrad_bf16_min_points), "
+                                   "which the input-gradient pass cannot read; render the geometry view with an fp32-dump model or with baked=") from e
+            raise
+    else:
+        grads = native.volume_sample_grad(field.vol, field.origin, field.spacing, points, field.C - 1)
+    with torch.no_grad():
+        cam2world = None
+        if space == "camera":
+            cam = rays["origins"][:, 0]
+            cam2world = create_cam2world_matrix(normalize_vecs(-cam), cam)[:, :3, :3].contiguous()
+        normals, shaded = native.shade_normals(grads, R, alpha, cam2world, light, ambient, background, alpha_min)
+        S = img_size
+        out = dict(pixels=native.to_host(generator._finish_scaled(pixels, B, S)), depth=native.to_host(depth.reshape(B, S, S).contiguous()),
+                   alpha=native.to_host(wsum.reshape(B, S, S).contiguous()),
+                   normal=native.to_host(normals.reshape(B, S, S, 3).permute(0, 3, 1, 2).contiguous()),
+                   shaded=native.to_host(shaded.reshape(B, 1, S, S).contiguous()))
+        if details:
+            out.update(origins=native.to_host(rays["origins"].contiguous()), dirs=native.to_host(rays["dirs"].contiguous()), points=native.to_host(points),
+                       grad=native.to_host(grads.contiguous()), cam2world=None if cam2world is None else native.to_host(cam2world))
+    return out
+
+
+def render_geometry(generator, z_geo=None, z_app=None, *, film=None, baked=None, light=(0, 0, 1), ambient=0.25, background=1.0, alpha_min=0.5,
+                    space="camera", details=False, **render_kwargs):
+    """A render and the geometry of its pixels: a normal map and a Lambert-shaded "shape" image.
+    The render is staged_forward's (z_geo / z_app, truncated with psi -- staged_forward's default 1) or, with film= (the meta dict of
+    sample_generator_wth_frequencies_phase_shifts), staged_forward_with_frequencies': the same rays, draws and launches; render_kwargs are
+    that call's arguments.  Per ray the surface point is origin + dir * (depth / alpha) where the weight sum alpha >= alpha_min (depth
+    itself otherwise, and under last_back), the normal is -grad(sigma) / |grad(sigma)| there, and the shaded value is
+    ambient + (1 - ambient) * max(n . light, 0), alpha-blended onto `background`; rays with alpha < alpha_min get a zero normal and
+    `background` (native.surface_points / shade_normals, include/fenerf.h "geometry views").
+    baked=None: grad(sigma) is the SIREN's own input gradient at the R surface points (extract_mesh's normal route: forward-save, chain,
+    input-gradient pass).  baked= a BakedField or a lattice resolution: the render is BakedField.render's (view direction locked) and
+    grad(sigma) the central difference of the lattice (native.volume_sample_grad): an approximation, and no SIREN launch per view.
+    space="camera": normals in the view's camera frame (x right, y up, z towards the camera); "world": as the field has them.
+    `light` is normalised on the host.  No-grad only.
+    -> dict on the CPU: pixels [B,C',S,S], depth [B,S,S] (exactly the staged call's), alpha [B,S,S] (the weight sum), normal [B,3,S,S],
+    shaded [B,1,S,S]; details=True adds origins, dirs [B,R,3], points, grad [B,Pp,3] (Pp = R rounded up to 32) and cam2world [B,3,3]."""
+    kw = dict(render_kwargs)
+    siren = generator.siren
+    if isinstance(baked, BakedField):
+        return baked.render_geometry(generator, light=light, ambient=ambient, background=background, alpha_min=alpha_min, space=space, details=details, **kw)
+    with torch.no_grad():
+        if film is None:
+            if z_geo is None:
+                raise TypeError("render_geometry: give z_geo (and z_app), film= or a BakedField")
+            z_app = z_geo if z_app is None else z_app
+            psi = kw.get("psi", 1)
+            avg_fg, avg_pg, avg_fa, avg_pa = generator.generate_avg_frequencies()
+            raw_fg, raw_pg = siren.geo_mapping_network(z_geo)
+            raw_fa, raw_pa = siren.app_mapping_network(z_app)
+            fg, pg = avg_fg + psi * (raw_fg - avg_fg), avg_pg + psi * (raw_pg - avg_pg)
+            fa, pa = avg_fa + psi * (raw_fa - avg_fa), avg_pa + psi * (raw_pa - avg_pa)
+        else:
+            fg, pg = film["truncated_frequencies_geo"], film["truncated_phase_shifts_geo"]
+            fa, pa = film["truncated_frequencies_app"], film["truncated_phase_shifts_app"]
+    if baked is not None:
+        meta = dict(truncated_frequencies_geo=fg, truncated_phase_shifts_geo=pg, truncated_frequencies_app=fa, truncated_phase_shifts_app=pa)
+        cube = baked_cube_length(kw["fov"], kw["ray_start"], kw["ray_end"], num_steps=kw["num_steps"])
+        field = bake_field(generator, None, film=meta, resolution=int(baked), cube_length=cube)
+        return field.render_geometry(generator, light=light, ambient=ambient, background=background, alpha_min=alpha_min, space=space, details=details, **kw)
+    return _render_geometry(generator, (fg, pg, fa, pa), None, bool(kw.get("lock_view_dependence", False)), kw, light, ambient, background, alpha_min,
+                            space, details)
 
 
 # ---- the inversion script's host pieces (inverse_render_double_semantic.py) ------------------------------------------------------------
@@ -762,12 +900,14 @@ def camera_trajectory(name, num_frames, fov):
     raise ValueError(f"unknown trajectory {name!r} (front | orbit | rotation_horizontal | non_rotation | sphere | zoom)")
 
 
-def render_double_latent_video(generator, seed, options, trajectory, latent_type="geo", psi=0.5, device=None, latents=None):
+def render_double_latent_video(generator, seed, options, trajectory, latent_type="geo", psi=0.5, device=None, latents=None, geometry=False):
     """The frame loop of run_video_double_latent_interpolation (:381-430): two identities from seeds `seed` and `seed + 1`
     (z_geo then z_app each), FiLM parameters truncated towards the mean and interpolated on the `latent_type` side
     (DoubleFrequencyInterpolator, :130-176: 'app' sweeps t over [-1, 1]), one staged_forward_with_frequencies per trajectory
     entry with v_mean / h_mean / fov from it.  -> dict(images [F,3,S,S], labels [F,3,S,S] (0..255 colours), acc [F,3,S,S],
-    depth [F,S,S]) on the CPU.  latents: optional ((z_geo1, z_app1), (z_geo2, z_app2)) instead of the seeded draws."""
+    depth [F,S,S]) on the CPU.  latents: optional ((z_geo1, z_app1), (z_geo2, z_app2)) instead of the seeded draws.
+    geometry: True, or a dict of render_geometry's options -- every frame goes through render_geometry (the same render) and the dict
+    gains normal [F,3,S,S] and shaded [F,1,S,S]; `acc` is then the weight sum * 2 - 1 whatever the fill_mode."""
     device = torch.device(device) if device is not None else generator.device
     zg_dim, za_dim = _latent_dims(generator)
     if latents is None:
@@ -789,6 +929,9 @@ def render_double_latent_video(generator, seed, options, trajectory, latent_type
     (fg1, fa1, pg1, pa1), (fg2, fa2, pg2, pa2) = ends
     move_geo, move_app = latent_type in ("geo", "both"), latent_type in ("app", "both")
     out = dict(images=[], labels=[], acc=[], depth=[])
+    geo = dict(geometry) if isinstance(geometry, dict) else {}
+    if geometry:
+        out.update(normal=[], shaded=[])
     kw = {k: v for k, v in options.items() if k != "num_frames"}
     for t, pitch, yaw, fov in trajectory:
         t = float(t)
@@ -797,7 +940,15 @@ def render_double_latent_video(generator, seed, options, trajectory, latent_type
         film = (lerp(fg1, fg2, t) if move_geo else fg1, lerp(fa1, fa2, t) if move_app else fa1,
                 lerp(pg1, pg2, t) if move_geo else pg1, lerp(pa1, pa2, t) if move_app else pa1)
         kw.update(h_mean=float(yaw), v_mean=float(pitch), fov=float(fov), h_stddev=0, v_stddev=0)
-        frame, depth, weight_sum = generator.staged_forward_with_frequencies(*film, **kw)
+        if geometry:
+            meta = dict(truncated_frequencies_geo=film[0], truncated_frequencies_app=film[1], truncated_phase_shifts_geo=film[2], truncated_phase_shifts_app=film[3])
+            view = render_geometry(generator, film=meta, **geo, **kw)
+            frame, depth = view["pixels"], view["depth"]
+            weight_sum = (view["alpha"] * 2 - 1)[:, None].expand(-1, 3, -1, -1)
+            out["normal"].append(view["normal"])
+            out["shaded"].append(view["shaded"])
+        else:
+            frame, depth, weight_sum = generator.staged_forward_with_frequencies(*film, **kw)
         out["images"].append(frame[:, -3:])
         out["labels"].append(mask2color(frame[:, :-3], device))
         out["acc"].append(weight_sum[:, -3:])

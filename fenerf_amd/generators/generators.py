@@ -93,11 +93,13 @@ class _Generator3dBase(nn.Module):
         return super().train(mode)
 
     def _render(self, film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
-                hierarchical_sample, sample_dist, lock_view_dependence, kwargs, use_fill, third, field_render=None):
+                hierarchical_sample, sample_dist, lock_view_dependence, kwargs, use_fill, third, field_render=None, rays_out=None):
         """film = (freq_geo, phase_geo, freq_app, phase_app) raw mapping outputs.
-        third: None | 'weights' | 'auto' (what fancy_integration would have returned third for this fill_mode).
+        third: None | 'weights' | 'auto' (what fancy_integration would have returned third for this fill_mode) | 'wsum' (the weight sum
+        whatever the fill_mode).
         field_render: a callable with NativeModel.render's signature that stands in for it (callers.BakedField: lookups in a baked lattice
         instead of the two SIREN passes); rays, draws, options and everything behind the call are the same.
+        rays_out: a dict that receives the render's `origins` / `dirs` [B,R,3] and `wsum` [B,R] or None (callers.render_geometry).
         Returns (pixels [B,R,C'], depth [B,R], third tensor or None, pitch, yaw)."""
         B = film[0].shape[0]
         dev = self.device
@@ -121,7 +123,7 @@ class _Generator3dBase(nn.Module):
         use_noise = noise_std != 0
         fill_mode = kwargs.get("fill_mode", None) if use_fill else None
         want_w = third == "weights" or (third == "auto" and fill_mode not in ("weight", "eval_seg_padding_background", "eval_white_back"))
-        want_ws = third == "auto" and not want_w
+        want_ws = third == "wsum" or (third == "auto" and not want_w)
         render = self.siren.native(dev).render if field_render is None else field_render
         rgb, depth, weights, wsum = render(
             origins, dirs, z_vals, u, noise_c.reshape(B, R, N) if (use_noise and noise_c is not None) else None,
@@ -132,6 +134,8 @@ class _Generator3dBase(nn.Module):
             t = weights.unsqueeze(-1)
         elif want_ws:
             t = wsum.unsqueeze(-1).expand_as(rgb)
+        if rays_out is not None:
+            rays_out.update(origins=origins, dirs=dirs, wsum=wsum)
         return rgb, depth, t, pitch, yaw
 
     def _wants_grad(self, film, *pose):

@@ -1555,3 +1555,53 @@ def volume_render(vol, origin, spacing, origins, dirs, z_coarse, u, noise_coarse
                                           _ptr(noise_final), C.byref(opts), _ptr(rgb), _ptr(depth), _ptr(weights), _ptr(wsum),
                                           C.c_void_p(ws.data_ptr()), C.c_size_t(int(nbytes)), _stream()))
     return rgb, depth, weights, wsum
+
+
+def surface_points(origins, dirs, depth, alpha=None, alpha_min=0.5):
+    """The surface point of every ray of a render (fenerf_surface_points, include/fenerf.h "geometry views"; restated in numpy by
+    fenerf_amd/geometry_emulation.py): origins / dirs [B,R,3], depth / alpha [B,R] (the composite's depth and weight sum; alpha None: z =
+    depth) -> points [B,Pp,3] on the device, Pp = R rounded up to a multiple of 32; rows R .. Pp - 1 repeat ray R - 1."""
+    B, R = depth.shape
+    dev = depth.device
+    o, d, z = _f32(origins, dev), _f32(dirs, dev), _f32(depth, dev)
+    a = _f32(alpha, dev) if alpha is not None else None
+    points = torch.empty((B, (R + 31) // 32 * 32, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_surface_points(B, R, _ptr(o), _ptr(d), _ptr(z), _ptr(a), float(alpha_min), _ptr(points), _stream()))
+    return points
+
+
+def volume_sample_grad(vol, origin, spacing, points, channel):
+    """Gradient of one channel of a channels-last device lattice vol [n0,n1,n2,ld] at points [..., 3] (fenerf_volume_sample_grad): the
+    central difference, one cell wide, of the trilinear interpolant; zeros outside the lattice and in its outermost shell of cells
+    -> grads [..., 3] on the device."""
+    dev = vol.device
+    assert vol.is_cuda and vol.dim() == 4 and vol.dtype == torch.float32 and vol.is_contiguous(), "expected a contiguous fp32 device lattice [n0,n1,n2,ld]"
+    n0, n1, n2, ld = vol.shape
+    o3, s3 = (C.c_float * 3)(*(float(x) for x in origin)), (C.c_float * 3)(*(float(x) for x in spacing))
+    pts = _f32(points, dev)
+    lead = pts.shape[:-1]
+    pts = pts.reshape(-1, 3)
+    P = pts.shape[0]
+    grads = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_volume_sample_grad(C.c_void_p(vol.data_ptr()), n0, n1, n2, ld, int(channel), o3, s3, P, _ptr(pts), _ptr(grads), _stream()))
+    return grads.reshape(*lead, 3)
+
+
+def shade_normals(grads, R, alpha=None, cam2world=None, light=(0.0, 0.0, 1.0), ambient=0.25, background=1.0, alpha_min=0.5, want_shaded=True):
+    """Normals and Lambert shading of the rays of a render (fenerf_shade_normals): grads [B,rows,3] with rows >= R (the first R rows of an
+    image are read), alpha [B,R] or None, cam2world [B,3,3] or None (normals in camera space) -> (normals [B,R,3], shaded [B,R] or None)
+    on the device.  `light` is used as given."""
+    dev = grads.device
+    g = _f32(grads, dev)
+    B, rows = g.shape[0], g.shape[1]
+    a = _f32(alpha, dev) if alpha is not None else None
+    c2w = _f32(cam2world, dev) if cam2world is not None else None
+    normals = torch.empty((B, R, 3), dtype=torch.float32, device=dev)
+    shaded = torch.empty((B, R), dtype=torch.float32, device=dev) if want_shaded else None
+    l3 = (C.c_float * 3)(*(float(x) for x in light))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_shade_normals(B, int(R), rows, _ptr(g), _ptr(a), _ptr(c2w), l3, float(ambient), float(background), float(alpha_min),
+                                                   _ptr(normals), _ptr(shaded), _stream()))
+    return normals, shaded

@@ -25,6 +25,18 @@ def _lerp(a, b, f):
     return ((a * one_minus).astype(F) + (b * f).astype(F)).astype(F)
 
 
+def _cells(n, origin, spacing, pts):
+    """steps 1-3 for pts [P,3]: -> (inside [P] bool, clamped cell index [Q,3] int64 and fractions [Q,3] float32 of the Q inside points)"""
+    with np.errstate(all="ignore"):
+        t = ((pts - origin[None, :]).astype(F) / spacing[None, :]).astype(F)
+        hi = np.array([F(n[k] - 1) for k in range(3)], dtype=F)
+        inside = np.all((t >= F(0.0)) & (t <= hi[None, :]), axis=1)
+        ti = t[inside]
+        i = np.minimum(np.floor(ti).astype(np.int64), np.array(n, dtype=np.int64)[None, :] - 2)
+        f = (ti - i.astype(F)).astype(F)
+    return inside, i, f
+
+
 def sample(vol, origin, spacing, points, outside_last, C=None):
     """vol [n0,n1,n2,ld], origin / spacing [3], points [P,3] -> rows [P,C] float32 (C = ld unless given)"""
     vol = np.asarray(vol, dtype=F)
@@ -37,12 +49,7 @@ def sample(vol, origin, spacing, points, outside_last, C=None):
     rows = np.zeros((P, C), dtype=F)
     rows[:, C - 1] = F(outside_last)
     with np.errstate(all="ignore"):
-        t = ((pts - o[None, :]).astype(F) / s[None, :]).astype(F)
-        hi = np.array([F(n[k] - 1) for k in range(3)], dtype=F)
-        inside = np.all((t >= F(0.0)) & (t <= hi[None, :]), axis=1)
-        ti = t[inside]
-        i = np.minimum(np.floor(ti).astype(np.int64), np.array(n, dtype=np.int64)[None, :] - 2)
-        f = (ti - i.astype(F)).astype(F)
+        inside, i, f = _cells(n, o, s, pts)
         i0, i1, i2 = i[:, 0], i[:, 1], i[:, 2]
         f0, f1, f2 = (f[:, k][:, None] for k in range(3))
         v = lambda d0, d1, d2: vol[i0 + d0, i1 + d1, i2 + d2, :C]

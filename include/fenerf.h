@@ -847,6 +847,54 @@ int fenerf_volume_render(const float* vol, int n0, int n1, int n2, int C, int ld
                          const FenerfCompositeOpts* opts, float* out_rgb, float* out_depth, float* out_weights, float* out_wsum,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- geometry views: the surface point, the normal and a shaded "shape" image for the pixels of a render (fenerf_geometry.hip) ----
+ * replaces: nothing the reference writes down.  Its scripts show geometry by writing a density volume and meshing it elsewhere
+ * (extract_shapes.py); here the rays of a render get a normal map and a Lambert image from what the composite already returns.
+ * Three stand-alone kernels, no model handle.  All arithmetic is fp32, every operation rounded on its own (bit for bit
+ * fenerf_amd/geometry_emulation.py).  No atomics: the same bytes on every run.  Each call enqueues only.
+ *
+ * fenerf_surface_points: origins / dirs [dev] [B*R][3], depth / alpha [dev] [B*R] (the composite's out_depth and out_wsum; alpha may be
+ *   NULL) -> points [dev] [B][Pp][3], Pp = R rounded up to a multiple of 32 (whole tiles for the differentiable SIREN calls).  Per ray:
+ *   1. z = depth.  With alpha, where alpha >= alpha_min (ordered: false for NaN): z = depth / alpha, so a partly covered ray is not pulled
+ *      towards the camera.
+ *   2. p_k = origin_k + dir_k * z: one multiply, then one add.
+ *   3. rows R .. Pp - 1 of an image repeat the point of that image's ray R - 1.
+ *   4. a non-finite input propagates into its own row only.
+ *   FENERF_E_INVALID, before anything is launched: B or R negative; alpha given with alpha_min not finite or not > 0; origins, dirs,
+ *   depth or points NULL.  B * R = 0 launches nothing and returns FENERF_OK.
+ *
+ * fenerf_volume_sample_grad: the gradient of one channel of a baked lattice (vol / origin / spacing as for fenerf_volume_sample) as the
+ *   central difference, one lattice cell wide, of its trilinear interpolant: points [dev] [P][3] -> grads [dev] [P][3].
+ *   1. steps 1-3 of the sampler above: the inside test, the clamped cell i_k, the fractions f_k.
+ *   2. a point is INTERIOR iff it is inside and 1 <= i_k <= n_k - 3 on all three axes.
+ *   3. V(j) = the sampler's step-4 value of `channel` at cell j with the point's fractions f (seven lerps: axis 2, axis 1, axis 0).
+ *   4. interior: g_k = (V(i + e_k) - V(i - e_k)) / (spacing[k] + spacing[k]); continuous across cells.
+ *   5. otherwise the row is (0, 0, 0).  An axis with fewer than 4 lattice points has no interior cell: every row is zero.
+ *   6. a non-finite lattice value propagates into the rows that read it; addresses come from the integer indices alone.
+ *   FENERF_E_INVALID: a NULL pointer; an axis below 2 points or more than 2^31 - 1 lattice points; channel < 0 or channel >= ld;
+ *   spacing[k] not finite or not positive; P < 0.  P = 0 launches nothing and returns FENERF_OK.
+ *
+ * fenerf_shade_normals: grads [dev] [B][rows_per_image][3] (the first R rows of an image are read: the padded layout of
+ *   fenerf_surface_points, or rows_per_image = R), alpha [dev] [B*R] or NULL, cam2world [dev] [B][3][3] row-major or NULL, light [host] [3]
+ *   (used as given) -> normals [dev] [B*R][3], shaded [dev] [B*R] or NULL.  Per ray, in this order:
+ *   1. s = (gx gx + gy gy) + gz gz.
+ *   2. len = sqrt(s).
+ *   3. n = (+0, +0, +0) if len == 0, else n_k = (-g_k) / len.
+ *   4. with cam2world (rotation R of the image): m_j = (R[0][j] n_0 + R[1][j] n_1) + R[2][j] n_2 -- the normal in camera space; else m = n.
+ *   5. a = 1 without alpha, else alpha clamped to [0, 1] by ordered compares (NaN stays NaN).
+ *   6. visible = no alpha, or alpha >= alpha_min.
+ *   7. d = (m_0 l_0 + m_1 l_1) + m_2 l_2.
+ *   8. lam = d < 0 ? 0 : d (NaN stays NaN).
+ *   9. shade = ambient + (1 - ambient) * lam.
+ *   visible: normals = m, shaded = a * shade + (1 - a) * background.  invisible: normals = 0, shaded = background.
+ *   FENERF_E_INVALID: grads, normals or light NULL; rows_per_image < R; a negative count; ambient, background or alpha_min not finite. */
+int fenerf_surface_points(int B, int R, const float* origins, const float* dirs, const float* depth, const float* alpha, float alpha_min,
+                          float* points, void* stream);
+int fenerf_volume_sample_grad(const float* vol, int n0, int n1, int n2, int ld, int channel, const float origin[3], const float spacing[3],
+                              int64_t P, const float* points, float* grads, void* stream);
+int fenerf_shade_normals(int B, int R, int64_t rows_per_image, const float* grads, const float* alpha, const float* cam2world,
+                         const float light[3], float ambient, float background, float alpha_min, float* normals, float* shaded, void* stream);
+
 /* Bytes of [dev] scratch fenerf_render_forward needs. */
 size_t fenerf_render_workspace_bytes(const FenerfModel* m, int B, int R, int N, int hierarchical);
 

@@ -33,7 +33,21 @@ def build_parser():
     parser.add_argument('--baked', type=int, default=None, metavar='RES',
                         help='bake each identity once into a RES^3 lattice (view direction locked) and render its views by trilinear lookup: an '
                              'approximation, RES^3 x 96 bytes of device memory (not in the reference; default: the exact renders)')
+    add_geometry_arguments(parser)
     return parser
+
+
+def add_geometry_arguments(parser):
+    parser.add_argument('--geometry', action='store_true',
+                        help='also write the normal map (n * 0.5 + 0.5) and the Lambert-shaded shape image of every view, as <name>_normal / '
+                             '<name>_shaded (callers.render_geometry; not in the reference).  Combines with --baked: lattice normals')
+    parser.add_argument('--light', type=float, nargs=3, default=(0.0, 0.0, 1.0), metavar=('X', 'Y', 'Z'), help='light direction in camera space (--geometry)')
+    parser.add_argument('--ambient', type=float, default=0.25, help='ambient term of the shaded image (--geometry)')
+
+
+def geometry_options(opt):
+    """render_multiview's / render_double_latent_video's `geometry` argument from the flags above"""
+    return dict(light=tuple(opt.light), ambient=opt.ambient) if opt.geometry else False
 
 
 def resolve_curriculum(name):
@@ -62,11 +76,16 @@ def main(argv=None):
     os.makedirs(opt.output_dir, exist_ok=True)
     generator = callers.load_generator(opt.path, device, use_ema=not opt.no_ema)
     for seed in opt.seeds:
-        images, segmaps = callers.render_multiview(generator, curriculum, int(seed), device, image_size=opt.image_size,
-                                                   ray_step_multiplier=opt.ray_step_multiplier,
-                                                   lock_view_dependence=opt.lock_view_dependence, baked=opt.baked)
+        images, segmaps, *views = callers.render_multiview(generator, curriculum, int(seed), device, image_size=opt.image_size,
+                                                           ray_step_multiplier=opt.ray_step_multiplier,
+                                                           lock_view_dependence=opt.lock_view_dependence, baked=opt.baked,
+                                                           geometry=geometry_options(opt))
         imageio_lite.save_image(images, os.path.join(opt.output_dir, f'grid_{seed}_RGB.png'), normalize=True, value_range=(-1, 1))
         imageio_lite.save_image(segmaps, os.path.join(opt.output_dir, f'grid_{seed}_SEG.png'))
+        if views:
+            normals, shaded = views
+            imageio_lite.save_image(normals * 0.5 + 0.5, os.path.join(opt.output_dir, f'grid_{seed}_normal.png'))
+            imageio_lite.save_image(shaded, os.path.join(opt.output_dir, f'grid_{seed}_shaded.png'))
         print(f"seed {seed}: {tuple(images.shape)} -> {opt.output_dir}/grid_{seed}_RGB.png, grid_{seed}_SEG.png")
 
 

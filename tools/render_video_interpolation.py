@@ -43,6 +43,8 @@ def build_parser():
     parser.add_argument("--save_with_video", action='store_true')
     parser.add_argument("--save_with_latent", action='store_true')
     parser.add_argument("--seed_mode", default='single', type=str, help='if the seeds are speficifed a range or a number')
+    from render_multiview import add_geometry_arguments
+    add_geometry_arguments(parser)          # --geometry [--light X Y Z] [--ambient A]: img_<j>_normal.png / img_<j>_shaded.png per frame, two strips
     return parser
 
 
@@ -78,7 +80,7 @@ def main(argv=None):
     import numpy as np
     import torch
     from fenerf_amd import callers, imageio_lite
-    from render_multiview import resolve_curriculum
+    from render_multiview import geometry_options, resolve_curriculum
     if opt.interpolation_type not in ('video_double_latent_interpolation', 'video_latent_interpolation'):
         raise SystemExit(f"--interpolation_type {opt.interpolation_type}: video_double_latent_interpolation | video_latent_interpolation")
     if not torch.cuda.is_available():
@@ -99,9 +101,15 @@ def main(argv=None):
         frame_dir = os.path.join(output_dir, "images", f"{opt.latent_type}_{opt.trajectory}")
         os.makedirs(frame_dir, exist_ok=True)
         out = callers.render_double_latent_video(generator, int(seed), dict(options, max_batch_size=opt.max_batch_size, depth_map=opt.depth_map),
-                                                 trajectory, latent_type=opt.latent_type, psi=opt.psi, device=device)
+                                                 trajectory, latent_type=opt.latent_type, psi=opt.psi, device=device, geometry=geometry_options(opt))
         F = out["images"].shape[0]
         depth_colors = []
+        if opt.geometry:
+            for j in range(F):
+                imageio_lite.save_image(out["normal"][j:j + 1] * 0.5 + 0.5, os.path.join(frame_dir, f"img_{j}_normal.png"), nrow=1)
+                imageio_lite.save_image(out["shaded"][j:j + 1], os.path.join(frame_dir, f"img_{j}_shaded.png"), nrow=1)
+            imageio_lite.save_image(out["normal"] * 0.5 + 0.5, os.path.join(output_dir, "interp_normal.png"), nrow=opt.num_frames)
+            imageio_lite.save_image(out["shaded"], os.path.join(output_dir, "interp_shaded.png"), nrow=opt.num_frames)
         for j in range(F):
             imageio_lite.save_image(out["labels"][j:j + 1], os.path.join(frame_dir, f"label_{j}.png"), nrow=1, normalize=True)
             imageio_lite.save_image(out["images"][j:j + 1], os.path.join(frame_dir, f"img_{j}.png"), nrow=1, normalize=True)
