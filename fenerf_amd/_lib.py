@@ -81,6 +81,7 @@ _SIGS = {
     "fenerf_abi_version": (_i, []),
     "fenerf_set_cu_budget": (_i, [_i]),
     "fenerf_set_render_fusion": (_i, [_i]),
+    "fenerf_set_render_split": (_i, [_i]),
     "fenerf_mapping_forward": (_i, [C.POINTER(FenerfMappingNet), _i, _vp, _vp, _vp, _vp]),
     "fenerf_mapping_workspace_floats": (_sz, [C.POINTER(FenerfMappingNet), _i]),
     "fenerf_mapping_backward": (_i, [C.POINTER(FenerfMappingNet), _i, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp]),
@@ -196,8 +197,9 @@ _SIGS = {
     "fenerf_render_forward": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 10 + [C.POINTER(FenerfCompositeOpts)] + [_vp] * 4 + [_vp, _sz, _vp]),
 }
 EXPORTS = tuple(_SIGS)
-N_PHASES = 17        # include/fenerf.h FENERF_N_PHASES
+N_PHASES = 19        # include/fenerf.h FENERF_N_PHASES_ALL
 FUSION_AUTO, FUSION_OFF, FUSION_FORCE = 0, 1, 2      # include/fenerf.h fenerf_set_render_fusion
+SPLIT_AUTO, SPLIT_OFF, SPLIT_FORCE = 0, 1, 2         # include/fenerf.h fenerf_set_render_split
 TAPE_F32, TAPE_U16, TAPE_F32_W = 0, 1, 2             # include/fenerf.h FENERF_TAPE_*
 GRID_GRAD_ATOMIC, GRID_GRAD_DETERMINISTIC = 0, 1     # include/fenerf.h FENERF_GRID_GRAD_*
 KEEP_LARGEST, KEEP_MIN_POINTS = 0, 1                 # include/fenerf.h FENERF_KEEP_*

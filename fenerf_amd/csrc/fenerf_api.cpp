@@ -62,7 +62,8 @@ std::mutex g_phase_mu;
 std::vector<PhaseRec*> g_phase_recs;
 const char* const kPhaseNames[PH_COUNT] = {"film_prep", "siren_forward", "forward_save", "chain", "wgrad_film_sums", "wgrad_square",
                                            "wgrad_square_reduce", "wgrad_thin", "wgrad_thin_reduce", "composite", "resample",
-                                           "composite_backward", "repack", "grid", "ray_setup", "other", "render_fused"};
+                                           "composite_backward", "repack", "grid", "ray_setup", "other", "render_fused", "siren_density",
+                                           "siren_colour"};
 }  // namespace
 PhaseScope::PhaseScope(int phase, void* stream) : rec(nullptr) {
   if (!g_phase_on.load(std::memory_order_relaxed)) return;
@@ -178,6 +179,7 @@ static int upload_model(FenerfModel* m, const FenerfModelDesc* d, hipStream_t st
   } else if (d->grid_ch && allocate) {
     return fail(FENERF_E_INVALID, "grid_ch > 0 but grid pointer is NULL");
   }
+  if ((rc = launch_nonfinite_scan(m, d->grid_ch && d->grid, stream))) return rc;   // what the split render must know about the colour parameters
   HIP_TRY(hipStreamSynchronize(stream));  // blob/consts are stack-owned host vectors
   return FENERF_OK;
 }
@@ -190,7 +192,7 @@ extern "C" const char* fenerf_last_error(void) { return g_err.c_str(); }
 extern "C" int fenerf_phase_timing(int enable) { return g_phase_on.exchange(enable ? 1 : 0); }
 extern "C" const char* fenerf_phase_name(int phase) { return phase >= 0 && phase < PH_COUNT ? kPhaseNames[phase] : ""; }
 extern "C" int fenerf_phase_times(double* ms, int* calls, int n) {
-  if (!ms || !calls || n < PH_COUNT) return fail(FENERF_E_INVALID, "fenerf_phase_times: need ms / calls arrays of FENERF_N_PHASES entries");
+  if (!ms || !calls || n < FENERF_N_PHASES) return fail(FENERF_E_INVALID, "fenerf_phase_times: need ms / calls arrays of FENERF_N_PHASES entries");
   std::vector<PhaseRec*> recs;
   {
     std::lock_guard<std::mutex> lock(g_phase_mu);
@@ -201,7 +203,7 @@ extern "C" int fenerf_phase_times(double* ms, int* calls, int n) {
     float t = 0.f;
     hipError_t e = hipEventSynchronize(r->e1);
     if (e == hipSuccess) e = hipEventElapsedTime(&t, r->e0, r->e1);
-    if (e == hipSuccess) { ms[r->phase] += (double)t; calls[r->phase] += 1; }
+    if (e == hipSuccess) { if (r->phase < n) { ms[r->phase] += (double)t; calls[r->phase] += 1; } }      // a caller with FENERF_N_PHASES entries: no later phase
     else rc = hip_fail(e, "fenerf_phase_times");
     (void)hipEventDestroy(r->e0);
     (void)hipEventDestroy(r->e1);
@@ -216,6 +218,14 @@ static constexpr bool kFusionAutoEnabled = false;
 extern "C" int fenerf_set_render_fusion(int mode) {
   const int prev = g_render_fusion;
   g_render_fusion = (mode == FENERF_FUSION_OFF || mode == FENERF_FUSION_FORCE) ? mode : FENERF_FUSION_AUTO;
+  return prev;
+}
+static thread_local int g_render_split = FENERF_SPLIT_AUTO;
+// AUTO takes the density + colour route only if it has been measured to be faster than the dense coarse launch (profiles/r16_split_forward.md)
+static constexpr bool kSplitAutoEnabled = true;
+extern "C" int fenerf_set_render_split(int mode) {
+  const int prev = g_render_split;
+  g_render_split = (mode == FENERF_SPLIT_OFF || mode == FENERF_SPLIT_FORCE) ? mode : FENERF_SPLIT_AUTO;
   return prev;
 }
 extern "C" int fenerf_set_cu_budget(int cus) {
@@ -320,6 +330,11 @@ extern "C" int fenerf_model_create(const FenerfModelDesc* d, FenerfModel** out) 
     }
   }
 #endif
+  if (m->precision == FENERF_PREC_F16X3) {
+    e = hipMalloc((void**)&m->d_colour_nonfinite, 2 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(m->d_colour_nonfinite, 0, 2 * sizeof(unsigned));
+    if (e != hipSuccess) { fenerf_model_destroy(m); return hip_fail(e, "fenerf_model_create"); }
+  }
   rc = upload_model(m, d, nullptr, true);
   if (rc) { fenerf_model_destroy(m); return rc; }
   *out = m;
@@ -387,9 +402,10 @@ extern "C" int fenerf_model_load_packed(FenerfModel* m, const float* stream_dev,
   if (m->differentiable) HIP_TRY(hipMemcpyAsync(m->d_bwd_stream, bwd_dev, n_bwd * sizeof(float), hipMemcpyDeviceToDevice, st));
   if (grid_dev) {
     if (!m->grid_ch) return fail(FENERF_E_INVALID, "model has no feature grid");
-    { PhaseScope ph(PH_GRID, stream); return launch_grid_relayout(grid_dev, m->d_grid, m->grid_ch, m->gd, m->gh, m->gw, stream); }
+    int rc = [&] { PhaseScope ph(PH_GRID, stream); return launch_grid_relayout(grid_dev, m->d_grid, m->grid_ch, m->gd, m->gh, m->gw, stream); }();
+    if (rc) return rc;
   }
-  return FENERF_OK;
+  return launch_nonfinite_scan(m, grid_dev != nullptr, stream);
 }
 
 extern "C" int fenerf_model_repack(FenerfModel* m, const float* flat_dev, size_t n_flat, const FenerfRepackMaps* r, const float* grid_dev,
@@ -415,9 +431,10 @@ extern "C" int fenerf_model_repack(FenerfModel* m, const float* flat_dev, size_t
   if (rc) return rc;
   if (grid_dev) {
     if (!m->grid_ch) return fail(FENERF_E_INVALID, "model has no feature grid");
-    { PhaseScope ph(PH_GRID, stream); return launch_grid_relayout(grid_dev, m->d_grid, m->grid_ch, m->gd, m->gh, m->gw, stream); }
+    rc = [&] { PhaseScope ph(PH_GRID, stream); return launch_grid_relayout(grid_dev, m->d_grid, m->grid_ch, m->gd, m->gh, m->gw, stream); }();
+    if (rc) return rc;
   }
-  return FENERF_OK;
+  return launch_nonfinite_scan(m, grid_dev != nullptr, stream);
 }
 
 extern "C" int fenerf_model_export_packed(const FenerfModel* m, float* stream_dev, size_t n_stream, float* consts_dev, size_t n_consts,
@@ -435,6 +452,7 @@ extern "C" int fenerf_model_export_packed(const FenerfModel* m, float* stream_de
 extern "C" void fenerf_model_destroy(FenerfModel* m) {
   if (!m) return;
   if (m->d_row_scale) (void)hipFree(m->d_row_scale);
+  if (m->d_colour_nonfinite) (void)hipFree(m->d_colour_nonfinite);
   if (m->d_stream32) (void)hipFree(m->d_stream32);
   if (m->d_consts32) (void)hipFree(m->d_consts32);
   if (m->d_stream) (void)hipFree(m->d_stream);
@@ -1401,7 +1419,7 @@ extern "C" int fenerf_volume_render(const float* vol, int n0, int n1, int n2, in
 // workspace layout of fenerf_render_forward
 namespace {
 struct RenderWs {
-  size_t film, coarse, fine, wts, zf, total;
+  size_t film, coarse, fine, wts, zf, counts, idx, xbuf, total;
 };
 RenderWs render_ws(const FenerfModel* m, int B, int R, int N, int hier) {
   RenderWs w;
@@ -1412,6 +1430,12 @@ RenderWs render_ws(const FenerfModel* m, int B, int R, int N, int hier) {
   w.fine = off; off += hier ? align_up(pts * m->C * sizeof(float), 256) : 0;
   w.wts = off; off += hier ? align_up(pts * sizeof(float), 256) : 0;
   w.zf = off; off += hier ? align_up(pts * sizeof(float), 256) : 0;
+  // the split coarse pass (fenerf_set_render_split): per image a counter, a list of R N sample indices and R N slots of H * 4 bytes for the
+  // trunk outputs of the kept samples -- capacity for every sample, touched only as far as the lists grow
+  const bool split = hier && m->precision == FENERF_PREC_F16X3;
+  w.counts = off; off += split ? align_up((size_t)B * sizeof(unsigned), 256) : 0;
+  w.idx = off; off += split ? align_up(pts * sizeof(unsigned), 256) : 0;
+  w.xbuf = off; off += split ? align_up(pts * (size_t)m->H * sizeof(float), 256) : 0;
   w.total = off;
   return w;
 }
@@ -1488,7 +1512,27 @@ extern "C" int fenerf_render_forward(const FenerfModel* m, int B, int R, int N, 
     PhaseScope ph(PH_RENDER_FUSED, stream);
     return launch_render16w_fused(m, sp, plan, zf, fine, c1, c2, stream);
   }
-  rc = run_siren(m, sp, stream);                       // coarse pass   (generators.py:479)
+  // Density + colour route (fenerf_set_render_split): under the relu clamp a coarse sample with sigma <= 0 has alpha = 0 exactly whatever
+  // its neighbours are, and without last_back and without noise on sigma its row meets an exact zero in the final composite -- its colour
+  // branch is skipped.  The sigma-only composite between the two launches reads nothing the colour pass writes.
+  const bool split_ok = m->precision == FENERF_PREC_F16X3 && m->forward_mode == FENERF_FORWARD_F16X3 && opts->clamp_mode == FENERF_CLAMP_RELU &&
+                        !opts->last_back && (opts->noise_std == 0.f || !noise_final) && m->d_colour_nonfinite;
+  if (g_render_split == FENERF_SPLIT_FORCE && !split_ok)
+    return fail(FENERF_E_UNSUPPORTED, "fenerf_set_render_split(FORCE): the density + colour route needs an f16x3 model at its default forward mode, "
+                                      "the relu clamp, last_back off and no noise on the final composite");
+  const bool split = split_ok && (g_render_split == FENERF_SPLIT_FORCE || (g_render_split == FENERF_SPLIT_AUTO && kSplitAutoEnabled));
+  SplitArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  if (split) {
+    sa.counts = (unsigned*)(base + ws.counts); sa.idx = (unsigned*)(base + ws.idx); sa.xbuf = (float*)(base + ws.xbuf);
+    sa.cap = (long long)R * N; sa.keep_all = m->d_colour_nonfinite;
+    HIP_TRY(hipMemsetAsync(sa.counts, 0, (size_t)B * sizeof(unsigned), (hipStream_t)stream));
+    // timed as a SIREN forward launch (it is the route's coarse launch: "siren_forward" keeps counting two per hierarchical render) and,
+    // inside that, under its own name
+    rc = [&] { PhaseScope ph(PH_SIREN, stream); PhaseScope pd(PH_SIREN_DENSITY, stream); return launch_siren16w_density(m, sp, sa, stream); }();
+  } else {
+    rc = run_siren(m, sp, stream);                     // coarse pass   (generators.py:479)
+  }
   if (rc) return rc;
   sp.raw_fg = nullptr;                                    // the fine pass finds f' / p' in the workspace
   memset(&cp, 0, sizeof(cp));                             // coarse weights (generators.py:487) and, in the same wave per ray, the
@@ -1499,6 +1543,10 @@ extern "C" int fenerf_render_forward(const FenerfModel* m, int B, int R, int N, 
   cp.u = u; cp.z_fine = zf;
   rc = run_composite(cp, false, stream);
   if (rc) return rc;
+  if (split) {                                            // colour of the kept coarse samples, into their rows
+    rc = [&] { PhaseScope ph(PH_SIREN_COLOUR, stream); return launch_siren16w_colour(m, sp, sa, stream); }();
+    if (rc) return rc;
+  }
   sp.z = zf; sp.out = fine;
   rc = run_siren(m, sp, stream);                       // fine pass     (generators.py:505)
   if (rc) return rc;

@@ -26,8 +26,9 @@ int ensure_dynamic_lds(const void* kfn, size_t bytes);
 // Per-phase device timing (fenerf_phase_timing / fenerf_phase_times): a PhaseScope around a launch group records a hipEvent pair on
 // the stream when timing is on, and is two loads of a flag when it is off.
 enum Phase { PH_FILM_PREP = 0, PH_SIREN, PH_SIREN_SAVE, PH_CHAIN, PH_WGRAD_FILM, PH_WGRAD_SQ, PH_WGRAD_SQ_REDUCE, PH_WGRAD_THIN,
-             PH_WGRAD_THIN_REDUCE, PH_COMPOSITE, PH_RESAMPLE, PH_COMPOSITE_BWD, PH_REPACK, PH_GRID, PH_RAY_SETUP, PH_OTHER, PH_RENDER_FUSED, PH_COUNT };
-static_assert(PH_COUNT == FENERF_N_PHASES, "include/fenerf.h FENERF_N_PHASES");
+             PH_WGRAD_THIN_REDUCE, PH_COMPOSITE, PH_RESAMPLE, PH_COMPOSITE_BWD, PH_REPACK, PH_GRID, PH_RAY_SETUP, PH_OTHER, PH_RENDER_FUSED,
+             PH_SIREN_DENSITY, PH_SIREN_COLOUR, PH_COUNT };
+static_assert(PH_COUNT == FENERF_N_PHASES_ALL && PH_RENDER_FUSED + 1 == FENERF_N_PHASES, "include/fenerf.h FENERF_N_PHASES / FENERF_N_PHASES_ALL");
 struct PhaseScope {
   PhaseScope(int phase, void* stream);
   ~PhaseScope();
@@ -65,6 +66,7 @@ struct FenerfModel {
   int wgrad_bf16_min_points; // desc->wgrad_bf16_min_points: 0 = fp32-class weight gradients; > 0 = bf16 dump for chunks of at least that many points
   fenerf::BwdShape bsh;
   float* d_bwd_stream;      // [rgb-head^T entries | backward ring] * 256 floats, or nullptr
+  unsigned* d_colour_nonfinite;   // two flag words (stream + consts | grid), rewritten whenever the stream / consts / grid are (launch_nonfinite_scan): the split render keeps every sample when set
   float* d_row_scale;       // fenerf_model_repack scratch: [2][L*H + 64] row scales (forward | backward), lazily allocated
   size_t n_stream, n_consts, n_bwd;   // floats resident in d_stream / d_consts / d_bwd_stream
   // FENERF_PREC_F16X3 models: the exact-fp32 stream / consts too (host-packed at create / update), for fenerf_siren_forward_pointwise --
@@ -205,6 +207,19 @@ int launch_siren_input_grads(const FenerfModel* m, int B, long long P, const flo
 int launch_ray_grads(int B, int R, int N, long long Pp, int passes, const float* d_pts2, const float* d_rd2, const float* z_coarse,
                      const float* z_fine, float* d_origins, float* d_dirs, void* stream);
 int launch_siren16w(const FenerfModel* m, const SirenParams& p, void* stream);   // f16x3 forward / forward-save, 16-point waves (fenerf_siren_f16w.hip)
+// The coarse launch of a hierarchical render as a density pass and a compacted colour pass (fenerf_siren_f16w.hip, PASS): per image a
+// list of the samples whose colour can reach a pixel.  `cap` = slots per image (the image's sample count: a list cannot overflow).
+struct SplitArgs {
+  unsigned* counts;          // [B]        kept samples per image (zeroed before the density pass)
+  unsigned* idx;             // [B][cap]   sample index within the image
+  float* xbuf;               // [B][cap][H/32][hi | lo][4 lane groups]  the trunk output as colour layer 0's B operands (H * 4 bytes per slot)
+  long long cap;
+  const unsigned* keep_all;  // the model's two flag words: either non-zero = a non-finite colour weight or grid voxel, every sample is kept
+};
+int launch_siren16w_density(const FenerfModel* m, const SirenParams& p, const SplitArgs& s, void* stream);
+int launch_siren16w_colour(const FenerfModel* m, const SirenParams& p, const SplitArgs& s, void* stream);    // p.out: the density pass's rows
+// fenerf_repack.hip: m->d_colour_nonfinite[0] <- "the packed stream or the consts hold a non-finite value", [1] <- "the relaid grid does" (grid_too)
+int launch_nonfinite_scan(FenerfModel* m, bool grid_too, void* stream);
 // fenerf_render_forward as ONE launch (fenerf_siren_f16w.hip, FUSED): ray groups of whole octs, see there
 struct FusedRenderPlan { int rays_per_group, octs_per_group, blocks; long long groups; };
 bool fused_render_plan(const FenerfModel* m, long long B, long long R, int N, bool balanced_only, FusedRenderPlan* plan);

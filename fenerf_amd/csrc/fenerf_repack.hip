@@ -149,4 +149,37 @@ int launch_repack(FenerfModel* m, const float* flat, const FenerfRepackMaps* r, 
   return check_launch("repack launch");
 }
 
+// The split render (fenerf_set_render_split) skips the colour branch of samples with sigma <= 0, which is only the reference's result while
+// every colour evaluation is finite (0 * NaN is a NaN pixel).  Whatever rewrites the packed stream, the consts or the relaid grid is
+// followed by this scan of what was written; the density pass keeps every sample while the word is set.  The stream's ring part is read as
+// fp16 halves (all-ones exponent = Inf / NaN; a NaN or Inf weight has one in its hi half), layer 0's fp32 block, the consts and the grid as
+// floats.  Over-approximates on purpose: a non-finite trunk weight sets the word too (its sigma is NaN and kept anyway).  Two words:
+// [0] stream + consts, [1] the grid, rescanned only when the grid was rewritten (113 MB at 32 x 96^3).
+__global__ void nonfinite_scan_kernel(const float* f32_a, long long n_a, const float* f32_b, long long n_b, const float* f32_c, long long n_c,
+                                      const uint16_t* h16, long long n_h, unsigned* flag) {
+  bool bad = false;
+  const long long stride = (long long)gridDim.x * blockDim.x, i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  auto scan = [&](const float* p, long long n) {
+    for (long long i = i0; i < n; i += stride) bad |= !(__builtin_fabsf(p[i]) < __builtin_inff());
+  };
+  scan(f32_a, n_a); scan(f32_b, n_b); scan(f32_c, n_c);
+  for (long long i = i0; i < n_h; i += stride) bad |= (h16[i] & 0x7c00u) == 0x7c00u;
+  if (bad) atomicOr(flag, 1u);
+}
+
+int launch_nonfinite_scan(FenerfModel* m, bool grid_too, void* stream) {
+  if (m->precision != FENERF_PREC_F16X3 || !m->d_colour_nonfinite) return FENERF_OK;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(m->d_colour_nonfinite, 0, (grid_too ? 2 : 1) * sizeof(unsigned), st);
+  if (e != hipSuccess) return hip_fail(e, "non-finite scan");
+  const long long n_l0 = (long long)m->sh.l0_entries * 256;
+  const long long n_grid = m->d_grid ? (long long)m->grid_ch * m->gd * m->gh * m->gw : 0;
+  hipLaunchKernelGGL(nonfinite_scan_kernel, dim3(64), dim3(256), 0, st, m->d_stream, n_l0, m->d_consts, (long long)m->n_consts, (const float*)nullptr, 0LL,
+                     reinterpret_cast<const uint16_t*>(m->d_stream + n_l0), ((long long)m->n_stream - n_l0) * 2, m->d_colour_nonfinite);
+  if (grid_too && n_grid)
+    hipLaunchKernelGGL(nonfinite_scan_kernel, dim3(1024), dim3(256), 0, st, m->d_grid, n_grid, (const float*)nullptr, 0LL, (const float*)nullptr, 0LL,
+                       (const uint16_t*)nullptr, 0LL, m->d_colour_nonfinite + 1);
+  return check_launch("non-finite scan launch");
+}
+
 }  // namespace fenerf

@@ -274,8 +274,8 @@ __device__ __forceinline__ void piece_range(int qc, int& p0, int& p1) {
 // coarse / fine rows and the fine depths are written and read back by the SAME workgroup a few microseconds apart (L2), ordered by
 // workgroup-scope fences + barriers; the weight ring is untouched by the ray phases (chunks 0 .. D-1 of the next tile land and wait), which
 // use the per-wave LDS block that parks colour layer 0's extra operands during a tile.
-template <bool FUSED> struct FuseArgs {};
-template <> struct FuseArgs<true> {
+template <bool FUSED, int PASS = 0> struct FuseArgs {};
+template <> struct FuseArgs<true, 0> {
   int rays_per_group, octs_per_group;
   long long groups, total_rays;
   float* z_fine;            // [B*R][N]  written by the coarse ray phase, read by the fine tiles and the final ray phase
@@ -291,11 +291,23 @@ template <> struct FuseArgs<true> {
 #ifndef FENERF_EXP_FUSED_MAXM
 #define FENERF_EXP_FUSED_MAXM 128
 #endif
+// PASS (round 16, fenerf_set_render_split): the coarse launch of a hierarchical render as two launches on the one packed stream.
+//   PASS = 1, density pass: layer 0, the geometry trunk and the label / sigma head of every sample; rgb is written as 0.  A sample whose
+//             colour can reach a pixel -- !(sigma <= 0), or a non-finite view direction, or non-finite colour parameters (S.keep_all / the
+//             image's appearance FiLM block) -- takes a slot of its image's list: its index and its trunk output, the xh / xl registers as
+//             colour layer 0 consumes them ([slot][k32-step][hi | lo][lane group] x 16 bytes = 1 KiB at H = 256).
+//   PASS = 2, colour pass: a persistent launch over octs of 8 x 16 slots of one image, sized on the device from counts[]: reloads xh / xl,
+//             recomputes the point, gathers the grid, runs colour layer 0, the colour layers and the rgb head and scatters three floats.
+// Both walk the stream with jumps of g_next over the stages they do not run (every stage is whole ring revolutions: the slot indices stay);
+// a kept sample's column sees the dense kernel's MFMA sequence on the dense kernel's operands, so its outputs are the dense kernel's bits.
+template <> struct FuseArgs<false, 1> : SplitArgs {};
+template <> struct FuseArgs<false, 2> : SplitArgs {};
 constexpr int FUSED_MAXM = FENERF_EXP_FUSED_MAXM;   // samples per ray (2 N) the ray phases handle: their LDS scratch is the 4-KiB colour-layer-0 block
 
-template <int H, bool GRID, int SAVE, bool FUSED = false, int TERMS2 = 0>
-__global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_geo, int n_color, int n_lab, int C, FuseArgs<FUSED> F) {
+template <int H, bool GRID, int SAVE, bool FUSED = false, int TERMS2 = 0, int PASS = 0>
+__global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_geo, int n_color, int n_lab, int C, FuseArgs<FUSED, PASS> F) {
   static_assert(!(FUSED && SAVE != 0), "the fused render is the no-grad path");
+  static_assert(PASS == 0 || (SAVE == 0 && !FUSED && TERMS2 == 0), "the split passes are plain no-grad evaluations at full f16x3");
   static_assert(TERMS2 == 0 || (SAVE == 0 && !FUSED), "the reduced-precision forwards are plain no-grad evaluations");
   constexpr bool LOR = TERMS2 != 1;      // weight lo halves are fetched and read from the ring at all
   constexpr bool LOC = TERMS2 == 0;      // ... and multiplied in the colour layers and the rgb head (geometry trunk, label / sigma head: whenever they are read)
@@ -311,6 +323,12 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
   if (P.clk && threadIdx.x == 0) {   // fenerf_siren_clock_probe: shader-clock and wall-clock stamps of this workgroup's first instruction
     P.clk[(size_t)blockIdx.x * 4 + 0] = __builtin_amdgcn_s_memtime();
     P.clk[(size_t)blockIdx.x * 4 + 1] = __builtin_amdgcn_s_memrealtime();
+  }
+  // colour pass: the units of work are counted on the device; a workgroup without one leaves before any LDS-DMA or barrier
+  long long c_units = 0;
+  if constexpr (PASS == 2) {
+    for (int b = 0; b < P.n_images; ++b) c_units += (F.counts[b] + 127u) / 128u;
+    if ((long long)blockIdx.x >= c_units) return;
   }
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -361,7 +379,11 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     ws.voff = e_old * 1024 + ((g & 1) * 32 + row) * 16;
   }
   const unsigned long long g_stream = reinterpret_cast<unsigned long long>(P.stream + P.ring_offset_floats);
-  ws.g_next = g_stream;
+  // split passes: the first streamed stage of a tile (density: FiLM layer 1, or the head of a one-layer trunk; colour: colour layer 0)
+  constexpr unsigned long long CB = CH * 1024;
+  const unsigned long long g_c0 = g_stream + (unsigned long long)(n_geo - 1) * SQ_CHUNKS * CB;
+  const unsigned long long g_first = PASS == 2 ? g_c0 : (PASS == 1 && n_geo == 1) ? g_c0 + C0_CHUNKS * CB : g_stream;
+  ws.g_next = PASS ? g_first : g_stream;
   ws.ring_lds = __builtin_amdgcn_readfirstlane(lds_addr(ring) + wave * 1024);
   ws.ring_lane = ring + lane * 16;
   ws.early = wave < NWAVE / 2;
@@ -403,7 +425,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
   a_cur.c = ws_read<LOR>(ws, 0, 0);
   a_cur.n = ws_read<LOR>(ws, 0, 1);
 
-  for (long long unit = o_begin + bi; unit < o_end; unit += blocks_in_x) {
+  for (long long unit = PASS == 2 ? (long long)blockIdx.x : o_begin + bi; unit < (PASS == 2 ? c_units : o_end); unit += PASS == 2 ? nblk : blocks_in_x) {
   const int nsub = FUSED ? 2 * opg : 1;       // FUSED: the group's coarse octs, then its fine octs
 #pragma unroll 1
   for (int sub = 0; sub < nsub; ++sub) {
@@ -415,12 +437,27 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       if (fine_pass) { z_src = F.z_fine; out_dst = F.out_fine; }
     }
     // the previous tile ended by issuing the replicated head chunks nchunk..nchunk+D-1 (== this tile's chunks 0..D-1)
-    ws.g_next = g_stream + (unsigned long long)DPF * (CH * 1024);
+    ws.g_next = (PASS ? g_first : g_stream) + (unsigned long long)DPF * (CH * 1024);
     const long long tile = oct * NWAVE + wave;
     // ---------------- this lane's point ----------------
     long long pt = tile * 16 + n;
     if (pt >= P.P) pt = P.P - 1;
-    const long long img = __builtin_amdgcn_readfirstlane((int)(pt / P.pts_per_image));   // tiles do not straddle images (launcher)
+    long long c_img = 0, c_slot0 = 0;     // colour pass: the unit's image, this wave's first slot of its list
+    unsigned c_cnt = 0;                   // ... and the length of that list
+    if constexpr (PASS == 2) {
+      long long u = unit;
+      for (;; ++c_img) {
+        c_cnt = F.counts[c_img];
+        const long long nu = (c_cnt + 127u) / 128u;
+        if (u < nu) break;
+        u -= nu;
+      }
+      c_slot0 = (u * NWAVE + wave) * 16;
+      long long slot = c_slot0 + n;       // lanes and tiles past the count compute on the last slot and store nothing
+      if (slot >= (long long)c_cnt) slot = (long long)c_cnt - 1;
+      pt = c_img * P.pts_per_image + F.idx[c_img * F.cap + slot];
+    }
+    const long long img = PASS == 2 ? c_img : __builtin_amdgcn_readfirstlane((int)(pt / P.pts_per_image));   // tiles do not straddle images (launcher)
     float px, py, pz, dx, dy, dz;
     if (P.points) {
       px = P.points[pt * 3 + 0]; py = P.points[pt * 3 + 1]; pz = P.points[pt * 3 + 2];
@@ -459,15 +496,26 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
         glds_1k_s(reinterpret_cast<const char*>(gp) + off, vo, dst + FILM_F + off);
       }
     };
+    half8 xh[KS], xl[KS];
+    if constexpr (PASS == 2) {
+      film_issue(n_geo);
+      // the trunk output the density pass parked for this slot: this lane's own B operands of colour layer 0 (16-byte loads, no conversion)
+      long long slot = c_slot0 + (opaque(lane) & 15);
+      if (slot >= (long long)c_cnt) slot = (long long)c_cnt - 1;
+      const float4* xb = reinterpret_cast<const float4*>(F.xbuf) + ((size_t)c_img * F.cap + slot) * (KS * 8) + (opaque(lane) >> 4);
+#pragma unroll
+      for (int k = 0; k < KS; ++k) { xh[k] = as_half8(xb[(2 * k + 0) * 4]); xl[k] = as_half8(xb[(2 * k + 1) * 4]); }
+    } else {
     film_issue(0);
     if (L > 1) film_issue(1);
+    }
 
     // grid features: lane (n, g) blends channels 16 (g & 1) + 8 (g >> 1) .. + 7 of its point's 8 corners (the k slots the
     // packer gave lane group g in the grid k32-step)
     float e[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) e[i] = 0.f;
-    if (GRID) {
+    if (GRID && PASS != 1) {
       const int ch0 = 16 * (g & 1) + 8 * (g >> 1);
       // the corner walk of fenerf_grid.h (the definition this must match), in place: any inlined form moves this kernel's prologue
       const float ix = ((qx + 1.f) / 2.f) * (float)(P.gw - 1);
@@ -500,7 +548,10 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       ep[0] = make_float4(e[0], e[1], e[2], e[3]);
       ep[1] = make_float4(e[4], e[5], e[6], e[7]);
     }
-    {
+    // density pass: what of the view direction the kept rule needs
+    const bool dir_bad = PASS == 1 && !(__builtin_fabsf(dx) < __builtin_inff() && __builtin_fabsf(dy) < __builtin_inff() &&
+                                        __builtin_fabsf(dz) < __builtin_inff());
+    if constexpr (PASS != 1) {
       half8 eh, el, dh, dl;
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
@@ -524,6 +575,10 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     }
     wait_vmcnt<0>();      // film 0/1 landed (own buffer, own reads: no barrier needed), point / grid loads done; once per tile
     LDS_FENCE();
+    if constexpr (PASS == 2) {   // the reloaded operands count as arrived HERE: no wait of the compiler's behind the first DMA of the stream loop
+#pragma unroll
+      for (int k = 0; k < KS; ++k) asm volatile("" : "+v"(xh[k]), "+v"(xl[k]));
+    }
 
     // f'' of FiLM layer `layer` at this lane group's first feature (p' follows FILM_F bytes behind); derived on the spot
     auto film_lane = [&](int layer) -> const float* {
@@ -531,9 +586,8 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       return reinterpret_cast<const float*>(film_base + (layer & 1) * FILM_BYTES) + 16 * (gq >> 1) + 4 * (gq & 1);
     };
 
-    half8 xh[KS], xl[KS];
     // ---------------- layer 0: 3 -> H on the exact fp32 MFMA (16x16x4: k = x, y, z, 0) ----------------
-    {
+    if constexpr (PASS != 2) {
       const float b = g == 0 ? qx : (g == 1 ? qy : (g == 2 ? qz : 0.f));
       const int gi = n >> 2, r = n & 3;
       const float* wl = l0_lds + ((g & 1) * 32 + 16 * (gi >> 1) + 4 * (gi & 1) + r) * 4 + (g >> 1);
@@ -555,9 +609,10 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       const float* ff = film_lane(l);
       const TapeW<SAVE> tw = tape_of(l);
       half8 yh[KS], yl[KS];
-      if (l + 1 < L) film_issue(l + 1);
+      if (l + 1 < (PASS == 1 ? n_geo : L)) film_issue(l + 1);
       if (SQ_CHUNKS < DPF + 2) wait_vmcnt<0>();
       if (l == n_geo) {
+        if constexpr (PASS != 1) {
         // ---------------- colour layer 0: [x | grid feats | dir] -> H, then the label/sigma head on the same x -------
         const float4* ext = ext_wave + opaque(lane);
         auto bop0 = [&](int sp, half8& bh, half8& bl) -> bool {
@@ -573,6 +628,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
           f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
           for (int qc = 0; qc < C0_QB; ++qc) {
+            if constexpr (PASS == 2) { if (nb * C0_QB + qc == C0_CHUNKS - DPF) ws.g_next += HEAD_CHUNKS * CB; }   // over the head stage
             chunk_step<LOR, LOC, PH>(acc, a_cur, ws, nb * C0_QB + qc, 2 * qc, bop0, [&](FilmQ2& fq) {
               if (nb > 0) {
                 int p0, p1;
@@ -594,10 +650,14 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
           acc_prev[0] = acc[0]; acc_prev[1] = acc[1];
         }
 #pragma unroll
-        for (int i = NB * C0_QB; i < C0_CHUNKS; ++i) chunk_skip<LOR, PH>(a_cur, ws, i);
+        for (int i = NB * C0_QB; i < C0_CHUNKS; ++i) {
+          if constexpr (PASS == 2) { if (i == C0_CHUNKS - DPF) ws.g_next += HEAD_CHUNKS * CB; }
+          chunk_skip<LOR, PH>(a_cur, ws, i);
+        }
         epi_all<KS, FILM_F / 4, SAVE>(acc_prev, NB - 1, ff, yh, yl, tw, tile_odd);
+        }
         // head on x (the trunk output), before x is overwritten with the colour-layer-0 activations
-        {
+        if constexpr (PASS == 0) {
           f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
           auto bop = [&](int sp, half8& bh, half8& bl) -> bool {
             if (sp < KS) { bh = xh[sp]; bl = xl[sp]; return true; }
@@ -636,6 +696,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
           f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
           for (int qc = 0; qc < QB; ++qc) {
+            if constexpr (PASS == 1) { if (nb * QB + qc == SQ_CHUNKS - DPF && l == n_geo - 1) ws.g_next += C0_CHUNKS * CB; }   // over colour layer 0
             chunk_step<LOR, LOM, PH>(acc, a_cur, ws, nb * QB + qc, 2 * qc, bop, [&](FilmQ2& fq) {
               if (nb > 0) {
                 int p0, p1;
@@ -657,7 +718,10 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
           acc_prev[0] = acc[0]; acc_prev[1] = acc[1];
         }
 #pragma unroll
-        for (int i = NB * QB; i < SQ_CHUNKS; ++i) chunk_skip<LOR, PH>(a_cur, ws, i);
+        for (int i = NB * QB; i < SQ_CHUNKS; ++i) {
+          if constexpr (PASS == 1) { if (i == SQ_CHUNKS - DPF && l == n_geo - 1) ws.g_next += C0_CHUNKS * CB; }
+          chunk_skip<LOR, PH>(a_cur, ws, i);
+        }
         epi_all<KS, FILM_F / 4, SAVE>(acc_prev, NB - 1, ff, yh, yl, tw, tile_odd);
         };
         // TERMS2 = 2: three terms per product through the geometry trunk, two in the colour layers (one instantiation of the stage each; the
@@ -672,7 +736,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       for (int k = 0; k < KS; ++k) { xh[k] = yh[k]; xl[k] = yl[k]; }
     };
 #pragma unroll 1
-    for (int l = 1; l < L; ++l) {
+    for (int l = PASS == 2 ? n_geo : 1; l < (PASS == 1 ? n_geo : L); ++l) {
       // One compile-time copy of the layer per wave half (round 6): the DMA position of a wave (top of a chunk step / half a step later)
       // was a run-time flag tested in every k32-step -- two scalar branches per k32-step, one of them taken.  With the branch between
       // layers instead: 2,599,000 -> 2,444,000 shader cycles per launch (- 6.0 %), of which the power manager keeps two thirds
@@ -684,7 +748,52 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
 #endif
     }
     // ---------------- rgb head + sigmoid (rows 0..2 = row tile 0, lane group 0) ----------------
-    {
+    if constexpr (PASS == 1) {
+      // the density tile ends with the head, straight behind the trunk (x stays what it is: the list takes it).  The stage is the dense
+      // kernel's, statement for statement, as a copy of its own: sharing one lambda with the dense kernel moves the dense kernel's code
+      auto head_stage = [&](auto ph_c) {
+        constexpr int PH = decltype(ph_c)::value;
+        f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+        auto bop = [&](int sp, half8& bh, half8& bl) -> bool {
+          if (sp < KS) { bh = xh[sp]; bl = xl[sp]; return true; }
+          return false;
+        };
+#pragma unroll
+        // (the label / sigma head keeps every term the kernel reads: with TERMS2 = 2 sigma and the labels are those of the default, bit for bit)
+        for (int qc = 0; qc < QB; ++qc) {
+          if constexpr (PASS == 1) { if (qc == HEAD_CHUNKS - DPF) ws.g_next = g_first; }      // the density tile ends here: the next tile's first chunks
+          chunk_step<LOR, true, PH>(acc, a_cur, ws, qc, 2 * qc, bop, [](FilmQ2&) {}, [](const FilmQ2&) {});
+        }
+#pragma unroll
+        for (int i = QB; i < HEAD_CHUNKS; ++i) {
+          if constexpr (PASS == 1) { if (i == HEAD_CHUNKS - DPF) ws.g_next = g_first; }
+          chunk_skip<LOR, PH>(a_cur, ws, i);
+        }
+        const int lane_o = opaque(lane);
+        const int n_o = lane_o & 15, f_o = 16 * (lane_o >> 5) + 4 * ((lane_o >> 4) & 1);
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = f_o + 8 * rt + r;
+            if (row <= n_lab) {
+              const int ch = row < n_lab ? row : C - 1;
+              stage[n_o * C + ch] = acc[rt][r] * cst[row] + cst[32 + row];
+            }
+          }
+        }
+      };
+#if FENERF_WAVE_HALF_COPIES
+      if (ws.early) head_stage(std::integral_constant<int, 0>{}); else head_stage(std::integral_constant<int, 1>{});
+#else
+      head_stage(std::integral_constant<int, -1>{});
+#endif
+      const int lane_o = opaque(lane);
+      if ((lane_o >> 4) == 0) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) stage[(lane_o & 15) * C + (C - 4) + r] = 0.f;
+      }
+    } else {
       constexpr int PH = -1;
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       auto bop = [&](int sp, half8& bh, half8& bl) -> bool {
@@ -692,11 +801,29 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
         return false;
       };
 #pragma unroll
-      for (int qc = 0; qc < QB; ++qc) chunk_step<LOR, LOC, PH>(acc, a_cur, ws, qc, 2 * qc, bop, [](FilmQ2&) {}, [](const FilmQ2&) {});
+      for (int qc = 0; qc < QB; ++qc) {
+        if constexpr (PASS == 2) { if (qc == HEAD_CHUNKS - DPF) ws.g_next = g_first; }      // the colour tile ends here: the next tile's first chunks
+        chunk_step<LOR, LOC, PH>(acc, a_cur, ws, qc, 2 * qc, bop, [](FilmQ2&) {}, [](const FilmQ2&) {});
+      }
 #pragma unroll
-      for (int i = QB; i < HEAD_CHUNKS; ++i) chunk_skip<LOR, PH>(a_cur, ws, i);
+      for (int i = QB; i < HEAD_CHUNKS; ++i) {
+        if constexpr (PASS == 2) { if (i == HEAD_CHUNKS - DPF) ws.g_next = g_first; }
+        chunk_skip<LOR, PH>(a_cur, ws, i);
+      }
       const int lane_o = opaque(lane);
       const int n_o = lane_o & 15;
+      if constexpr (PASS == 2) {
+        // three floats per kept point, scattered into its row of the coarse pass
+        const long long slot = c_slot0 + n_o;
+        if ((lane_o >> 4) == 0 && slot < (long long)c_cnt) {
+          float* row = out_dst + (c_img * P.pts_per_image + F.idx[c_img * F.cap + slot]) * C + (C - 4);
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            const float v = acc[0][r] * cst[64 + r] + cst[68 + r];
+            row[r] = 1.f / (1.f + __expf(-v));
+          }
+        }
+      } else
       if ((lane_o >> 4) == 0) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
@@ -709,11 +836,41 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    {
+    if constexpr (PASS != 2) {
       const long long base = tile * 16 * C;
       const long long limit = P.P * C;
       for (int i = opaque(lane); i < 16 * C; i += 64)
         if (base + i < limit) out_dst[base + i] = stage[i];
+    }
+    if constexpr (PASS == 1) {
+      // ---------------- kept samples -> their image's list: ballot over the 16 real points, one returning atomic per wave ----------------
+      const int lane_o = opaque(lane);
+      const int n_o = lane_o & 15, g_o = lane_o >> 4;
+      // non-finite colour parameters keep every sample (the reference's 0 * NaN is a NaN pixel): the model's flag word, or a non-finite
+      // f'' / p' in this image's appearance block
+      bool film_bad = false;
+      for (int i = lane_o; i < n_color * H; i += 64) {
+        const float fv = fp_img[(size_t)n_geo * H + i], pv = pp_img[(size_t)n_geo * H + i];
+        film_bad |= !(__builtin_fabsf(fv) < __builtin_inff()) || !(__builtin_fabsf(pv) < __builtin_inff());
+      }
+      const bool keep_all = (F.keep_all[0] | F.keep_all[1]) != 0u || __builtin_amdgcn_ballot_w64(film_bad) != 0ull;
+      const float sg = stage[n_o * C + (C - 1)];
+      const long long pt_raw = tile * 16 + n_o;                      // clamped phantom lanes never count
+      const bool keep = pt_raw < P.P && (!(sg <= 0.f) || dir_bad || keep_all);
+      const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep) & 0xffffull;
+      const unsigned cnt = (unsigned)__builtin_popcountll(bal);
+      unsigned b0 = 0;
+      if (lane_o == 0 && cnt) b0 = atomicAdd(F.counts + img, cnt);
+      const unsigned slot = (unsigned)__builtin_amdgcn_readfirstlane((int)b0) + (unsigned)__builtin_popcountll(bal & ((1ull << n_o) - 1ull));
+      if (keep) {
+        if (g_o == 0) F.idx[img * F.cap + slot] = (unsigned)(pt_raw - img * P.pts_per_image);
+        float4* xb = reinterpret_cast<float4*>(F.xbuf) + ((size_t)img * F.cap + slot) * (KS * 8) + g_o;
+#pragma unroll
+        for (int k = 0; k < KS; ++k) {
+          xb[(2 * k + 0) * 4] = __builtin_bit_cast(float4, xh[k]);
+          xb[(2 * k + 1) * 4] = __builtin_bit_cast(float4, xl[k]);
+        }
+      }
     }
     wait_vmcnt<0>();   // stores may retire out of order with the DMA loads: keep them out of the counted waits
     __builtin_amdgcn_wave_barrier();
@@ -788,6 +945,18 @@ static int launch_t(const FenerfModel* m, const SirenParams& p, void* stream) {
   return check_launch("siren16w launch");
 }
 
+// The split coarse pass (PASS = 1 density, PASS = 2 colour): `blocks` persistent workgroups
+template <int H, bool GRID, int PASS>
+static int launch_split_t(const FenerfModel* m, const SirenParams& p, const SplitArgs& s, unsigned blocks, void* stream) {
+  const size_t lds = lds_bytes_16w(m, H);
+  auto kfn = siren16w_kernel<H, GRID, 0, false, 0, PASS>;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
+  FuseArgs<false, PASS> F;
+  static_cast<SplitArgs&>(F) = s;
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, m->C, F);
+  return check_launch(PASS == 1 ? "siren16w density launch" : "siren16w colour launch");
+}
+
 }  // namespace w16
 
 // One launch over points whose tiles do not straddle images.
@@ -832,6 +1001,31 @@ int launch_render16w_fused(const FenerfModel* m, const SirenParams& p, const Fus
   });
 }
 
+// image b of a launch over several, as a launch of its own
+static SirenParams image_params(const FenerfModel* m, const SirenParams& p, long long b) {
+  const int L = m->L, H = m->H;
+  SirenParams q = p;
+  q.P = p.pts_per_image;
+  q.fp = p.fp + (size_t)b * L * H;
+  q.pp = p.pp + (size_t)b * L * H;
+  if (p.raw_fg) {   // FiLM pre-pass in the launch: this image's raw blocks
+    q.raw_fg = p.raw_fg + (size_t)b * m->n_geo * H; q.raw_pg = p.raw_pg + (size_t)b * m->n_geo * H;
+    q.raw_fa = p.raw_fa + (size_t)b * m->n_color * H; q.raw_pa = p.raw_pa + (size_t)b * m->n_color * H;
+    q.n_images = 1;
+  }
+  q.out = p.out + (size_t)b * p.pts_per_image * m->C;
+  if (p.points) {
+    q.points = p.points + (size_t)b * p.pts_per_image * 3;
+    if (p.pdirs) q.pdirs = p.pdirs + (size_t)b * p.pts_per_image * 3;
+  } else {
+    const long long rays = p.pts_per_image / p.n_per_ray;
+    q.origins = p.origins + (size_t)b * rays * 3;
+    q.dirs = p.dirs + (size_t)b * rays * 3;
+    q.z = p.z + (size_t)b * p.pts_per_image;
+  }
+  return q;
+}
+
 // FENERF_PREC_F16X3 models, forward and forward-save.  Tiles must not straddle images (FiLM parameters are fetched per wave, the
 // tape is laid out in 32-point tiles per image): when points-per-image is not a multiple of 32, launch image by image (each
 // launch ends in a ragged tile).
@@ -839,31 +1033,41 @@ int launch_siren16w(const FenerfModel* m, const SirenParams& p, void* stream) {
   if (p.P <= 0) return FENERF_OK;
   if (p.pts_per_image % 32 == 0 || p.P == p.pts_per_image) return launch_siren16w_one(m, p, stream);
   const long long nimg = p.P / p.pts_per_image;
-  const int L = m->L, H = m->H;
   for (long long b = 0; b < nimg; ++b) {
-    SirenParams q = p;
-    q.P = p.pts_per_image;
-    q.fp = p.fp + (size_t)b * L * H;
-    q.pp = p.pp + (size_t)b * L * H;
-    if (p.raw_fg) {   // FiLM pre-pass in the launch: this image's raw blocks
-      q.raw_fg = p.raw_fg + (size_t)b * m->n_geo * H; q.raw_pg = p.raw_pg + (size_t)b * m->n_geo * H;
-      q.raw_fa = p.raw_fa + (size_t)b * m->n_color * H; q.raw_pa = p.raw_pa + (size_t)b * m->n_color * H;
-      q.n_images = 1;
-    }
-    q.out = p.out + (size_t)b * p.pts_per_image * m->C;
-    if (p.points) {
-      q.points = p.points + (size_t)b * p.pts_per_image * 3;
-      if (p.pdirs) q.pdirs = p.pdirs + (size_t)b * p.pts_per_image * 3;
-    } else {
-      const long long rays = p.pts_per_image / p.n_per_ray;
-      q.origins = p.origins + (size_t)b * rays * 3;
-      q.dirs = p.dirs + (size_t)b * rays * 3;
-      q.z = p.z + (size_t)b * p.pts_per_image;
-    }
-    int rc = launch_siren16w_one(m, q, stream);
+    int rc = launch_siren16w_one(m, image_params(m, p, b), stream);
     if (rc) return rc;
   }
   return FENERF_OK;
+}
+
+// Density pass of the split coarse launch: every sample's labels and sigma, rgb = 0, and the per-image lists of kept samples.
+int launch_siren16w_density(const FenerfModel* m, const SirenParams& p, const SplitArgs& s, void* stream) {
+  if (p.P <= 0) return FENERF_OK;
+  auto one = [&](const SirenParams& q, const SplitArgs& t) {
+    return dispatch_width(m->H, m->grid_ch != 0, [&](auto h, auto g) {
+      return w16::launch_split_t<decltype(h)::value, decltype(g)::value, 1>(m, q, t, persistent_blocks((q.P + 15) / 16, w16::NWAVE, m->num_cus), stream);
+    });
+  };
+  if (p.pts_per_image % 32 == 0 || p.P == p.pts_per_image) return one(p, s);
+  const long long nimg = p.P / p.pts_per_image;
+  for (long long b = 0; b < nimg; ++b) {     // ragged images: one launch each, on its own list
+    SplitArgs t = s;
+    t.counts = s.counts + b; t.idx = s.idx + (size_t)b * s.cap; t.xbuf = s.xbuf + (size_t)b * s.cap * m->H;
+    int rc = one(image_params(m, p, b), t);
+    if (rc) return rc;
+  }
+  return FENERF_OK;
+}
+
+// Colour pass: one persistent launch over the lists of all images (its units never straddle images); sized for the lists' capacity, the
+// workgroups beyond the counted units return at once.
+int launch_siren16w_colour(const FenerfModel* m, const SirenParams& p, const SplitArgs& s, void* stream) {
+  if (p.P <= 0) return FENERF_OK;
+  const long long nimg = p.P / p.pts_per_image;
+  const long long max_units = nimg * ((p.pts_per_image + 127) / 128);
+  return dispatch_width(m->H, m->grid_ch != 0, [&](auto h, auto g) {
+    return w16::launch_split_t<decltype(h)::value, decltype(g)::value, 2>(m, p, s, persistent_blocks(max_units, 1, m->num_cus), stream);
+  });
 }
 
 }  // namespace fenerf

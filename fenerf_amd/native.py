@@ -1107,6 +1107,25 @@ class render_fusion:
         return False
 
 
+class render_split:
+    """with native.render_split("off" | "force" | "auto"): ...  -- how the calling thread's hierarchical four-launch renders run their coarse
+    SIREN launch inside the block (include/fenerf.h fenerf_set_render_split): one dense launch ("off"), a density launch + a colour launch
+    over the samples with sigma > 0 only ("force": FENERF_E_UNSUPPORTED where the route's conditions do not hold), or the split route where
+    they hold ("auto", the default).  The results are the same bit for bit."""
+    MODES = {"auto": _lib.SPLIT_AUTO, "off": _lib.SPLIT_OFF, "force": _lib.SPLIT_FORCE}
+
+    def __init__(self, mode):
+        self.mode = self.MODES[mode]
+
+    def __enter__(self):
+        self._prev = _lib.lib().fenerf_set_render_split(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        _lib.lib().fenerf_set_render_split(self._prev)
+        return False
+
+
 class cu_budget:
     """with native.cu_budget(n): ...  -- the calling thread's launches inside the block are sized for at most n compute units
     (include/fenerf.h fenerf_set_cu_budget; 0 / None = the whole device).  Workspace sizes are queried under the same setting."""

@@ -217,6 +217,23 @@ int fenerf_set_cu_budget(int cus);
 #define FENERF_FUSION_OFF 1
 #define FENERF_FUSION_FORCE 2
 int fenerf_set_render_fusion(int mode);
+/* How the CALLING THREAD's fenerf_render_forward calls run the COARSE SIREN launch of a hierarchical four-launch render (no reference
+ * analogue; rgb, depth, weights and weights_sum are the same bit for bit either way):
+ *   FENERF_SPLIT_OFF    one dense launch: every coarse sample through the whole network;
+ *   FENERF_SPLIT_FORCE  a density launch (trunk, labels, sigma; rgb rows 0) that lists, per image, the samples whose colour can reach a
+ *        pixel -- !(sigma <= 0), a non-finite view direction, or non-finite colour parameters (then every sample) --, the sigma-only
+ *        composite + resampling, then a colour launch over the listed samples only, from their parked trunk outputs.  Under the relu clamp
+ *        an unlisted sample has alpha = 0 exactly, so its colour meets an exact zero in the final composite.  Conditions: a
+ *        FENERF_PREC_F16X3 model at FENERF_FORWARD_F16X3, clamp_mode relu, last_back off, noise_std == 0 or noise_final == NULL, and the
+ *        one-launch route (fenerf_set_render_fusion) not taken; FENERF_E_UNSUPPORTED from fenerf_render_forward when they do not hold;
+ *   FENERF_SPLIT_AUTO (default)  the split route where the conditions hold (measured faster: profiles/r16_split_forward.md), the dense
+ *        launch otherwise.
+ * The workspace (fenerf_render_workspace_bytes) holds the lists at capacity -- H * 4 + 4 bytes per coarse sample -- of which only the kept
+ * samples' slots are touched.  Returns the previous mode. */
+#define FENERF_SPLIT_AUTO 0
+#define FENERF_SPLIT_OFF 1
+#define FENERF_SPLIT_FORCE 2
+int fenerf_set_render_split(int mode);
 
 long fenerf_struct_size(const char* struct_name);
 long fenerf_struct_field_offset(const char* struct_name, const char* field);
@@ -396,8 +413,14 @@ double fenerf_siren_executed_flop_per_point(const FenerfModel* m);
 /* Per-phase device times of everything the library launches (bench.py's generator-step breakdown).  fenerf_phase_timing(1)
  * makes every launch group record a hipEvent pair on its stream (off by default: no events, no cost); fenerf_phase_times
  * synchronises those events, ADDS the elapsed milliseconds / launch-group counts per phase into ms[] / calls[] (n >=
- * FENERF_N_PHASES entries, caller-zeroed) and forgets them.  fenerf_phase_name(i) names phase i ("forward_save", "chain", ...). */
-#define FENERF_N_PHASES 17
+ * FENERF_N_PHASES entries, caller-zeroed) and forgets them.  fenerf_phase_name(i) names phase i ("forward_save", "chain", ...).
+ * The two launches of the split coarse pass (fenerf_set_render_split) are "siren_density" and "siren_colour"; the density launch, being the
+ * render's coarse SIREN launch, is ALSO counted and timed under "siren_forward" (so that phase keeps its two launches per hierarchical
+ * render): a sum over all phases counts it twice.  These two phases were added without breaking callers built against 17 phases
+ * (FENERF_ABI_VERSION is unchanged): n >= FENERF_N_PHASES is still all that is required, and a caller that passes fewer than
+ * FENERF_N_PHASES_ALL entries simply does not receive the phases beyond its arrays (their records are forgotten like the others). */
+#define FENERF_N_PHASES 17        /* the least a caller must pass: the phases up to "render_fused" */
+#define FENERF_N_PHASES_ALL 19    /* ... + "siren_density", "siren_colour" */
 int fenerf_phase_timing(int enable);
 int fenerf_phase_times(double* ms, int* calls, int n);
 const char* fenerf_phase_name(int phase);
