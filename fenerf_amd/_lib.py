@@ -171,6 +171,7 @@ _SIGS = {
                                             _vp, C.POINTER(FenerfSirenGrads), _i64, _i64, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp]),
     "fenerf_sparse_select_workspace_bytes": (C.c_size_t, [_i, _i64]),
     "fenerf_sparse_select": (_i, [_i, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fenerf_split_scan": (_i, [_i, _i64, _i64, _vp, _vp, _vp, _vp]),
     # marching tetrahedra on a device volume (fenerf_mesh.hip)
     "fenerf_mesh_workspace_bytes": (_sz, [_i, _i, _i]),
     "fenerf_mesh_count": (_i, [_vp, _i, _i, _i, C.c_float, _vp, _vp, _vp]),

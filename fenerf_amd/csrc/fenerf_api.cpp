@@ -1195,6 +1195,12 @@ extern "C" int fenerf_sparse_select(int B, int R, int N, int C, int64_t cap, con
   { PhaseScope ph(PH_OTHER, stream); return launch_sparse_select(B, R, N, C, cap, d_coarse, d_fine, z_coarse, z_fine, origins, dirs, (const long long*)images, pts, rd, d_sel, counts, workspace, stream); }
 }
 
+extern "C" int fenerf_split_scan(int B, int64_t tiles, int64_t cap, const uint16_t* masks, uint32_t* idx, uint32_t* counts, void* stream) {
+  if (B < 1 || B > 65535 || tiles < 1 || tiles > ((int64_t)1 << 27) || cap < 16 * tiles) return fail(FENERF_E_INVALID, "need 1 <= B <= 65535, 1 <= tiles <= 2^27, cap >= 16 tiles");
+  if (!masks || !idx || !counts) return fail(FENERF_E_INVALID, "fenerf_split_scan: masks / idx / counts is NULL");
+  { PhaseScope ph(PH_OTHER, stream); return launch_split_scan(masks, B, tiles, cap, idx, counts, stream); }
+}
+
 // ---- iso-surface extraction (fenerf_mesh.hip) ----
 namespace {
 int check_lattice(const char* who, int n0, int n1, int n2) {
@@ -1419,7 +1425,7 @@ extern "C" int fenerf_volume_render(const float* vol, int n0, int n1, int n2, in
 // workspace layout of fenerf_render_forward
 namespace {
 struct RenderWs {
-  size_t film, coarse, fine, wts, zf, counts, idx, xbuf, total;
+  size_t film, coarse, fine, wts, zf, counts, idx, masks, xbuf, total;
 };
 RenderWs render_ws(const FenerfModel* m, int B, int R, int N, int hier) {
   RenderWs w;
@@ -1430,11 +1436,12 @@ RenderWs render_ws(const FenerfModel* m, int B, int R, int N, int hier) {
   w.fine = off; off += hier ? align_up(pts * m->C * sizeof(float), 256) : 0;
   w.wts = off; off += hier ? align_up(pts * sizeof(float), 256) : 0;
   w.zf = off; off += hier ? align_up(pts * sizeof(float), 256) : 0;
-  // the split coarse pass (fenerf_set_render_split): per image a counter, a list of R N sample indices and R N slots of H * 4 bytes for the
-  // trunk outputs of the kept samples -- capacity for every sample, touched only as far as the lists grow
+  // the split coarse pass (fenerf_set_render_split): per image a counter, a list of R N sample indices, a 16-bit kept mask per 16-sample
+  // tile and R N slots of H * 4 bytes for the trunk outputs of the kept samples -- a slot per sample, touched only where a sample is kept
   const bool split = hier && m->precision == FENERF_PREC_F16X3;
   w.counts = off; off += split ? align_up((size_t)B * sizeof(unsigned), 256) : 0;
   w.idx = off; off += split ? align_up(pts * sizeof(unsigned), 256) : 0;
+  w.masks = off; off += split ? align_up((size_t)B * split_tiles_per_image((long long)R * N) * sizeof(unsigned short), 256) : 0;
   w.xbuf = off; off += split ? align_up(pts * (size_t)m->H * sizeof(float), 256) : 0;
   w.total = off;
   return w;
@@ -1525,10 +1532,10 @@ extern "C" int fenerf_render_forward(const FenerfModel* m, int B, int R, int N, 
   memset(&sa, 0, sizeof(sa));
   if (split) {
     sa.counts = (unsigned*)(base + ws.counts); sa.idx = (unsigned*)(base + ws.idx); sa.xbuf = (float*)(base + ws.xbuf);
+    sa.masks = (unsigned short*)(base + ws.masks);
     sa.cap = (long long)R * N; sa.keep_all = m->d_colour_nonfinite;
-    HIP_TRY(hipMemsetAsync(sa.counts, 0, (size_t)B * sizeof(unsigned), (hipStream_t)stream));
     // timed as a SIREN forward launch (it is the route's coarse launch: "siren_forward" keeps counting two per hierarchical render) and,
-    // inside that, under its own name
+    // inside that, under its own name; the scan that turns the tile masks into the lists is part of it
     rc = [&] { PhaseScope ph(PH_SIREN, stream); PhaseScope pd(PH_SIREN_DENSITY, stream); return launch_siren16w_density(m, sp, sa, stream); }();
   } else {
     rc = run_siren(m, sp, stream);                     // coarse pass   (generators.py:479)

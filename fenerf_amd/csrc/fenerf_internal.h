@@ -209,15 +209,21 @@ int launch_ray_grads(int B, int R, int N, long long Pp, int passes, const float*
 int launch_siren16w(const FenerfModel* m, const SirenParams& p, void* stream);   // f16x3 forward / forward-save, 16-point waves (fenerf_siren_f16w.hip)
 // The coarse launch of a hierarchical render as a density pass and a compacted colour pass (fenerf_siren_f16w.hip, PASS): per image a
 // list of the samples whose colour can reach a pixel.  `cap` = slots per image (the image's sample count: a list cannot overflow).
+// The density pass writes one kept mask per 16-sample tile and parks a kept sample's trunk output at the sample's own slot; a scan of the
+// masks (launch_split_scan, inside launch_siren16w_density) makes the lists, in ascending sample order.
 struct SplitArgs {
-  unsigned* counts;          // [B]        kept samples per image (zeroed before the density pass)
-  unsigned* idx;             // [B][cap]   sample index within the image
-  float* xbuf;               // [B][cap][H/32][hi | lo][4 lane groups]  the trunk output as colour layer 0's B operands (H * 4 bytes per slot)
+  unsigned* counts;          // [B]        kept samples per image (written by the scan)
+  unsigned* idx;             // [B][cap]   sample index within the image, ascending (written by the scan)
+  float* xbuf;               // [B][cap][H/32][hi | lo][4 lane groups]  the trunk output as colour layer 0's B operands (H * 4 bytes per sample)
+  unsigned short* masks;     // [B][split_tiles_per_image]  bit n: sample 16 tile + n is kept (every tile's mask is written by every density pass)
   long long cap;
   const unsigned* keep_all;  // the model's two flag words: either non-zero = a non-finite colour weight or grid voxel, every sample is kept
 };
+inline long long split_tiles_per_image(long long pts_per_image) { return (pts_per_image + 15) / 16; }
 int launch_siren16w_density(const FenerfModel* m, const SirenParams& p, const SplitArgs& s, void* stream);
 int launch_siren16w_colour(const FenerfModel* m, const SirenParams& p, const SplitArgs& s, void* stream);    // p.out: the density pass's rows
+// fenerf_repack.hip: idx / counts of B images from their tile masks (one launch, a workgroup per 256 tiles of an image)
+int launch_split_scan(const unsigned short* masks, int B, long long tiles_per_image, long long cap, unsigned* idx, unsigned* counts, void* stream);
 // fenerf_repack.hip: m->d_colour_nonfinite[0] <- "the packed stream or the consts hold a non-finite value", [1] <- "the relaid grid does" (grid_too)
 int launch_nonfinite_scan(FenerfModel* m, bool grid_too, void* stream);
 // fenerf_render_forward as ONE launch (fenerf_siren_f16w.hip, FUSED): ray groups of whole octs, see there

@@ -182,4 +182,56 @@ int launch_nonfinite_scan(FenerfModel* m, bool grid_too, void* stream) {
   return check_launch("non-finite scan launch");
 }
 
+// The kept lists of the split render, from the density pass's tile masks (bit n of masks[b][tile] = sample 16 tile + n of image b is kept):
+// per image the exclusive prefix over the masks' popcounts gives every kept sample its list entry, idx[b][prefix + r] in ascending sample
+// order, and counts[b].  No atomics: the lists are the same on every run.  The grid is ceil(tiles / 256) workgroups per image, image-major
+// in x; a workgroup takes 256 tiles, one per thread.  What the tiles before its own hold it counts itself (a strided pass over the
+// image's earlier masks: every workgroup is independent of every other), then the scan of sparse_scan_kernel (fenerf_render_grad.hip)
+// over its own tiles.  Not one workgroup per image: at B = 1 that is one CU writing the whole list (141,531 entries at 128 x 128 x 24)
+// while 255 stand idle, on the critical path between the density launch and the composite.  The price is the re-count, tiles^2 / 512
+// mask reads per image in all: 96 workgroups x at most 48 KB at that shape (out of L2), 4 GB at 2^20 tiles (16.8 M samples) per image --
+// beyond that a carry between workgroups is the better kernel.  Both measured in profiles/r17_split_lists.md.
+__global__ void __launch_bounds__(256) split_scan_kernel(const unsigned short* masks, long long tiles, long long cap, unsigned wgs_per_image,
+                                                         unsigned* idx, unsigned* counts) {
+  const unsigned b = blockIdx.x / wgs_per_image, piece = blockIdx.x - b * wgs_per_image;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const unsigned short* mk = masks + (long long)b * tiles;
+  unsigned* out = idx + (long long)b * cap;
+  const long long first = (long long)piece * 256, j = first + t;
+  __shared__ unsigned wave_part[4], wave_sum[4];
+  unsigned part = 0;                                        // kept samples of the tiles before this workgroup's
+  for (long long i = t; i < first; i += 256) part += __popc((unsigned)mk[i]);
+  for (int o = 32; o; o >>= 1) part += __shfl_xor(part, o);
+  const unsigned m = j < tiles ? (unsigned)mk[j] : 0u;
+  const unsigned v = __popc(m);
+  unsigned incl = v;                                        // inclusive scan inside the wave
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned u = __shfl_up(incl, o);
+    if (lane >= o) incl += u;
+  }
+  if (lane == 63) wave_sum[w] = incl;
+  if (lane == 0) wave_part[w] = part;
+  __syncthreads();
+  unsigned before = wave_part[0] + wave_part[1] + wave_part[2] + wave_part[3];
+  for (int k = 0; k < w; ++k) before += wave_sum[k];
+  unsigned slot = before + incl - v;
+  for (unsigned mm = m; mm; mm &= mm - 1u) {
+    if (slot < cap) out[slot] = (unsigned)j * 16u + (unsigned)__builtin_ctz(mm);
+    ++slot;
+  }
+  if (piece == wgs_per_image - 1 && t == 255) {             // the image's last thread holds the total
+    const unsigned total = before + incl;
+    counts[b] = total < cap ? total : (unsigned)cap;        // (phantom lanes carry no bit: a list cannot outgrow its image)
+  }
+}
+
+int launch_split_scan(const unsigned short* masks, int B, long long tiles_per_image, long long cap, unsigned* idx, unsigned* counts, void* stream) {
+  if (B <= 0 || tiles_per_image <= 0) return FENERF_OK;
+  const long long wpi = (tiles_per_image + 255) / 256;       // images sit in grid.x (grid.y ends at 65,535 images)
+  if (wpi * B > 0x7fffffffLL) return fail(FENERF_E_INVALID, "split scan: more than 2^31 - 1 workgroups (images x ceil(tiles per image / 256))");
+  hipLaunchKernelGGL(split_scan_kernel, dim3((unsigned)(wpi * B)), dim3(256), 0, (hipStream_t)stream, masks, tiles_per_image, cap, (unsigned)wpi, idx,
+                     counts);
+  return check_launch("split scan launch");
+}
+
 }  // namespace fenerf

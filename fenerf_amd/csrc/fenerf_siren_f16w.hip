@@ -294,9 +294,10 @@ template <> struct FuseArgs<true, 0> {
 // PASS (round 16, fenerf_set_render_split): the coarse launch of a hierarchical render as two launches on the one packed stream.
 //   PASS = 1, density pass: layer 0, the geometry trunk and the label / sigma head of every sample; rgb is written as 0.  A sample whose
 //             colour can reach a pixel -- !(sigma <= 0), or a non-finite view direction, or non-finite colour parameters (S.keep_all / the
-//             image's appearance FiLM block) -- takes a slot of its image's list: its index and its trunk output, the xh / xl registers as
-//             colour layer 0 consumes them ([slot][k32-step][hi | lo][lane group] x 16 bytes = 1 KiB at H = 256).
-//   PASS = 2, colour pass: a persistent launch over octs of 8 x 16 slots of one image, sized on the device from counts[]: reloads xh / xl,
+//             image's appearance FiLM block) -- sets its bit in its tile's mask and parks its trunk output at its own slot, the xh / xl
+//             registers as colour layer 0 consumes them ([sample][k32-step][hi | lo][lane group] x 16 bytes = 1 KiB at H = 256).  A scan of
+//             the masks behind the launch (launch_split_scan) makes each image's list of kept sample indices, ascending, and its count.
+//   PASS = 2, colour pass: a persistent launch over octs of 8 x 16 list entries of one image, sized on the device from counts[]: reloads xh / xl,
 //             recomputes the point, gathers the grid, runs colour layer 0, the colour layers and the rgb head and scatters three floats.
 // Both walk the stream with jumps of g_next over the stages they do not run (every stage is whole ring revolutions: the slot indices stay);
 // a kept sample's column sees the dense kernel's MFMA sequence on the dense kernel's operands, so its outputs are the dense kernel's bits.
@@ -424,6 +425,8 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
   APipe a_cur;
   a_cur.c = ws_read<LOR>(ws, 0, 0);
   a_cur.n = ws_read<LOR>(ws, 0, 1);
+  [[maybe_unused]] long long chk_img = -1;     // density pass: the image whose appearance FiLM block this wave checked last, and what the check gave
+  [[maybe_unused]] bool chk_all = false;
 
   for (long long unit = PASS == 2 ? (long long)blockIdx.x : o_begin + bi; unit < (PASS == 2 ? c_units : o_end); unit += PASS == 2 ? nblk : blocks_in_x) {
   const int nsub = FUSED ? 2 * opg : 1;       // FUSED: the group's coarse octs, then its fine octs
@@ -499,10 +502,8 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     half8 xh[KS], xl[KS];
     if constexpr (PASS == 2) {
       film_issue(n_geo);
-      // the trunk output the density pass parked for this slot: this lane's own B operands of colour layer 0 (16-byte loads, no conversion)
-      long long slot = c_slot0 + (opaque(lane) & 15);
-      if (slot >= (long long)c_cnt) slot = (long long)c_cnt - 1;
-      const float4* xb = reinterpret_cast<const float4*>(F.xbuf) + ((size_t)c_img * F.cap + slot) * (KS * 8) + (opaque(lane) >> 4);
+      // the trunk output the density pass parked at this sample's slot: this lane's own B operands of colour layer 0 (16-byte loads, no conversion)
+      const float4* xb = reinterpret_cast<const float4*>(F.xbuf) + ((size_t)c_img * F.cap + (size_t)(pt - c_img * P.pts_per_image)) * (KS * 8) + (opaque(lane) >> 4);
 #pragma unroll
       for (int k = 0; k < KS; ++k) { xh[k] = as_half8(xb[(2 * k + 0) * 4]); xl[k] = as_half8(xb[(2 * k + 1) * 4]); }
     } else {
@@ -836,41 +837,41 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if constexpr (PASS != 2) {
-      const long long base = tile * 16 * C;
-      const long long limit = P.P * C;
-      for (int i = opaque(lane); i < 16 * C; i += 64)
-        if (base + i < limit) out_dst[base + i] = stage[i];
-    }
     if constexpr (PASS == 1) {
-      // ---------------- kept samples -> their image's list: ballot over the 16 real points, one returning atomic per wave ----------------
+      // ---------------- kept samples: the tile's mask, and the trunk output parked at the sample's own slot ----------------
+      // (nothing here waits on memory or on another wave: the lists are made from the masks by launch_split_scan, behind this launch)
       const int lane_o = opaque(lane);
       const int n_o = lane_o & 15, g_o = lane_o >> 4;
       // non-finite colour parameters keep every sample (the reference's 0 * NaN is a NaN pixel): the model's flag word, or a non-finite
-      // f'' / p' in this image's appearance block
-      bool film_bad = false;
-      for (int i = lane_o; i < n_color * H; i += 64) {
-        const float fv = fp_img[(size_t)n_geo * H + i], pv = pp_img[(size_t)n_geo * H + i];
-        film_bad |= !(__builtin_fabsf(fv) < __builtin_inff()) || !(__builtin_fabsf(pv) < __builtin_inff());
+      // f'' / p' in this image's appearance block -- checked once per image this wave meets
+      if (img != chk_img) {
+        bool film_bad = false;
+        for (int i = lane_o; i < n_color * H; i += 64) {
+          const float fv = fp_img[(size_t)n_geo * H + i], pv = pp_img[(size_t)n_geo * H + i];
+          film_bad |= !(__builtin_fabsf(fv) < __builtin_inff()) || !(__builtin_fabsf(pv) < __builtin_inff());
+        }
+        chk_all = (F.keep_all[0] | F.keep_all[1]) != 0u || __builtin_amdgcn_ballot_w64(film_bad) != 0ull;
+        chk_img = img;
       }
-      const bool keep_all = (F.keep_all[0] | F.keep_all[1]) != 0u || __builtin_amdgcn_ballot_w64(film_bad) != 0ull;
       const float sg = stage[n_o * C + (C - 1)];
       const long long pt_raw = tile * 16 + n_o;                      // clamped phantom lanes never count
-      const bool keep = pt_raw < P.P && (!(sg <= 0.f) || dir_bad || keep_all);
+      const bool keep = pt_raw < P.P && (!(sg <= 0.f) || dir_bad || chk_all);
       const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep) & 0xffffull;
-      const unsigned cnt = (unsigned)__builtin_popcountll(bal);
-      unsigned b0 = 0;
-      if (lane_o == 0 && cnt) b0 = atomicAdd(F.counts + img, cnt);
-      const unsigned slot = (unsigned)__builtin_amdgcn_readfirstlane((int)b0) + (unsigned)__builtin_popcountll(bal & ((1ull << n_o) - 1ull));
       if (keep) {
-        if (g_o == 0) F.idx[img * F.cap + slot] = (unsigned)(pt_raw - img * P.pts_per_image);
-        float4* xb = reinterpret_cast<float4*>(F.xbuf) + ((size_t)img * F.cap + slot) * (KS * 8) + g_o;
+        float4* xb = reinterpret_cast<float4*>(F.xbuf) + ((size_t)img * F.cap + (size_t)(pt_raw - img * P.pts_per_image)) * (KS * 8) + g_o;
 #pragma unroll
         for (int k = 0; k < KS; ++k) {
           xb[(2 * k + 0) * 4] = __builtin_bit_cast(float4, xh[k]);
           xb[(2 * k + 1) * 4] = __builtin_bit_cast(float4, xl[k]);
         }
       }
+      if (lane_o == 0 && tile < ntiles) F.masks[tile] = (unsigned short)bal;      // phantom tiles of the last oct have no mask
+    }
+    if constexpr (PASS != 2) {
+      const long long base = tile * 16 * C;
+      const long long limit = P.P * C;
+      for (int i = opaque(lane); i < 16 * C; i += 64)
+        if (base + i < limit) out_dst[base + i] = stage[i];
     }
     wait_vmcnt<0>();   // stores may retire out of order with the DMA loads: keep them out of the counted waits
     __builtin_amdgcn_wave_barrier();
@@ -1048,15 +1049,18 @@ int launch_siren16w_density(const FenerfModel* m, const SirenParams& p, const Sp
       return w16::launch_split_t<decltype(h)::value, decltype(g)::value, 1>(m, q, t, persistent_blocks((q.P + 15) / 16, w16::NWAVE, m->num_cus), stream);
     });
   };
-  if (p.pts_per_image % 32 == 0 || p.P == p.pts_per_image) return one(p, s);
-  const long long nimg = p.P / p.pts_per_image;
-  for (long long b = 0; b < nimg; ++b) {     // ragged images: one launch each, on its own list
-    SplitArgs t = s;
-    t.counts = s.counts + b; t.idx = s.idx + (size_t)b * s.cap; t.xbuf = s.xbuf + (size_t)b * s.cap * m->H;
-    int rc = one(image_params(m, p, b), t);
-    if (rc) return rc;
+  const long long nimg = p.P / p.pts_per_image, tpi = split_tiles_per_image(p.pts_per_image);
+  if (p.pts_per_image % 32 == 0 || p.P == p.pts_per_image) {
+    if (int rc = one(p, s)) return rc;
+  } else {
+    for (long long b = 0; b < nimg; ++b) {     // ragged images: one launch each, on its own masks and slots
+      SplitArgs t = s;
+      t.masks = s.masks + (size_t)b * tpi; t.xbuf = s.xbuf + (size_t)b * s.cap * m->H;
+      int rc = one(image_params(m, p, b), t);
+      if (rc) return rc;
+    }
   }
-  return FENERF_OK;
+  return launch_split_scan(s.masks, (int)nimg, tpi, s.cap, s.idx, s.counts, stream);    // the lists of all images, from the masks
 }
 
 // Colour pass: one persistent launch over the lists of all images (its units never straddle images); sized for the lists' capacity, the

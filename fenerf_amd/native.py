@@ -1351,6 +1351,20 @@ def sparse_select(d_coarse, d_fine, z_coarse, z_fine, origins, dirs, cap, want_d
     return pts, rd, d_sel, counts
 
 
+def split_scan(masks, cap=None):
+    """The list step of the split coarse pass on its own (fenerf_split_scan, include/fenerf.h): masks int16 / uint16-as-int16 device tensor
+    [B, tiles], bit n of masks[b, t] = sample 16 t + n of image b is kept.  -> idx int32 [B, cap] (entries 0 .. counts[b] - 1 of row b: the
+    kept sample indices, ascending; the rest is left at -1), counts int32 [B]."""
+    assert masks.is_cuda and masks.dtype == torch.int16 and masks.dim() == 2 and masks.is_contiguous()
+    B, tiles = masks.shape
+    cap = 16 * tiles if cap is None else cap
+    idx = torch.full((B, cap), -1, dtype=torch.int32, device=masks.device)
+    counts = torch.empty((B,), dtype=torch.int32, device=masks.device)
+    with torch.cuda.device(masks.device):
+        _lib.check(_lib.lib().fenerf_split_scan(B, tiles, cap, C.c_void_p(masks.data_ptr()), C.c_void_p(idx.data_ptr()), C.c_void_p(counts.data_ptr()), _stream()))
+    return idx, counts
+
+
 def ray_grads(d_points, d_viewdirs, z_coarse, z_fine=None, want_origins=True, want_dirs=True):
     """Per-sample gradients -> per-ray gradients (fenerf_ray_grads, include/fenerf.h): d_points / d_viewdirs [passes * B, Pp, 3] (pass-major;
     Pp = R * N rounded up to whole 32-point tiles, the pad rows are never read; d_viewdirs None under a locked view) as siren_input_grads

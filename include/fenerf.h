@@ -228,8 +228,9 @@ int fenerf_set_render_fusion(int mode);
  *        one-launch route (fenerf_set_render_fusion) not taken; FENERF_E_UNSUPPORTED from fenerf_render_forward when they do not hold;
  *   FENERF_SPLIT_AUTO (default)  the split route where the conditions hold (measured faster: profiles/r16_split_forward.md), the dense
  *        launch otherwise.
- * The workspace (fenerf_render_workspace_bytes) holds the lists at capacity -- H * 4 + 4 bytes per coarse sample -- of which only the kept
- * samples' slots are touched.  Returns the previous mode. */
+ * The workspace (fenerf_render_workspace_bytes) holds the lists at capacity -- H * 4 + 4 bytes per coarse sample and 2 bytes per 16 of
+ * them -- of which only the kept samples' slots are touched.  The lists are in ascending sample order: the same on every run.
+ * Returns the previous mode. */
 #define FENERF_SPLIT_AUTO 0
 #define FENERF_SPLIT_OFF 1
 #define FENERF_SPLIT_FORCE 2
@@ -746,6 +747,13 @@ size_t fenerf_sparse_select_workspace_bytes(int B, int64_t P);
 int fenerf_sparse_select(int B, int R, int N, int C, int64_t cap, const float* d_coarse, const float* d_fine, const float* z_coarse,
                          const float* z_fine, const float* origins, const float* dirs, const int64_t* images, float* pts, float* rd,
                          float* d_sel, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The list step of the split coarse pass (fenerf_set_render_split) on its own, for tests: masks [dev] [B][tiles] uint16, bit n of
+ * masks[b][t] = sample 16 t + n of image b is kept.  -> idx [dev] [B][cap] uint32: the kept sample indices of image b, ascending, in
+ * entries 0 .. counts[b] - 1 (the rest is not written); counts [dev] [B] uint32.  cap >= 16 * tiles.  One launch of
+ * ceil(tiles / 256) workgroups per image, no atomics; a workgroup re-counts the image's tiles before its own (tiles^2 / 512 mask reads
+ * per image: meant for renders, up to about 2^20 tiles per image). */
+int fenerf_split_scan(int B, int64_t tiles, int64_t cap, const uint16_t* masks, uint32_t* idx, uint32_t* counts, void* stream);
 
 /* ---- iso-surface extraction: marching tetrahedra on the device (no model handle, like fenerf_composite) ----
  * replaces: skimage.measure.marching_cubes on the host copy of the density volume (extract_shapes.py, extract_double_semantic_shapes.py).
