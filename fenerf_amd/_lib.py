@@ -196,6 +196,11 @@ _SIGS = {
     "fenerf_composite_backward": (_i, [_i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(FenerfCompositeOpts), _vp, _vp, _vp, _vp]),
     "fenerf_render_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "fenerf_render_forward": (_i, [_vp, _i, _i, _i, _i, _i] + [_vp] * 10 + [C.POINTER(FenerfCompositeOpts)] + [_vp] * 4 + [_vp, _sz, _vp]),
+    # the geometry route (fenerf_siren_f16w.hip PASS = 3): labels and sigma without the colour branch, compact rows
+    "fenerf_siren_density": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "fenerf_siren_density_rays": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "fenerf_render_density_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
+    "fenerf_render_density": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 8 + [C.POINTER(FenerfCompositeOpts), _i] + [_vp] * 4 + [_vp, _sz, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 N_PHASES = 19        # include/fenerf.h FENERF_N_PHASES_ALL

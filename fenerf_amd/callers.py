@@ -97,18 +97,22 @@ def _latent_dims(generator, default=256):
 
 
 def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.25, 0.0, 0.25, 0.5), image_size=256,
-                     ray_step_multiplier=2, lock_view_dependence=False, z_dim=None, latents=None, baked=None, geometry=False):
+                     ray_step_multiplier=2, lock_view_dependence=False, z_dim=None, latents=None, baked=None, geometry=False, labels_only=False):
     """Five yaw angles of one identity (render_multiview_images_double_semantic.py:66-85).
     -> (images [V,3,S,S] in [-1,1], segmaps [V,3,S,S] in [0,1]) on the CPU.
     geometry: True, or a dict of render_geometry's options (light, ambient, background, alpha_min, space) -- every view goes through
     render_geometry (the same render) and the result gains (normals [V,3,S,S] in [-1,1], shaded [V,1,S,S]).
     latents: optional (z_geo, z_app) instead of the seeded draws (tests teacher-force the reference's CPU-generator values).
     baked: a lattice resolution -- the identity is baked once (bake_field, view direction locked) and every view is rendered from the
-    lattice by BakedField.render with the exact route's rays and draws: an approximation.  None = the exact renders."""
+    lattice by BakedField.render with the exact route's rays and draws: an approximation.  None = the exact renders.
+    labels_only: only the semantic row and the depth, through generator.staged_geometry (no colour branch where the model's density route
+    serves it) -> (segmaps [V,3,S,S] in [0,1] -- the default call's, bit for bit --, depth maps [V,S,S]); not with baked or geometry."""
+    if labels_only and (baked is not None or geometry):
+        raise ValueError("render_multiview: labels_only renders the exact semantic row; it takes neither baked nor geometry")
     kw = multiview_kwargs(curriculum, image_size, ray_step_multiplier, lock_view_dependence)
     h_mean = kw["h_mean"]
     zg_dim, za_dim = (z_dim, z_dim) if z_dim is not None else _latent_dims(generator)
-    images, segmaps, normals, shadeds = [], [], [], []
+    images, segmaps, normals, shadeds, depths = [], [], [], [], []
     geo = dict(geometry) if isinstance(geometry, dict) else {}
     field = None
     for a in face_angles:
@@ -119,6 +123,11 @@ def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.
         if latents is not None:
             z_geo, z_app = (torch.as_tensor(t, dtype=torch.float32, device=device) for t in latents)
         with torch.no_grad():
+            if labels_only:
+                seg, depth = generator.staged_geometry(z_geo, z_app, **kw)
+                segmaps.append(mask2color(seg, device, scale=255.0))
+                depths.append(depth)
+                continue
             if baked is None and not geometry:
                 img, _ = generator.staged_forward(z_geo, z_app, **kw)
             elif baked is None:
@@ -137,6 +146,8 @@ def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.
             shadeds.append(view["shaded"])
         images.append(img[:, -3:])
         segmaps.append(mask2color(img[:, :-3], device, scale=255.0))
+    if labels_only:
+        return torch.cat(segmaps), torch.cat(depths)
     if geometry:
         return torch.cat(images), torch.cat(segmaps), torch.cat(normals), torch.cat(shadeds)
     return torch.cat(images), torch.cat(segmaps)
@@ -163,13 +174,32 @@ def create_samples(N=256, voxel_origin=(0, 0, 0), cube_length=2.0, device=None):
     return samples.unsqueeze(0), voxel_origin, voxel_size
 
 
+def _lattice_sigma(nat, samples, fg, pg, fa, pa, want_labels=False):
+    """sigma [1,P] of the lattice points (view direction locked) and, with want_labels, the argmax label [1,P] uint8 (first maximum wins,
+    torch.argmax on the label logits).  The density route where the model serves it (NativeModel.supports_density: no colour branch,
+    one float per point, nothing to slice), else the full forward -- the same bits either way."""
+    if nat.supports_density():
+        if want_labels and nat.n_labels() > 0:
+            rows = nat.siren_density(samples, fg, pg, labels=True)
+            return rows[..., -1], torch.argmax(rows[..., :-1], dim=-1).to(torch.uint8)
+        sigma = nat.siren_density(samples, fg, pg, labels=False)
+        return sigma, (torch.zeros_like(sigma, dtype=torch.uint8) if want_labels else None)
+    out = nat.siren_forward(samples, None, fg, pg, fa, pa)          # None = locked view dir
+    labels = None
+    if want_labels:
+        labels = torch.argmax(out[..., :-4], dim=-1).to(torch.uint8) if out.shape[-1] > 4 else torch.zeros(out.shape[:-1], dtype=torch.uint8, device=out.device)
+    return out[..., -1], labels
+
+
 def sample_generator(generator, z_geo, z_app=None, max_batch=None, voxel_resolution=256, voxel_origin=(0, 0, 0), cube_length=2.0,
-                     psi=0.5):
+                     psi=0.5, return_labels=False):
     """Density volume [N,N,N] (numpy) of one identity for marching cubes (extract_double_semantic_shapes.py:38-62):
     truncated FiLM parameters, view direction locked to (0,0,-1).  One fused kernel launch evaluates all N^3 points;
     `max_batch` is accepted for signature compatibility and ignored.  (The reference passes the same z to both mapping
-    networks; pass z_app to differ.)"""
+    networks; pass z_app to differ.)  return_labels: -> (density volume, label volume [N,N,N] uint8: the argmax of every point's label
+    logits, first maximum wins)."""
     z_app = z_geo if z_app is None else z_app
+    N = voxel_resolution
     samples, _, _ = create_samples(voxel_resolution, voxel_origin, cube_length, device=z_geo.device)
     avg_fg, avg_pg, avg_fa, avg_pa = generator.generate_avg_frequencies()
     with torch.no_grad():
@@ -177,8 +207,11 @@ def sample_generator(generator, z_geo, z_app=None, max_batch=None, voxel_resolut
         raw_fa, raw_pa = generator.siren.app_mapping_network(z_app)
         fg, pg = avg_fg + psi * (raw_fg - avg_fg), avg_pg + psi * (raw_pg - avg_pg)
         fa, pa = avg_fa + psi * (raw_fa - avg_fa), avg_pa + psi * (raw_pa - avg_pa)
-        out = generator.siren.native(samples.device).siren_forward(samples, None, fg, pg, fa, pa)   # None = locked view dir
-    return native.to_host(out[..., -1].reshape(voxel_resolution, voxel_resolution, voxel_resolution).contiguous()).numpy()
+        sigma, labels = _lattice_sigma(generator.siren.native(samples.device), samples, fg, pg, fa, pa, want_labels=return_labels)
+    volume = native.to_host(sigma.reshape(N, N, N).contiguous()).numpy()
+    if return_labels:
+        return volume, native.to_host(labels.reshape(N, N, N).contiguous()).numpy()
+    return volume
 
 
 def film_from_inversion(meta, device=None):
@@ -191,16 +224,20 @@ def film_from_inversion(meta, device=None):
 
 
 def sample_generator_wth_frequencies_phase_shifts(generator, meta, max_batch=None, voxel_resolution=256, voxel_origin=(0, 0, 0),
-                                                  cube_length=2.0, psi=0.5):
+                                                  cube_length=2.0, psi=0.5, return_labels=False):
     """Density volume [N,N,N] of an INVERTED identity (extract_double_semantic_shapes.py:65-87, the reference's spelling of the name):
     meta carries 'truncated_frequencies_geo' / '_app' and 'truncated_phase_shifts_geo' / '_app' (the script fills them with mean +
     offset of an inversion checkpoint, :127-133 -- film_from_inversion above); view direction locked to (0, 0, -1); `max_batch` and `psi`
-    are accepted and ignored (the reference ignores psi here too)."""
+    are accepted and ignored (the reference ignores psi here too).  return_labels: as sample_generator's."""
     samples, _, _ = create_samples(voxel_resolution, voxel_origin, cube_length, device=generator.device)
     with torch.no_grad():
-        out = generator.siren.native(samples.device).siren_forward(samples, None, meta["truncated_frequencies_geo"], meta["truncated_phase_shifts_geo"],
-                                                                   meta["truncated_frequencies_app"], meta["truncated_phase_shifts_app"])
-    return native.to_host(out[..., -1].reshape(voxel_resolution, voxel_resolution, voxel_resolution).contiguous()).numpy()
+        sigma, labels = _lattice_sigma(generator.siren.native(samples.device), samples, meta["truncated_frequencies_geo"], meta["truncated_phase_shifts_geo"],
+                                       meta["truncated_frequencies_app"], meta["truncated_phase_shifts_app"], want_labels=return_labels)
+    shape = (voxel_resolution,) * 3
+    volume = native.to_host(sigma.reshape(shape).contiguous()).numpy()
+    if return_labels:
+        return volume, native.to_host(labels.reshape(shape).contiguous()).numpy()
+    return volume
 
 
 MESH_NORMAL_CHUNK = 262144       # vertices per differentiable SIREN call of extract_mesh's normals: bounds the tape
@@ -251,9 +288,7 @@ def extract_mesh(generator, z_geo, z_app=None, *, film=None, voxel_resolution=25
             fa, pa = film["truncated_frequencies_app"], film["truncated_phase_shifts_app"]
         samples, origin, voxel_size = create_samples(N, voxel_origin, cube_length, device=device)
         nat = siren.native(samples.device)
-        out = nat.siren_forward(samples, None, fg, pg, fa, pa)          # None = locked view dir
-        sigma = out[..., -1].reshape(N, N, N).contiguous()
-        del out
+        sigma = _lattice_sigma(nat, samples, fg, pg, fa, pa)[0].reshape(N, N, N).contiguous()
         components = None
         if keep != "all":
             sigma, stats = native.filter_volume(sigma, iso, keep, out=sigma)

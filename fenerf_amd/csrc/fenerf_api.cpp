@@ -1565,6 +1565,139 @@ extern "C" int fenerf_render_forward(const FenerfModel* m, int B, int R, int N, 
   return run_composite(cp, true, stream);
 }
 
+// ---- the geometry route: labels and sigma without the colour branch (fenerf_siren_f16w.hip PASS = 3)
+namespace {
+// what every density entry refuses before it looks at its shapes; FENERF_OK, or the code with the error string set
+int density_model(const FenerfModel* m) {
+  if (!m) return fail(FENERF_E_INVALID, "model is NULL");
+  if (m->precision != FENERF_PREC_F16X3)
+    return fail(FENERF_E_UNSUPPORTED, "the density route runs on the f16x3 forward kernel: FENERF_PREC_F16X3 models only (take the full forward and slice it)");
+  if (m->forward_mode == FENERF_FORWARD_F16X2)
+    return fail(FENERF_E_UNSUPPORTED, "the density route keeps three terms per product: its sigma is not that of forward mode f16x2 (take the full forward and slice it)");
+  return FENERF_OK;
+}
+int density_row(const FenerfModel* m, int with_labels) { return with_labels ? m->n_lab + 1 : 1; }
+// the launch: raw geometry FiLM parameters in, f' / p' of the geometry layers into film_ws ([B][L][H] each, the dense layout) by the launch itself
+SirenParams density_params(const FenerfModel* m, SirenParams sp, int B, const float* fg, const float* pg, void* film_ws) {
+  float* fp = (float*)film_ws;
+  sp.fp = fp; sp.pp = fp + (size_t)B * m->L * m->H;
+  sp.raw_fg = fg; sp.raw_pg = pg;
+  sp.film_bias = m->d_consts + CONST_FILM_BIAS;
+  sp.film_inv_scale = m->d_consts + CONST_FILM_BIAS + (size_t)m->L * m->H;
+  sp.n_images = B;
+  return sp;
+}
+int run_density(const FenerfModel* m, const SirenParams& sp, int row, void* stream) {
+  // timed as a SIREN forward launch and, inside that, under "siren_density" -- like the density launch of the split coarse pass
+  PhaseScope ph(PH_SIREN, stream);
+  PhaseScope pd(PH_SIREN_DENSITY, stream);
+  return launch_siren16w_plain_density(m, sp, row, stream);
+}
+struct RenderDensityWs { size_t film, coarse, fine, zf, total; };
+RenderDensityWs render_density_ws(const FenerfModel* m, int B, int R, int N, int hier, int row) {
+  RenderDensityWs w;
+  const size_t pts = (size_t)B * R * N;
+  size_t off = 0;
+  w.film = off; off += fenerf_film_workspace_bytes(m, B);
+  w.coarse = off; off += align_up(pts * row * sizeof(float), 256);
+  w.fine = off; off += hier ? align_up(pts * row * sizeof(float), 256) : 0;
+  w.zf = off; off += hier ? align_up(pts * sizeof(float), 256) : 0;
+  w.total = off;
+  return w;
+}
+}  // namespace
+
+extern "C" int fenerf_siren_density(const FenerfModel* m, int B, int64_t P, const float* points, const float* freq_geo, const float* phase_geo,
+                                    int with_labels, float* out, void* film_ws, void* stream) {
+  if (int rc = density_model(m)) return rc;
+  if (B <= 0 || P < 0) return fail(FENERF_E_INVALID, "B must be > 0 and P >= 0");
+  if (P == 0) return FENERF_OK;
+  if (!points || !out) return fail(FENERF_E_INVALID, "points / out is NULL");
+  if (!freq_geo || !phase_geo) return fail(FENERF_E_INVALID, "freq_geo / phase_geo is NULL");
+  if (!film_ws) return fail(FENERF_E_INVALID, "film workspace is NULL");
+  const SirenParams sp = density_params(m, point_params(m, nullptr, nullptr, B, P, points, nullptr, out), B, freq_geo, phase_geo, film_ws);
+  return run_density(m, sp, density_row(m, with_labels), stream);
+}
+
+extern "C" int fenerf_siren_density_rays(const FenerfModel* m, int B, int R, int N, const float* origins, const float* dirs, const float* z,
+                                         const float* freq_geo, const float* phase_geo, int with_labels, float* out, void* film_ws, void* stream) {
+  if (int rc = density_model(m)) return rc;
+  if (B <= 0 || R < 0 || N <= 0) return fail(FENERF_E_INVALID, "B, N must be > 0 and R >= 0");
+  if (R == 0) return FENERF_OK;
+  if (!origins || !dirs || !z || !out) return fail(FENERF_E_INVALID, "origins / dirs / z / out is NULL");
+  if (!freq_geo || !phase_geo) return fail(FENERF_E_INVALID, "freq_geo / phase_geo is NULL");
+  if (!film_ws) return fail(FENERF_E_INVALID, "film workspace is NULL");
+  const SirenParams sp = density_params(m, ray_params(m, nullptr, nullptr, B, R, N, origins, dirs, z, 0, out), B, freq_geo, phase_geo, film_ws);
+  return run_density(m, sp, density_row(m, with_labels), stream);
+}
+
+extern "C" size_t fenerf_render_density_workspace_bytes(const FenerfModel* m, int B, int R, int N, int hierarchical, int with_labels) {
+  if (!m || B <= 0 || R <= 0 || N <= 0) return 0;
+  return render_density_ws(m, B, R, N, hierarchical, density_row(m, with_labels)).total;
+}
+
+extern "C" int fenerf_render_density(const FenerfModel* m, int B, int R, int N, int hierarchical, const float* origins, const float* dirs,
+                                     const float* z_coarse, const float* u, const float* noise_coarse, const float* noise_final,
+                                     const float* freq_geo, const float* phase_geo, const FenerfCompositeOpts* opts, int with_labels,
+                                     float* out_labels, float* out_depth, float* out_weights, float* out_wsum, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  if (int rc = density_model(m)) return rc;
+  int rc = check_opts(opts);
+  if (rc) return rc;
+  if (B < 0 || R < 0 || N <= 0) return fail(FENERF_E_INVALID, "B, R must be >= 0 and N > 0");
+  const int M = hierarchical ? 2 * N : N;
+  if (M > FENERF_MAX_RAY_SAMPLES) return fail(FENERF_E_INVALID, "at most 1024 samples per ray (512 + 512 hierarchical; FENERF_MAX_RAY_SAMPLES)");
+  if (hierarchical && N < 3) return fail(FENERF_E_INVALID, "hierarchical sampling needs num_steps >= 3");
+  if (opts->fill_mode == FENERF_FILL_EVAL_WHITE_BACK && m->C != 4) return fail(FENERF_E_INVALID, "eval_white_back needs a 3-channel model");
+  if ((long long)B * R == 0) return FENERF_OK;
+  const int row = density_row(m, with_labels);
+  if (!origins || !dirs || !z_coarse) return fail(FENERF_E_INVALID, "origins / dirs / z_coarse is NULL");
+  if (row > 1 && !out_labels) return fail(FENERF_E_INVALID, "out_labels is NULL (with_labels on a model with label channels)");
+  if (!out_labels && !out_depth && !out_weights && !out_wsum) return fail(FENERF_E_INVALID, "every output is NULL");
+  if (hierarchical && !u) return fail(FENERF_E_INVALID, "hierarchical sampling needs u");
+  const RenderDensityWs ws = render_density_ws(m, B, R, N, hierarchical, row);
+  if (!workspace || workspace_bytes < ws.total) return fail(FENERF_E_INVALID, "workspace too small (see fenerf_render_density_workspace_bytes)");
+  if (!freq_geo || !phase_geo) return fail(FENERF_E_INVALID, "film parameter pointer is NULL");
+  char* base = (char*)workspace;
+  float* coarse = (float*)(base + ws.coarse);
+  float* labels = row > 1 ? out_labels : nullptr;      // rows of sigma alone have no channel to composite
+  const long long BR = (long long)B * R;
+  // fenerf_render_forward's launch sequence (its four-launch route) on rows of `row` floats: the same launchers, C = row
+  SirenParams sp = density_params(m, ray_params(m, nullptr, nullptr, B, R, N, origins, dirs, z_coarse, 0, coarse), B, freq_geo, phase_geo, base + ws.film);
+  CompositeParams cp;
+  if (!hierarchical) {
+    rc = run_density(m, sp, row, stream);                   // the only pass     (generators.py:479)
+    if (rc) return rc;
+    memset(&cp, 0, sizeof(cp));
+    cp.BR = BR; cp.M = N; cp.C = row; cp.N = N;
+    cp.rows_a = coarse; cp.z_a = z_coarse; cp.noise = noise_final; cp.o = *opts;
+    cp.out_rgb = labels; cp.out_depth = out_depth; cp.out_weights = out_weights; cp.out_wsum = out_wsum;
+    cp.out_ch = out_channels(row, opts);
+    return run_composite(cp, false, stream);                // (generators.py:519)
+  }
+  float* fine = (float*)(base + ws.fine);
+  float* zf = (float*)(base + ws.zf);
+  rc = run_density(m, sp, row, stream);                     // coarse pass   (generators.py:479)
+  if (rc) return rc;
+  memset(&cp, 0, sizeof(cp));                               // coarse weights + inverse-CDF resampling (generators.py:487-499)
+  cp.BR = BR; cp.M = N; cp.C = row; cp.N = N;
+  cp.rows_a = coarse; cp.z_a = z_coarse; cp.noise = noise_coarse;
+  cp.o.clamp_mode = opts->clamp_mode; cp.o.noise_std = opts->noise_std;
+  cp.sigma_only = 1; cp.out_ch = row - 1;
+  cp.u = u; cp.z_fine = zf;
+  rc = run_composite(cp, false, stream);
+  if (rc) return rc;
+  sp.z = zf; sp.out = fine;                                 // (the geometry FiLM blocks are prepared again: a few thousand values per workgroup)
+  rc = run_density(m, sp, row, stream);                     // fine pass     (generators.py:505)
+  if (rc) return rc;
+  memset(&cp, 0, sizeof(cp));                               // merge + final composite (generators.py:508-519)
+  cp.BR = BR; cp.M = 2 * N; cp.C = row; cp.N = N;
+  cp.rows_a = fine; cp.rows_b = coarse; cp.z_a = zf; cp.z_b = z_coarse; cp.noise = noise_final; cp.o = *opts;
+  cp.out_rgb = labels; cp.out_depth = out_depth; cp.out_weights = out_weights; cp.out_wsum = out_wsum;
+  cp.out_ch = out_channels(row, opts);
+  return run_composite(cp, true, stream);
+}
+
 // =====================================================================================================================================
 // The differentiable hierarchical render as TWO calls (round 5; SURVEY.md 8b "fenerf_render_backward"): what rounds 1-4 orchestrated in
 // Python (fenerf_amd/generators/autograd.py::_hierarchical_forward / HierarchicalRenderFunction.backward, siren/autograd.py::

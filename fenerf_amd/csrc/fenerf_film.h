@@ -34,4 +34,28 @@ __device__ __forceinline__ void film_prep_prologue(const SirenParams& P, long lo
   __syncthreads();
 }
 
+// The geometry layers alone (the plain density pass, fenerf_siren_f16w.hip PASS = 3): the same values at the same places of the [B][L][H]
+// blocks; the appearance layers' slots are left as they are and raw_fa / raw_pa are never read (they may be nullptr).
+__device__ __forceinline__ void film_prep_prologue_geo(const SirenParams& P, long long img0, long long img1, int H, int n_geo, int n_color) {
+  const int L = n_geo + n_color;
+  float* fp = const_cast<float*>(P.fp);
+  float* pp = const_cast<float*>(P.pp);
+  if (img1 >= P.n_images) img1 = P.n_images - 1;
+  const long long total = (img1 - img0 + 1) * (long long)n_geo * H;
+  for (long long k = threadIdx.x; k < total; k += blockDim.x) {
+    const int n = (int)(k % H);
+    const int l = (int)((k / H) % n_geo);
+    const long long b = img0 + k / ((long long)H * n_geo);
+    const float fr = P.raw_fg[(b * n_geo + l) * H + n], ph = P.raw_pg[(b * n_geo + l) * H + n];
+    const float f = __fadd_rn(__fmul_rn(fr, 15.f), 30.f);
+    const double inv2pi = 0.15915494309189533576888;
+    const double sc = P.film_inv_scale ? (double)P.film_inv_scale[l * H + n] : 1.0;
+    const long long i = (b * L + l) * H + n;
+    fp[i] = (float)((double)f * inv2pi * sc);
+    pp[i] = (float)(((double)f * (double)P.film_bias[l * H + n] + (double)ph) * inv2pi);
+  }
+  __threadfence();
+  __syncthreads();
+}
+
 }  // namespace fenerf

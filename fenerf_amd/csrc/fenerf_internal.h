@@ -222,6 +222,10 @@ struct SplitArgs {
 inline long long split_tiles_per_image(long long pts_per_image) { return (pts_per_image + 15) / 16; }
 int launch_siren16w_density(const FenerfModel* m, const SirenParams& p, const SplitArgs& s, void* stream);
 int launch_siren16w_colour(const FenerfModel* m, const SirenParams& p, const SplitArgs& s, void* stream);    // p.out: the density pass's rows
+// The plain density pass (fenerf_siren_f16w.hip PASS = 3, instantiated in fenerf_siren_f16w_density.hip): labels and sigma of every point
+// without the colour branch, p.out = [P][row] with row = n_lab + 1 ([labels | sigma]) or 1 (sigma alone).  p.raw_fg / p.raw_pg must be set
+// (the launch prepares the geometry FiLM blocks itself); p.pdirs / p.raw_fa / p.raw_pa are never read.
+int launch_siren16w_plain_density(const FenerfModel* m, const SirenParams& p, int row, void* stream);
 // fenerf_repack.hip: idx / counts of B images from their tile masks (one launch, a workgroup per 256 tiles of an image)
 int launch_split_scan(const unsigned short* masks, int B, long long tiles_per_image, long long cap, unsigned* idx, unsigned* counts, void* stream);
 // fenerf_repack.hip: m->d_colour_nonfinite[0] <- "the packed stream or the consts hold a non-finite value", [1] <- "the relaid grid does" (grid_too)

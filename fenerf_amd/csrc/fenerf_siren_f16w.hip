@@ -299,6 +299,9 @@ template <> struct FuseArgs<true, 0> {
 //             the masks behind the launch (launch_split_scan) makes each image's list of kept sample indices, ascending, and its count.
 //   PASS = 2, colour pass: a persistent launch over octs of 8 x 16 list entries of one image, sized on the device from counts[]: reloads xh / xl,
 //             recomputes the point, gathers the grid, runs colour layer 0, the colour layers and the rgb head and scatters three floats.
+//   PASS = 3, plain density pass (round 18, fenerf_siren_density / fenerf_render_density): the density pass's walk and arithmetic as a query of
+//             its own -- no masks, no parked trunk output, no appearance-FiLM check, no view direction --, and a compact row per point: C is
+//             the row's stride, n_lab + 1 = [labels | sigma], or 1 = sigma alone.  Its instantiations live in fenerf_siren_f16w_density.hip.
 // Both walk the stream with jumps of g_next over the stages they do not run (every stage is whole ring revolutions: the slot indices stay);
 // a kept sample's column sees the dense kernel's MFMA sequence on the dense kernel's operands, so its outputs are the dense kernel's bits.
 template <> struct FuseArgs<false, 1> : SplitArgs {};
@@ -308,9 +311,11 @@ constexpr int FUSED_MAXM = FENERF_EXP_FUSED_MAXM;   // samples per ray (2 N) the
 template <int H, bool GRID, int SAVE, bool FUSED = false, int TERMS2 = 0, int PASS = 0>
 __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_geo, int n_color, int n_lab, int C, FuseArgs<FUSED, PASS> F) {
   static_assert(!(FUSED && SAVE != 0), "the fused render is the no-grad path");
+  static_assert(PASS >= 0 && PASS <= 3, "PASS: 0 dense, 1 density + kept masks, 2 colour, 3 plain density");
   static_assert(PASS == 0 || (SAVE == 0 && !FUSED && TERMS2 == 0), "the split passes are plain no-grad evaluations at full f16x3");
   static_assert(TERMS2 == 0 || (SAVE == 0 && !FUSED), "the reduced-precision forwards are plain no-grad evaluations");
   constexpr bool LOR = TERMS2 != 1;      // weight lo halves are fetched and read from the ring at all
+  constexpr bool DENS = PASS == 1 || PASS == 3;   // the density walk: layer 0, the trunk, the label / sigma head; the colour stages are jumped over
   constexpr bool LOC = TERMS2 == 0;      // ... and multiplied in the colour layers and the rgb head (geometry trunk, label / sigma head: whenever they are read)
   constexpr int NB = H / 32, KS = H / 32;                       // 32-row n-blocks; k32-steps of an H-wide input
   constexpr int QB = (KS + 1) / 2;                              // chunks per square n-block body
@@ -383,7 +388,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
   // split passes: the first streamed stage of a tile (density: FiLM layer 1, or the head of a one-layer trunk; colour: colour layer 0)
   constexpr unsigned long long CB = CH * 1024;
   const unsigned long long g_c0 = g_stream + (unsigned long long)(n_geo - 1) * SQ_CHUNKS * CB;
-  const unsigned long long g_first = PASS == 2 ? g_c0 : (PASS == 1 && n_geo == 1) ? g_c0 + C0_CHUNKS * CB : g_stream;
+  const unsigned long long g_first = PASS == 2 ? g_c0 : (DENS && n_geo == 1) ? g_c0 + C0_CHUNKS * CB : g_stream;
   ws.g_next = PASS ? g_first : g_stream;
   ws.ring_lds = __builtin_amdgcn_readfirstlane(lds_addr(ring) + wave * 1024);
   ws.ring_lane = ring + lane * 16;
@@ -408,7 +413,8 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     const long long p_first = (o_begin + bi) * opg * (NWAVE * 16);
     long long p_last = o_end * opg * (NWAVE * 16) - 1;
     if (p_last >= P.P) p_last = P.P - 1;
-    film_prep_prologue(P, p_first / P.pts_per_image, p_last / P.pts_per_image, H, n_geo, n_color);
+    if constexpr (PASS == 3) film_prep_prologue_geo(P, p_first / P.pts_per_image, p_last / P.pts_per_image, H, n_geo, n_color);
+    else film_prep_prologue(P, p_first / P.pts_per_image, p_last / P.pts_per_image, H, n_geo, n_color);
   }
 
   // ---- prime the shared stream: chunks 0..D-1 in flight, first k32-step of chunk 0 in registers
@@ -516,7 +522,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     float e[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) e[i] = 0.f;
-    if (GRID && PASS != 1) {
+    if (GRID && !DENS) {
       const int ch0 = 16 * (g & 1) + 8 * (g >> 1);
       // the corner walk of fenerf_grid.h (the definition this must match), in place: any inlined form moves this kernel's prologue
       const float ix = ((qx + 1.f) / 2.f) * (float)(P.gw - 1);
@@ -552,7 +558,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
     // density pass: what of the view direction the kept rule needs
     const bool dir_bad = PASS == 1 && !(__builtin_fabsf(dx) < __builtin_inff() && __builtin_fabsf(dy) < __builtin_inff() &&
                                         __builtin_fabsf(dz) < __builtin_inff());
-    if constexpr (PASS != 1) {
+    if constexpr (!DENS) {
       half8 eh, el, dh, dl;
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
@@ -610,10 +616,10 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       const float* ff = film_lane(l);
       const TapeW<SAVE> tw = tape_of(l);
       half8 yh[KS], yl[KS];
-      if (l + 1 < (PASS == 1 ? n_geo : L)) film_issue(l + 1);
+      if (l + 1 < (DENS ? n_geo : L)) film_issue(l + 1);
       if (SQ_CHUNKS < DPF + 2) wait_vmcnt<0>();
       if (l == n_geo) {
-        if constexpr (PASS != 1) {
+        if constexpr (!DENS) {
         // ---------------- colour layer 0: [x | grid feats | dir] -> H, then the label/sigma head on the same x -------
         const float4* ext = ext_wave + opaque(lane);
         auto bop0 = [&](int sp, half8& bh, half8& bl) -> bool {
@@ -697,7 +703,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
           f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
           for (int qc = 0; qc < QB; ++qc) {
-            if constexpr (PASS == 1) { if (nb * QB + qc == SQ_CHUNKS - DPF && l == n_geo - 1) ws.g_next += C0_CHUNKS * CB; }   // over colour layer 0
+            if constexpr (DENS) { if (nb * QB + qc == SQ_CHUNKS - DPF && l == n_geo - 1) ws.g_next += C0_CHUNKS * CB; }   // over colour layer 0
             chunk_step<LOR, LOM, PH>(acc, a_cur, ws, nb * QB + qc, 2 * qc, bop, [&](FilmQ2& fq) {
               if (nb > 0) {
                 int p0, p1;
@@ -720,7 +726,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
         }
 #pragma unroll
         for (int i = NB * QB; i < SQ_CHUNKS; ++i) {
-          if constexpr (PASS == 1) { if (i == SQ_CHUNKS - DPF && l == n_geo - 1) ws.g_next += C0_CHUNKS * CB; }
+          if constexpr (DENS) { if (i == SQ_CHUNKS - DPF && l == n_geo - 1) ws.g_next += C0_CHUNKS * CB; }
           chunk_skip<LOR, PH>(a_cur, ws, i);
         }
         epi_all<KS, FILM_F / 4, SAVE>(acc_prev, NB - 1, ff, yh, yl, tw, tile_odd);
@@ -737,7 +743,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
       for (int k = 0; k < KS; ++k) { xh[k] = yh[k]; xl[k] = yl[k]; }
     };
 #pragma unroll 1
-    for (int l = PASS == 2 ? n_geo : 1; l < (PASS == 1 ? n_geo : L); ++l) {
+    for (int l = PASS == 2 ? n_geo : 1; l < (DENS ? n_geo : L); ++l) {
       // One compile-time copy of the layer per wave half (round 6): the DMA position of a wave (top of a chunk step / half a step later)
       // was a run-time flag tested in every k32-step -- two scalar branches per k32-step, one of them taken.  With the branch between
       // layers instead: 2,599,000 -> 2,444,000 shader cycles per launch (- 6.0 %), of which the power manager keeps two thirds
@@ -749,7 +755,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
 #endif
     }
     // ---------------- rgb head + sigmoid (rows 0..2 = row tile 0, lane group 0) ----------------
-    if constexpr (PASS == 1) {
+    if constexpr (DENS) {
       // the density tile ends with the head, straight behind the trunk (x stays what it is: the list takes it).  The stage is the dense
       // kernel's, statement for statement, as a copy of its own: sharing one lambda with the dense kernel moves the dense kernel's code
       auto head_stage = [&](auto ph_c) {
@@ -762,12 +768,12 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
 #pragma unroll
         // (the label / sigma head keeps every term the kernel reads: with TERMS2 = 2 sigma and the labels are those of the default, bit for bit)
         for (int qc = 0; qc < QB; ++qc) {
-          if constexpr (PASS == 1) { if (qc == HEAD_CHUNKS - DPF) ws.g_next = g_first; }      // the density tile ends here: the next tile's first chunks
+          if constexpr (DENS) { if (qc == HEAD_CHUNKS - DPF) ws.g_next = g_first; }      // the density tile ends here: the next tile's first chunks
           chunk_step<LOR, true, PH>(acc, a_cur, ws, qc, 2 * qc, bop, [](FilmQ2&) {}, [](const FilmQ2&) {});
         }
 #pragma unroll
         for (int i = QB; i < HEAD_CHUNKS; ++i) {
-          if constexpr (PASS == 1) { if (i == HEAD_CHUNKS - DPF) ws.g_next = g_first; }
+          if constexpr (DENS) { if (i == HEAD_CHUNKS - DPF) ws.g_next = g_first; }
           chunk_skip<LOR, PH>(a_cur, ws, i);
         }
         const int lane_o = opaque(lane);
@@ -777,7 +783,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int row = f_o + 8 * rt + r;
-            if (row <= n_lab) {
+            if (row <= n_lab && (PASS != 3 || row == n_lab || C > 1)) {      // plain pass: C = n_lab + 1, or 1 = sigma alone
               const int ch = row < n_lab ? row : C - 1;
               stage[n_o * C + ch] = acc[rt][r] * cst[row] + cst[32 + row];
             }
@@ -789,10 +795,12 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
 #else
       head_stage(std::integral_constant<int, -1>{});
 #endif
+      if constexpr (PASS == 1) {
       const int lane_o = opaque(lane);
       if ((lane_o >> 4) == 0) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) stage[(lane_o & 15) * C + (C - 4) + r] = 0.f;
+      }
       }
     } else {
       constexpr int PH = -1;
@@ -918,6 +926,7 @@ __global__ __launch_bounds__(512, 2) void siren16w_kernel(SirenParams P, int n_g
   }
 }
 
+#ifndef FENERF_F16W_DENSITY_TU
 static size_t lds_bytes_16w(const FenerfModel* m, int H) {
   const int stage_f4 = (16 * m->C + 3) / 4;
   const size_t film_f = H * 4 < 1024 ? 1024 : H * 4;
@@ -958,7 +967,54 @@ static int launch_split_t(const FenerfModel* m, const SirenParams& p, const Spli
   return check_launch(PASS == 1 ? "siren16w density launch" : "siren16w colour launch");
 }
 
+#endif  // !FENERF_F16W_DENSITY_TU
 }  // namespace w16
+
+#ifdef FENERF_F16W_DENSITY_TU
+// ---- the plain density pass (PASS = 3): this translation unit's only launcher (fenerf_siren_f16w_density.hip)
+namespace w16 {
+template <int H, bool GRID>
+static int launch_plain_t(const FenerfModel* m, const SirenParams& p, int row, void* stream) {
+  // the dense kernel's LDS plan with the output stage of a compact row (row <= m->C: the layout is the kernel's own, from its C argument)
+  const int stage_f4 = (16 * row + 3) / 4;
+  const size_t film_f = H * 4 < 1024 ? 1024 : H * 4;
+  const size_t lds = (size_t)NSLOT * CH * 1024 + (size_t)NWAVE * 2 * (2 * film_f) + (size_t)(H / 32) * 1024 + 80 * 4 + (size_t)NWAVE * stage_f4 * 16 +
+                     (size_t)NWAVE * 4096;
+  auto kfn = siren16w_kernel<H, GRID, 0, false, 0, 3>;
+  if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
+  const unsigned blocks = persistent_blocks((p.P + 15) / 16, NWAVE, m->num_cus);
+  hipLaunchKernelGGL(kfn, dim3(blocks), dim3(512), lds, (hipStream_t)stream, p, m->n_geo, m->n_color, m->n_lab, row, FuseArgs<false, 3>{});
+  return check_launch("siren16w plain density launch");
+}
+}  // namespace w16
+
+// Labels and sigma (row = n_lab + 1) or sigma alone (row = 1) of every point, p.out = [P][row]; p.raw_fg / p.raw_pg are required (the
+// geometry FiLM blocks are prepared by the launch itself), p.pdirs / p.raw_fa / p.raw_pa are never read.  Tiles must not straddle images:
+// images whose point count is no multiple of 32 get a launch each, like launch_siren16w.
+int launch_siren16w_plain_density(const FenerfModel* m, const SirenParams& p, int row, void* stream) {
+  if (p.P <= 0) return FENERF_OK;
+  auto one = [&](const SirenParams& q) {
+    return dispatch_width(m->H, m->grid_ch != 0, [&](auto h, auto g) { return w16::launch_plain_t<decltype(h)::value, decltype(g)::value>(m, q, row, stream); });
+  };
+  if (p.pts_per_image % 32 == 0 || p.P == p.pts_per_image) return one(p);
+  const long long nimg = p.P / p.pts_per_image;
+  for (long long b = 0; b < nimg; ++b) {
+    SirenParams q = p;
+    q.P = p.pts_per_image;
+    q.fp = p.fp + (size_t)b * m->L * m->H; q.pp = p.pp + (size_t)b * m->L * m->H;
+    q.raw_fg = p.raw_fg + (size_t)b * m->n_geo * m->H; q.raw_pg = p.raw_pg + (size_t)b * m->n_geo * m->H;
+    q.n_images = 1;
+    q.out = p.out + (size_t)b * p.pts_per_image * row;            // the compact stride, not C
+    if (p.points) q.points = p.points + (size_t)b * p.pts_per_image * 3;
+    else {
+      const long long rays = p.pts_per_image / p.n_per_ray;
+      q.origins = p.origins + (size_t)b * rays * 3; q.dirs = p.dirs + (size_t)b * rays * 3; q.z = p.z + (size_t)b * p.pts_per_image;
+    }
+    if (int rc = one(q)) return rc;
+  }
+  return FENERF_OK;
+}
+#else
 
 // One launch over points whose tiles do not straddle images.
 static int launch_siren16w_one(const FenerfModel* m, const SirenParams& q, void* stream) {
@@ -1073,5 +1129,7 @@ int launch_siren16w_colour(const FenerfModel* m, const SirenParams& p, const Spl
     return w16::launch_split_t<decltype(h)::value, decltype(g)::value, 2>(m, p, s, persistent_blocks(max_units, 1, m->num_cus), stream);
   });
 }
+
+#endif  // FENERF_F16W_DENSITY_TU
 
 }  // namespace fenerf

@@ -138,6 +138,39 @@ class _Generator3dBase(nn.Module):
             rays_out.update(origins=origins, dirs=dirs, wsum=wsum)
         return rgb, depth, t, pitch, yaw
 
+    def _geometry_field(self):
+        """What stands in for NativeModel.render in a geometry render (_render's field_render): the density route where the model
+        serves it (NativeModel.render_density: no colour branch), else the full render with its rgb channels cut off.  Either way the
+        first tensor holds the label channels of the full render's pixels (with the background channel of the padding fill modes)."""
+        nat = self.siren.native(self.device)
+
+        def field(origins, dirs, z, u, noise_c, noise_f, fg, pg, fa, pa, opts, hierarchical=True, lock_view=False, want_weights=False,
+                  want_wsum=False):
+            pad = opts.fill_mode in (_lib.FILL["seg_padding_background"], _lib.FILL["eval_seg_padding_background"])
+            if nat.supports_density() and (nat.n_labels() > 0 or not pad):
+                labels, depth, weights, wsum = nat.render_density(origins, dirs, z, u, noise_c, noise_f, fg, pg, opts, hierarchical=hierarchical,
+                                                                  labels=True, want_weights=want_weights, want_wsum=want_wsum)
+                if labels is None:        # a model without label channels: a depth render
+                    labels = depth.new_zeros(depth.shape + (0,))
+                return labels, depth, weights, wsum
+            rgb, depth, weights, wsum = nat.render(origins, dirs, z, u, noise_c, noise_f, fg, pg, fa, pa, opts, hierarchical=hierarchical,
+                                                   lock_view=lock_view, want_weights=want_weights, want_wsum=want_wsum)
+            return rgb[..., :rgb.shape[-1] - 3].contiguous(), depth, weights, wsum
+        return field
+
+    def _staged_geometry(self, film, batch_size, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
+                         hierarchical_sample, sample_dist, lock_view_dependence, kwargs):
+        """the render of a staged_forward (same rays, same draws, same options) through _geometry_field -> (label channels of its image
+        [B,n,S,S] on the CPU, depth map [B,S,S] on the CPU), bit for bit"""
+        labels, depth, _, pitch, yaw = self._render(film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
+                                                    hierarchical_sample, sample_dist, lock_view_dependence, kwargs, use_fill=True, third=None,
+                                                    field_render=self._geometry_field())
+        depth_map = native.to_host(depth.reshape(batch_size, img_size, img_size).contiguous())
+        # the image's own finishing statements (softmax over the label channels, layout, * 2 - 1) on pixels whose rgb channels are zeros,
+        # cut off again: every label value takes the path it takes in staged_forward
+        pixels = self._finish_scaled(torch.cat([labels, labels.new_zeros(labels.shape[:-1] + (3,))], dim=-1), batch_size, img_size)
+        return native.to_host(pixels[:, :-3].contiguous()), depth_map
+
     def _wants_grad(self, film, *pose):
         """pose: the call's h_mean / v_mean -- a tensor among them that requires grad (a camera pose under optimisation) makes the render
         differentiable too"""
@@ -420,6 +453,42 @@ class DoubleImplicitGenerator3d(_Generator3dBase):
             pixels = native.to_host(self._finish_scaled(pixels, batch_size, img_size))
         return pixels, depth_map
 
+    def staged_geometry(self, z_geo, z_app, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
+                        psi=1, lock_view_dependence=False, max_batch_size=50000, depth_map=False, near_clip=0, far_clip=2,
+                        sample_dist=None, hierarchical_sample=False, **kwargs):
+        """staged_forward's semantic channels and depth map without its colour branch -> (labels.cpu() [B,n,S,S], depth_map.cpu()):
+        from the same generator state exactly the bits staged_forward's image holds in its channels [:-3] (softmax_label and the
+        background channel of the padding fill modes included) and its depth map.  The generator is consumed as staged_forward consumes
+        it (average frequencies, camera, jitter, u, noise).  z_app is accepted and not needed (None is fine)."""
+        batch_size = z_geo.shape[0]
+        self.generate_avg_frequencies()
+        with torch.no_grad():
+            raw_fg, raw_pg = self.siren.geo_mapping_network(z_geo)
+            fg = self.avg_frequencies_geo + psi * (raw_fg - self.avg_frequencies_geo)
+            pg = self.avg_phase_shifts_geo + psi * (raw_pg - self.avg_phase_shifts_geo)
+            # colour parameters for a model the density route does not serve (its labels and depth do not read them): the average ones
+            fa = self.avg_frequencies_app.expand(batch_size, -1).contiguous()
+            pa = self.avg_phase_shifts_app.expand(batch_size, -1).contiguous()
+            return self._staged_geometry((fg, pg, fa, pa), batch_size, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
+                                         h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence, kwargs)
+
+    def staged_geometry_with_frequencies(self, truncated_frequencies_geo, truncated_frequencies_app, truncated_phase_shifts_geo,
+                                         truncated_phase_shifts_app, img_size, fov, ray_start, ray_end, num_steps, h_stddev,
+                                         v_stddev, h_mean, v_mean, psi=0.7, lock_view_dependence=False, max_batch_size=50000,
+                                         depth_map=False, near_clip=0, far_clip=2, sample_dist=None, hierarchical_sample=False,
+                                         **kwargs):
+        """staged_forward_with_frequencies' semantic channels and depth map -> (labels.cpu(), depth_map.cpu()); the appearance
+        parameters are accepted and not needed (None is fine where the density route serves the model)."""
+        batch_size = truncated_frequencies_geo.shape[0]
+        with torch.no_grad():
+            fa, pa = truncated_frequencies_app, truncated_phase_shifts_app
+            if fa is None or pa is None:
+                n_app = len(self.siren.color_layer_sine) * self.siren.hidden_dim
+                fa = pa = truncated_frequencies_geo.new_zeros((batch_size, n_app))
+            return self._staged_geometry((truncated_frequencies_geo, truncated_phase_shifts_geo, fa, pa), batch_size, img_size, fov,
+                                         ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean, hierarchical_sample,
+                                         sample_dist, lock_view_dependence, kwargs)
+
     def staged_forward_with_frequencies(self, truncated_frequencies_geo, truncated_frequencies_app, truncated_phase_shifts_geo,
                                         truncated_phase_shifts_app, img_size, fov, ray_start, ray_end, num_steps, h_stddev,
                                         v_stddev, h_mean, v_mean, psi=0.7, lock_view_dependence=False, max_batch_size=50000,
@@ -537,6 +606,28 @@ class ImplicitGenerator3d(_Generator3dBase):
             pixels = self._finish_scaled(pixels, batch_size, img_size)   # stays on the device (generators.py:231)
         return pixels, depth_map, weights_sum
 
+    def staged_geometry(self, z, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean, psi=1,
+                        lock_view_dependence=False, max_batch_size=50000, depth_map=False, near_clip=0, far_clip=2,
+                        sample_dist=None, hierarchical_sample=False, **kwargs):
+        """staged_forward's depth map without its colour branch -> (labels.cpu() [B,0,S,S]: this class has no label channels,
+        depth_map.cpu()), from the same generator state the bits of staged_forward's depth map."""
+        batch_size = z.shape[0]
+        with torch.no_grad():
+            f, p = self._staged_film(z, psi)
+            return self._staged_geometry(self._film(f, p), batch_size, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev,
+                                         h_mean, v_mean, hierarchical_sample, sample_dist, lock_view_dependence, kwargs)
+
+    def staged_geometry_with_frequencies(self, truncated_frequencies, truncated_phase_shifts, img_size, fov, ray_start, ray_end,
+                                         num_steps, h_stddev, v_stddev, h_mean, v_mean, psi=0.7, lock_view_dependence=False,
+                                         max_batch_size=50000, depth_map=False, near_clip=0, far_clip=2, sample_dist=None,
+                                         hierarchical_sample=False, **kwargs):
+        """staged_forward_with_frequencies' depth map -> (labels.cpu() [B,0,S,S], depth_map.cpu())"""
+        batch_size = truncated_frequencies.shape[0]
+        with torch.no_grad():
+            return self._staged_geometry(self._film(truncated_frequencies, truncated_phase_shifts), batch_size, img_size, fov, ray_start,
+                                         ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean, hierarchical_sample, sample_dist,
+                                         lock_view_dependence, kwargs)
+
     def staged_forward_with_frequencies(self, truncated_frequencies, truncated_phase_shifts, img_size, fov, ray_start, ray_end,
                                         num_steps, h_stddev, v_stddev, h_mean, v_mean, psi=0.7, lock_view_dependence=False,
                                         max_batch_size=50000, depth_map=False, near_clip=0, far_clip=2, sample_dist=None,
@@ -594,3 +685,11 @@ class StyleGenerator3d(ImplicitGenerator3d):
     def staged_forward_with_frequencies(self, truncated_frequencies, truncated_phase_shifts, *args, **kwargs):
         kwargs.pop("fill_color", None)
         return super().staged_forward_with_frequencies(truncated_frequencies, truncated_phase_shifts, *args, **kwargs)
+
+    def staged_geometry(self, z, *args, **kwargs):
+        kwargs.pop("fill_color", None)
+        return super().staged_geometry(z, *args, **kwargs)
+
+    def staged_geometry_with_frequencies(self, truncated_frequencies, truncated_phase_shifts, *args, **kwargs):
+        kwargs.pop("fill_color", None)
+        return super().staged_geometry_with_frequencies(truncated_frequencies, truncated_phase_shifts, *args, **kwargs)

@@ -1027,6 +1027,86 @@ class NativeModel:
                                                _stream()))
         return rgb, depth, weights, wsum
 
+    # ---- the geometry route: labels and sigma without the colour branch (include/fenerf.h "The geometry route")
+    def supports_density(self):
+        """True when siren_density / siren_density_rays / render_density serve this model: an f16x3 model whose forward mode keeps
+        three terms per product through the trunk (the default and 'f16x3c2').  Otherwise take the full forward and slice it."""
+        return self.precision == "f16x3" and self.forward_mode != self.FORWARD_MODES["f16x2"]
+
+    def n_labels(self):
+        """label channels in front of rgb and sigma in a full row"""
+        return self.C - 4
+
+    def _film_geo(self, B, fg, pg):
+        H, ng = self.spec["hidden_dim"], self.spec["n_geo"]
+        fg, pg = _f32(fg, self.device), _f32(pg, self.device)
+        if self.padded:
+            fg, pg = self._pad_film(fg, ng), self._pad_film(pg, ng)
+        for t in (fg, pg):
+            if tuple(t.shape) != (B, ng * H):
+                raise ValueError(f"film parameter of shape {tuple(t.shape)}, expected {(B, ng * self.logical_H)}")
+        return fg, pg
+
+    def _density_shape(self, lead, labels):
+        return tuple(lead) + (self.n_labels() + 1,) if labels and self.n_labels() > 0 else tuple(lead)
+
+    def siren_density(self, points, fg, pg, labels=True, out=None):
+        """[B,P,3] points -> [B,P,n_lab+1] = [labels | sigma] (labels=True on a model with label channels), else [B,P] = sigma: the
+        bits of siren_forward's label and sigma channels, without its colour branch and without a view direction."""
+        B, P = points.shape[0], points.shape[1]
+        fg, pg = self._film_geo(B, fg, pg)
+        points = _f32(points, self.device)
+        shape = self._density_shape((B, P), labels)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        with torch.cuda.device(self.device):
+            ws = self._workspace("film", _lib.lib().fenerf_film_workspace_bytes(self._h, B))
+            _lib.check(_lib.lib().fenerf_siren_density(self._h, B, P, _ptr(points), _ptr(fg), _ptr(pg), int(bool(labels)), _ptr(out),
+                                                       C.c_void_p(ws.data_ptr()), _stream()))
+        return out
+
+    def siren_density_rays(self, origins, dirs, z, fg, pg, labels=True):
+        """origins/dirs [B,R,3], z [B,R,N] -> [B,R,N,n_lab+1] or [B,R,N]: siren_forward_rays' label and sigma channels"""
+        B, R, N = z.shape
+        fg, pg = self._film_geo(B, fg, pg)
+        origins, dirs, z = _f32(origins, self.device), _f32(dirs, self.device), _f32(z, self.device)
+        out = torch.empty(self._density_shape((B, R, N), labels), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            ws = self._workspace("film", _lib.lib().fenerf_film_workspace_bytes(self._h, B))
+            _lib.check(_lib.lib().fenerf_siren_density_rays(self._h, B, R, N, _ptr(origins), _ptr(dirs), _ptr(z), _ptr(fg), _ptr(pg),
+                                                            int(bool(labels)), _ptr(out), C.c_void_p(ws.data_ptr()), _stream()))
+        return out
+
+    def render_density(self, origins, dirs, z_coarse, u, noise_coarse, noise_final, fg, pg, opts, hierarchical=True, labels=True,
+                       want_weights=False, want_wsum=False):
+        """render() without its colour branch: (labels [B,R,n_lab] -- [B,R,n_lab+1] with the background channel of the seg_padding
+        fill modes in front -- or None, depth [B,R], weights [B,R,M] or None, wsum [B,R] or None), each the bits of render()'s."""
+        B, R, N = z_coarse.shape
+        dev = self.device
+        fg, pg = self._film_geo(B, fg, pg)
+        origins, dirs, z_coarse = _f32(origins, dev), _f32(dirs, dev), _f32(z_coarse, dev)
+        u = _f32(u, dev) if u is not None else None
+        noise_coarse = _f32(noise_coarse, dev) if noise_coarse is not None else None
+        noise_final = _f32(noise_final, dev) if noise_final is not None else None
+        M = 2 * N if hierarchical else N
+        pad = opts.fill_mode in (_lib.FILL["seg_padding_background"], _lib.FILL["eval_seg_padding_background"])
+        labels = bool(labels) and self.n_labels() > 0
+        lab = torch.empty((B, R, self.n_labels() + (1 if pad else 0)), dtype=torch.float32, device=dev) if labels else None
+        depth = torch.empty((B, R), dtype=torch.float32, device=dev)
+        weights = torch.empty((B, R, M), dtype=torch.float32, device=dev) if want_weights else None
+        wsum = torch.empty((B, R), dtype=torch.float32, device=dev) if want_wsum else None
+        l = _lib.lib()
+        with torch.cuda.device(dev):
+            nbytes = l.fenerf_render_density_workspace_bytes(self._h, B, R, N, int(hierarchical), int(labels))
+            ws = self._workspace("render_density", nbytes)
+            _lib.check(l.fenerf_render_density(self._h, B, R, N, int(hierarchical), _ptr(origins), _ptr(dirs), _ptr(z_coarse), _ptr(u),
+                                               _ptr(noise_coarse), _ptr(noise_final), _ptr(fg), _ptr(pg), C.byref(opts), int(labels),
+                                               _ptr(lab), _ptr(depth), _ptr(weights), _ptr(wsum), C.c_void_p(ws.data_ptr()),
+                                               C.c_size_t(ws.numel()), _stream()))
+        return lab, depth, weights, wsum
+
 
 class NativeLocalModel:
     """Owns a FenerfLocalModel*: SPATIALSIRENGRID's SIREN and its per-point mapping network packed into one fp32 stream; forward()

@@ -274,6 +274,27 @@ class _DoubleLatentSiren(_NativeSiren):
         return self.native(input.device).siren_forward(input, ray_directions, frequencies_geo, phase_shifts_geo,
                                                        frequencies_app, phase_shifts_app)
 
+    def geometry(self, input, z_geo, **kwargs):
+        """[B,P,3] points -> [B,P,n_lab+1] = [labels | sigma]: what forward() returns in those channels.  They depend on the geometry
+        latent alone (siren.py:1514, :1522-1527), so no z_app and no view direction is taken."""
+        fg, pg = self.geo_mapping_network(z_geo)
+        return self.geometry_with_frequencies_phase_shifts(input, fg, pg, **kwargs)
+
+    def geometry_with_frequencies_phase_shifts(self, input, frequencies_geo, phase_shifts_geo, **kwargs):
+        """Without grad, on a model the density route serves (NativeModel.supports_density), the native labels + sigma query: the bits of
+        forward_with_frequencies_phase_shifts' channels without its colour branch.  Otherwise that forward, sliced (the colour inputs it
+        needs are zeros and the locked view direction: labels and sigma do not read them) -- differentiable wherever the module is."""
+        if not self._wants_grad(input, frequencies_geo, phase_shifts_geo):
+            nat = self.native(input.device)
+            if nat.supports_density():
+                return nat.siren_density(input, frequencies_geo, phase_shifts_geo, labels=True)
+        n_app = len(self.color_layer_sine) * self.hidden_dim
+        zeros = frequencies_geo.new_zeros((frequencies_geo.shape[0], n_app))
+        rd = torch.zeros_like(input)
+        rd[..., -1] = -1
+        out = self.forward_with_frequencies_phase_shifts(input, frequencies_geo, zeros, phase_shifts_geo, zeros, rd)
+        return torch.cat([out[..., :-4], out[..., -1:]], dim=-1)
+
 
 class SIRENBASELINESEMANTICDISENTANGLE(_DoubleLatentSiren):
     """README 'w/o latent grid' model (siren.py:1163-1229)."""

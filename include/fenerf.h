@@ -942,6 +942,44 @@ int fenerf_render_forward(const FenerfModel* m, int B, int R, int N, int hierarc
                           const FenerfCompositeOpts* opts, float* out_rgb, float* out_depth, float* out_weights,
                           float* out_wsum, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- The geometry route: density and labels without the colour branch.
+ * replaces: nothing the reference has as a call of its own -- it evaluates the whole network and slices.  sigma and the label logits are
+ * functions of the geometry trunk alone (siren.py:1514, :1522-1527: the feature grid, the colour layers and the rgb head feed rgb only);
+ * these entries evaluate layer 0, the trunk and the label / sigma head and nothing else (69 % of a point's matrix work).  Callers that keep
+ * `out[..., -1]` of a full forward -- the voxel grid of extract_double_semantic_shapes.py:38-62 -- or the semantic map and depth of a view
+ * get the SAME BITS: a point's sigma and labels see the dense kernel's instruction sequence on the dense kernel's operands.
+ *
+ * out [dev] is a COMPACT row per point: with_labels != 0: [B,P,n_lab+1] = [labels | sigma]; with_labels == 0 (or a model without label
+ * channels): [B,P], sigma alone.  freq_geo / phase_geo [dev] [B, n_geo*H] raw mapping-network outputs; no view direction and no
+ * appearance parameters are taken.  film_ws: fenerf_film_workspace_bytes(m, B) bytes (the geometry layers' blocks are prepared by the
+ * launch itself).  fenerf_siren_density_rays: point (b,r,k) = origins[b,r] + dirs[b,r]*z[b,r,k], out [B,R,N,row].
+ *
+ * fenerf_render_density is fenerf_render_forward with both SIREN launches replaced by the density launch: coarse rows -> sigma-only
+ * composite + resampling -> fine rows -> merge + composite, on rows of n_lab + 1 (or 1) floats through the launchers of fenerf_composite /
+ * fenerf_merge_composite.  out_labels [B,R,n_lab] ([B,R,n_lab+1] with the background channel of the seg_padding fill modes in front) equals
+ * the first out_channels - 3 channels of fenerf_render_forward's out_rgb bit for bit, out_depth / out_weights / out_wsum equal its outputs
+ * bit for bit -- under either clamp, with noise, last_back and every fill mode.  Rows of sigma alone composite no channel: out_labels is
+ * then not written and may be NULL (a depth / weights render).  Any output may be NULL, not all of them.
+ *
+ * FENERF_E_UNSUPPORTED (a binding then takes the full forward and slices it): a FENERF_PREC_F32 model; forward mode FENERF_FORWARD_F16X2,
+ *   whose sigma is not the default's.  FENERF_FORWARD_F16X3_COLOR_X2 is served: its sigma and labels are the default's bits by construction.
+ *   (The per-point-modulated model is a FenerfLocalModel and has no entry here.)
+ * FENERF_E_INVALID: a NULL pointer, a negative count, N outside fenerf_render_forward's limits, a workspace below
+ *   fenerf_render_density_workspace_bytes.  Every refusal is made before anything is launched.  P = 0, R = 0 or B * R = 0: FENERF_OK,
+ *   nothing launched.
+ * Phase timers: every density launch counts under "siren_forward" and, inside that, under "siren_density" (like the split coarse pass).
+ * These entries were added without changing a struct or an existing signature: FENERF_ABI_VERSION is unchanged. */
+int fenerf_siren_density(const FenerfModel* m, int B, int64_t P, const float* points, const float* freq_geo, const float* phase_geo,
+                         int with_labels, float* out, void* film_ws, void* stream);
+int fenerf_siren_density_rays(const FenerfModel* m, int B, int R, int N, const float* origins, const float* dirs, const float* z,
+                              const float* freq_geo, const float* phase_geo, int with_labels, float* out, void* film_ws, void* stream);
+size_t fenerf_render_density_workspace_bytes(const FenerfModel* m, int B, int R, int N, int hierarchical, int with_labels);
+int fenerf_render_density(const FenerfModel* m, int B, int R, int N, int hierarchical, const float* origins, const float* dirs,
+                          const float* z_coarse, const float* u, const float* noise_coarse, const float* noise_final,
+                          const float* freq_geo, const float* phase_geo, const FenerfCompositeOpts* opts, int with_labels,
+                          float* out_labels, float* out_depth, float* out_weights, float* out_wsum, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,6 +42,9 @@ def build_parser():
     parser.add_argument('--iso', type=float, default=10.0, help='density level of the --mesh surface')
     parser.add_argument('--keep_largest', action='store_true', help='--mesh: keep only the largest connected component of {sigma >= iso}')
     parser.add_argument('--min_component', type=int, default=None, metavar='N', help='--mesh: drop components of fewer than N lattice points')
+    parser.add_argument('--labels', action='store_true',
+                        help='also write <seed>_labels.npy beside the .mrc: the semantic class (argmax of the label logits, uint8) of every lattice point '
+                             '(not in the reference)')
     parser.add_argument('--simplify', type=int, default=None, metavar='K', help='--mesh: merge the vertices of every K^3 block of cells (K >= 2)')
     return parser
 
@@ -56,6 +59,19 @@ def mesh_options(opt):
         raise SystemExit("--simplify needs K >= 2")
     keep = "largest" if opt.keep_largest else (opt.min_component if opt.min_component is not None else "all")
     return dict(keep=keep, simplify=opt.simplify)
+
+
+def sample_volume(sample, opt, *args, **kwargs):
+    """(density volume, label volume or None) of callers.sample_generator / sample_generator_wth_frequencies_phase_shifts as --labels asks"""
+    if opt.labels:
+        return sample(*args, return_labels=True, **kwargs)
+    return sample(*args, **kwargs), None
+
+
+def write_labels(path, labels):
+    import numpy as np
+    np.save(path, labels)
+    print(f"  labels {labels.shape} uint8, {len(np.unique(labels))} classes present -> {path}")
 
 
 def write_mesh(callers, imageio_lite, path, generator, opt, **latent):
@@ -82,9 +98,12 @@ def main(argv=None):
         for seed in opt.seeds:
             torch.manual_seed(int(seed))
             z = torch.randn(1, z_dim, device=device)
-            voxel_grid = callers.sample_generator(generator, z, cube_length=opt.cube_size, voxel_resolution=opt.voxel_resolution)
+            voxel_grid, labels = sample_volume(callers.sample_generator, opt, generator, z, cube_length=opt.cube_size,
+                                               voxel_resolution=opt.voxel_resolution)
             out = os.path.join(opt.output_dir, f'{seed}.mrc')
             imageio_lite.write_mrc(out, voxel_grid)
+            if labels is not None:
+                write_labels(os.path.join(opt.output_dir, f'{seed}_labels.npy'), labels)
             print(f"seed {seed}: sigma {voxel_grid.shape} in [{voxel_grid.min():.3g}, {voxel_grid.max():.3g}] -> {out}")
             if opt.mesh:
                 # the mean FiLM parameters are drawn from the generator state the seed and the z draw leave behind: the same state again, so
@@ -96,10 +115,12 @@ def main(argv=None):
         meta = torch.load(opt.latent_path, map_location=device, weights_only=False)
         fg, fa, pg, pa = callers.film_from_inversion(meta, device)
         meta = dict(meta, truncated_frequencies_geo=fg, truncated_frequencies_app=fa, truncated_phase_shifts_geo=pg, truncated_phase_shifts_app=pa)
-        voxel_grid = callers.sample_generator_wth_frequencies_phase_shifts(generator, meta, cube_length=opt.cube_size,
-                                                                           voxel_resolution=opt.voxel_resolution)
+        voxel_grid, labels = sample_volume(callers.sample_generator_wth_frequencies_phase_shifts, opt, generator, meta, cube_length=opt.cube_size,
+                                           voxel_resolution=opt.voxel_resolution)
         out = os.path.join(opt.output_dir, f'{opt.seeds[0]}.mrc')
         imageio_lite.write_mrc(out, voxel_grid)
+        if labels is not None:
+            write_labels(os.path.join(opt.output_dir, f'{opt.seeds[0]}_labels.npy'), labels)
         if opt.mesh:
             write_mesh(callers, imageio_lite, os.path.join(opt.output_dir, f'{opt.seeds[0]}.ply'), generator, opt, film=meta)
         print(f"inverted identity {opt.latent_path}: sigma {voxel_grid.shape} in [{voxel_grid.min():.3g}, {voxel_grid.max():.3g}] -> {out}")

@@ -33,6 +33,9 @@ def build_parser():
     parser.add_argument('--baked', type=int, default=None, metavar='RES',
                         help='bake each identity once into a RES^3 lattice (view direction locked) and render its views by trilinear lookup: an '
                              'approximation, RES^3 x 96 bytes of device memory (not in the reference; default: the exact renders)')
+    parser.add_argument('--labels_only', action='store_true',
+                        help='render only the semantic row (grid_<seed>_SEG.png, the same pixels) through the density route: no colour branch, no '
+                             'RGB grid (not in the reference; not with --baked or --geometry)')
     add_geometry_arguments(parser)
     return parser
 
@@ -75,7 +78,16 @@ def main(argv=None):
     curriculum = resolve_curriculum(opt.curriculum)
     os.makedirs(opt.output_dir, exist_ok=True)
     generator = callers.load_generator(opt.path, device, use_ema=not opt.no_ema)
+    if opt.labels_only and (opt.baked is not None or opt.geometry):
+        raise SystemExit("--labels_only takes neither --baked nor --geometry")
     for seed in opt.seeds:
+        if opt.labels_only:
+            segmaps, _ = callers.render_multiview(generator, curriculum, int(seed), device, image_size=opt.image_size,
+                                                  ray_step_multiplier=opt.ray_step_multiplier, lock_view_dependence=opt.lock_view_dependence,
+                                                  labels_only=True)
+            imageio_lite.save_image(segmaps, os.path.join(opt.output_dir, f'grid_{seed}_SEG.png'))
+            print(f"seed {seed}: {tuple(segmaps.shape)} -> {opt.output_dir}/grid_{seed}_SEG.png")
+            continue
         images, segmaps, *views = callers.render_multiview(generator, curriculum, int(seed), device, image_size=opt.image_size,
                                                            ray_step_multiplier=opt.ray_step_multiplier,
                                                            lock_view_dependence=opt.lock_view_dependence, baked=opt.baked,
