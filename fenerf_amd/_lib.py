@@ -201,6 +201,12 @@ _SIGS = {
     "fenerf_siren_density_rays": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "fenerf_render_density_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i, _i]),
     "fenerf_render_density": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 8 + [C.POINTER(FenerfCompositeOpts), _i] + [_vp] * 4 + [_vp, _sz, _vp]),
+    # proposal lattice (fenerf_proposal.hip): fine depths of a render from a baked density lattice, and the one-pass render that uses them
+    "fenerf_proposal_depths": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _i, _i, _i] + [_vp] * 5 +
+                               [C.POINTER(FenerfCompositeOpts)] + [_vp] * 3),
+    "fenerf_render_proposal_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "fenerf_render_proposal": (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _i, _i, _i, _i] + [_vp] * 10 +
+                               [C.POINTER(FenerfCompositeOpts)] + [_vp] * 4 + [_vp, _vp, _sz, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 N_PHASES = 19        # include/fenerf.h FENERF_N_PHASES_ALL

@@ -97,7 +97,8 @@ def _latent_dims(generator, default=256):
 
 
 def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.25, 0.0, 0.25, 0.5), image_size=256,
-                     ray_step_multiplier=2, lock_view_dependence=False, z_dim=None, latents=None, baked=None, geometry=False, labels_only=False):
+                     ray_step_multiplier=2, lock_view_dependence=False, z_dim=None, latents=None, baked=None, geometry=False, labels_only=False,
+                     proposal=None):
     """Five yaw angles of one identity (render_multiview_images_double_semantic.py:66-85).
     -> (images [V,3,S,S] in [-1,1], segmaps [V,3,S,S] in [0,1]) on the CPU.
     geometry: True, or a dict of render_geometry's options (light, ambient, background, alpha_min, space) -- every view goes through
@@ -106,7 +107,11 @@ def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.
     baked: a lattice resolution -- the identity is baked once (bake_field, view direction locked) and every view is rendered from the
     lattice by BakedField.render with the exact route's rays and draws: an approximation.  None = the exact renders.
     labels_only: only the semantic row and the depth, through generator.staged_geometry (no colour branch where the model's density route
-    serves it) -> (segmaps [V,3,S,S] in [0,1] -- the default call's, bit for bit --, depth maps [V,S,S]); not with baked or geometry."""
+    serves it) -> (segmaps [V,3,S,S] in [0,1] -- the default call's, bit for bit --, depth maps [V,S,S]); not with baked or geometry.
+    proposal: a lattice resolution -- the identity's DENSITY is baked once (bake_density) and every view places its samples from the
+    lattice and evaluates the network there (DensityField.render: one SIREN pass, view-dependent colour kept).  Not
+    with baked, geometry or labels_only.  None = the exact renders."""
+    _refuse_proposal_with("render_multiview", proposal, baked=baked, geometry=geometry, labels_only=labels_only)
     if labels_only and (baked is not None or geometry):
         raise ValueError("render_multiview: labels_only renders the exact semantic row; it takes neither baked nor geometry")
     kw = multiview_kwargs(curriculum, image_size, ray_step_multiplier, lock_view_dependence)
@@ -128,7 +133,12 @@ def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.
                 segmaps.append(mask2color(seg, device, scale=255.0))
                 depths.append(depth)
                 continue
-            if baked is None and not geometry:
+            if proposal is not None:
+                avg = generator.generate_avg_frequencies()          # staged_forward's draws before its render, per view
+                if field is None:
+                    field = _proposal_multiview_field(generator, z_geo, z_app, avg, kw, proposal)
+                img, _, _ = field.render(generator, **kw)
+            elif baked is None and not geometry:
                 img, _ = generator.staged_forward(z_geo, z_app, **kw)
             elif baked is None:
                 view = render_geometry(generator, z_geo, z_app, **geo, **kw)
@@ -412,6 +422,45 @@ class BakedField:
         return _render_geometry(generator, self.film, self, True, render_kwargs, light, ambient, background, alpha_min, space, details)
 
 
+def _bake_film(who, generator, z_geo, z_app, film, psi):
+    """the FiLM parameters a lattice is baked from, exactly as extract_mesh: the truncated z route or film= -> (fg, pg, fa, pa), device"""
+    siren = generator.siren
+    if film is None:
+        z_app = z_geo if z_app is None else z_app
+        device = z_geo.device
+        avg_fg, avg_pg, avg_fa, avg_pa = generator.generate_avg_frequencies()
+        raw_fg, raw_pg = siren.geo_mapping_network(z_geo)
+        raw_fa, raw_pa = siren.app_mapping_network(z_app)
+        fg, pg = avg_fg + psi * (raw_fg - avg_fg), avg_pg + psi * (raw_pg - avg_pg)
+        fa, pa = avg_fa + psi * (raw_fa - avg_fa), avg_pa + psi * (raw_pa - avg_pa)
+    else:
+        device = generator.device
+        fg, pg = film["truncated_frequencies_geo"], film["truncated_phase_shifts_geo"]
+        fa, pa = film["truncated_frequencies_app"], film["truncated_phase_shifts_app"]
+    if any(t.requires_grad for t in (fg, pg, fa, pa)):
+        raise RuntimeError(f"{who}: the baked route is no-grad only (a FiLM tensor requires grad)")
+    if fg.shape[0] != 1:
+        raise ValueError(f"{who}: one identity per lattice (FiLM batch of 1)")
+    return (fg, pg, fa, pa), torch.device(device)
+
+
+def _bake_slabs(n, origin, spacing, device, max_points):
+    """the points of an n^3 lattice, origin + i * spacing per coordinate column (one fp32 multiply, one fp32 add), in slabs of at most
+    max_points points along axis 0 padded to whole 32-point tiles -> (a0, a1, points [P + pad, 3], P) per slab"""
+    idx = torch.arange(n, dtype=torch.float32, device=device)
+    sp = torch.tensor(spacing, dtype=torch.float32, device=device)
+    axis = [idx * sp + torch.tensor(origin[k], dtype=torch.float32, device=device) for k in range(3)]      # origin + i * spacing
+    slab = max(1, min(n, int(max_points) // (n * n)))
+    for a0 in range(0, n, slab):
+        a1 = min(n, a0 + slab)
+        pts = torch.stack(torch.meshgrid(axis[0][a0:a1], axis[1], axis[2], indexing="ij"), dim=-1).reshape(-1, 3)
+        P = pts.shape[0]
+        pad = (-P) % 32
+        if pad:
+            pts = torch.cat([pts, pts[-1:].expand(pad, -1)])
+        yield a0, a1, pts, P
+
+
 def bake_field(generator, z_geo, z_app=None, *, film=None, resolution=256, center=(0, 0, 0), cube_length, psi=0.5, max_points=1 << 24):
     """Evaluates one identity's field ONCE on a resolution^3 lattice of the cube of side cube_length around `center` (baked_cube_length
     gives the side that holds a camera's samples) and keeps all C channels -> BakedField.  FiLM parameters exactly as extract_mesh: the
@@ -424,65 +473,147 @@ def bake_field(generator, z_geo, z_app=None, *, film=None, resolution=256, cente
         raise ValueError("bake_field: resolution must be at least 2")
     siren = generator.siren
     with torch.no_grad():
-        if film is None:
-            z_app = z_geo if z_app is None else z_app
-            device = z_geo.device
-            avg_fg, avg_pg, avg_fa, avg_pa = generator.generate_avg_frequencies()
-            raw_fg, raw_pg = siren.geo_mapping_network(z_geo)
-            raw_fa, raw_pa = siren.app_mapping_network(z_app)
-            fg, pg = avg_fg + psi * (raw_fg - avg_fg), avg_pg + psi * (raw_pg - avg_pg)
-            fa, pa = avg_fa + psi * (raw_fa - avg_fa), avg_pa + psi * (raw_pa - avg_pa)
-        else:
-            device = generator.device
-            fg, pg = film["truncated_frequencies_geo"], film["truncated_phase_shifts_geo"]
-            fa, pa = film["truncated_frequencies_app"], film["truncated_phase_shifts_app"]
-        if any(t.requires_grad for t in (fg, pg, fa, pa)):
-            raise RuntimeError("bake_field: the baked route is no-grad only (a FiLM tensor requires grad)")
-        if fg.shape[0] != 1:
-            raise ValueError("bake_field: one identity per lattice (FiLM batch of 1)")
-        device = torch.device(device)
+        (fg, pg, fa, pa), device = _bake_film("bake_field", generator, z_geo, z_app, film, psi)
         spacing = float(cube_length) / (n - 1)
         origin = tuple(float(c) - float(cube_length) / 2 for c in center)
         nat = siren.native(device)
         C_out = int(siren.output_dim)
         ld = max(BAKED_LD, (C_out + 3) // 4 * 4)
         vol = torch.zeros((n, n, n, ld), dtype=torch.float32, device=device)
-        idx = torch.arange(n, dtype=torch.float32, device=device)
-        sp = torch.tensor(spacing, dtype=torch.float32, device=device)
-        axis = [idx * sp + torch.tensor(origin[k], dtype=torch.float32, device=device) for k in range(3)]      # origin + i * spacing
-        slab = max(1, min(n, int(max_points) // (n * n)))
-        for a0 in range(0, n, slab):
-            a1 = min(n, a0 + slab)
-            pts = torch.stack(torch.meshgrid(axis[0][a0:a1], axis[1], axis[2], indexing="ij"), dim=-1).reshape(-1, 3)
-            P = pts.shape[0]
-            pad = (-P) % 32
-            if pad:
-                pts = torch.cat([pts, pts[-1:].expand(pad, -1)])
+        for a0, a1, pts, P in _bake_slabs(n, origin, spacing, device, max_points):
             rows = nat.siren_forward(pts[None].contiguous(), None, fg, pg, fa, pa)[0, :P]          # None = locked view dir
             vol[a0:a1, :, :, :C_out] = rows.reshape(a1 - a0, n, n, C_out)
             del rows, pts
     return BakedField(vol, origin, (spacing,) * 3, C_out, (fg, pg, fa, pa))
 
 
-def _baked_multiview_field(generator, z_geo, z_app, avg, kw, resolution):
-    """the lattice render_multiview's views read: staged_forward's truncated FiLM parameters (psi of the kwargs bag; avg = what
-    generate_avg_frequencies returned for this view's generator state), in the cube that holds the camera's samples"""
+def _multiview_film(generator, z_geo, z_app, avg, kw):
+    """staged_forward's truncated FiLM parameters (psi of the kwargs bag; avg = what generate_avg_frequencies returned for this view's
+    generator state) as the meta dict bake_field / bake_density take"""
     avg_fg, avg_pg, avg_fa, avg_pa = avg
     with torch.no_grad():
         raw_fg, raw_pg = generator.siren.geo_mapping_network(z_geo)
         raw_fa, raw_pa = generator.siren.app_mapping_network(z_app)
         psi = kw.get("psi", 1)
-        film = dict(truncated_frequencies_geo=avg_fg + psi * (raw_fg - avg_fg), truncated_phase_shifts_geo=avg_pg + psi * (raw_pg - avg_pg),
+        return dict(truncated_frequencies_geo=avg_fg + psi * (raw_fg - avg_fg), truncated_phase_shifts_geo=avg_pg + psi * (raw_pg - avg_pg),
                     truncated_frequencies_app=avg_fa + psi * (raw_fa - avg_fa), truncated_phase_shifts_app=avg_pa + psi * (raw_pa - avg_pa))
+
+
+def _baked_multiview_field(generator, z_geo, z_app, avg, kw, resolution):
+    """the lattice render_multiview's views read: staged_forward's truncated FiLM parameters, in the cube that holds the camera's samples"""
+    film = _multiview_film(generator, z_geo, z_app, avg, kw)
     cube = baked_cube_length(kw["fov"], kw["ray_start"], kw["ray_end"], num_steps=kw["num_steps"])
     return bake_field(generator, None, film=film, resolution=resolution, cube_length=cube)
 
 
 def _baked_inversion_field(generator, film, render_options, resolution):
     """the lattice the inversion renders read: film = film_from_inversion's (freq_geo, freq_app, phase_geo, phase_app)"""
-    meta = dict(truncated_frequencies_geo=film[0], truncated_frequencies_app=film[1], truncated_phase_shifts_geo=film[2], truncated_phase_shifts_app=film[3])
     cube = baked_cube_length(render_options["fov"], render_options["ray_start"], render_options["ray_end"], num_steps=render_options["num_steps"])
-    return bake_field(generator, None, film=meta, resolution=resolution, cube_length=cube)
+    return bake_field(generator, None, film=_film_meta(film), resolution=resolution, cube_length=cube)
+
+
+# ---- proposal lattice: bake an identity's DENSITY once, place every view's samples from it, evaluate the network there (INTEGRATION.md L) --
+class DensityField:
+    """One identity's density on a lattice (bake_density): vol [n0,n1,n2] on the device, lattice point i_k of axis k at origin[k] + i_k *
+    spacing[k].  sigma depends on position alone, so the lattice serves every view, view-dependent colour included.  film = the (freq_geo,
+    phase_geo, freq_app, phase_app) it was baked from: render() evaluates the network with them at the depths the lattice proposes."""
+
+    def __init__(self, vol, origin, spacing, film, outside_last=BAKED_OUTSIDE_SIGMA):
+        self.vol, self.origin, self.spacing = vol, tuple(float(x) for x in origin), tuple(float(x) for x in spacing)
+        self.film = film
+        self.outside_last = float(outside_last)
+
+    def sample(self, points):
+        """points [..., 3] on the device -> sigma [...] (native.volume_sample on the one-channel lattice)"""
+        if torch.is_grad_enabled() and points.requires_grad:
+            raise RuntimeError("DensityField.sample: the proposal route is no-grad only")
+        return native.volume_sample(self.vol.unsqueeze(-1), self.origin, self.spacing, points, self.outside_last, 1)[..., 0]
+
+    def _field_render(self, nat):
+        def field(origins, dirs, z_coarse, u, noise_coarse, noise_final, fg, pg, fa, pa, opts, hierarchical=True, lock_view=False,
+                  want_weights=False, want_wsum=False):
+            """NativeModel.render's signature, fed the exact route's draws as they come: u as is, the first N columns of noise_final
+            (noise is indexed by sorted position; N samples are composited)"""
+            N = z_coarse.shape[-1]
+            nf = noise_final[..., :N].contiguous() if noise_final is not None else None
+            return nat.render_proposal(self.vol, self.origin, self.spacing, origins, dirs, z_coarse, u, noise_coarse, nf, fg, pg, fa, pa, opts,
+                                       outside_last=self.outside_last, lock_view=lock_view, want_weights=want_weights, want_wsum=want_wsum)
+        return field
+
+    def render(self, generator, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean, hierarchical_sample=True,
+               sample_dist=None, lock_view_dependence=False, **kwargs):
+        """staged_forward_with_frequencies of the baked identity with the coarse SIREN pass replaced by a lookup into the density lattice:
+        the generator's own _render (the same rays, draws in the same order, composite options, fill modes) and image epilogue; the
+        network is evaluated once per ray sample, at the N depths resampled from the lattice's weights, with the caller's view direction
+        (lock_view_dependence as given).  -> (pixels [B,C',S,S], depth [B,S,S], third) on the CPU, as staged_forward_with_frequencies
+        returns them (weights: [B,R,N]).  No-grad only."""
+        if not hierarchical_sample:
+            raise ValueError("DensityField.render: hierarchical_sample=False has no fine samples to propose; render it with the exact route")
+        tensors = [t for t in (*self.film, h_mean, v_mean) if isinstance(t, torch.Tensor)]
+        if any(t.requires_grad for t in tensors):
+            raise RuntimeError("DensityField.render: the proposal route is no-grad only (a FiLM tensor or a pose requires grad)")
+        for k in ("psi", "max_batch_size", "depth_map", "near_clip", "far_clip"):      # staged_forward's own arguments
+            kwargs.pop(k, None)
+        B = self.film[0].shape[0]
+        with torch.no_grad():
+            field = self._field_render(generator.siren.native(generator.device))
+            pixels, depth, third, _, _ = generator._render(self.film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean,
+                                                           v_mean, True, sample_dist, bool(lock_view_dependence), kwargs, use_fill=True,
+                                                           third="auto", field_render=field)
+            depth_map = native.to_host(depth.reshape(B, img_size, img_size).contiguous())
+            third = native.to_host(third.reshape((B, img_size, img_size, -1)).permute(0, 3, 1, 2).contiguous() * 2 - 1)
+            pixels = native.to_host(generator._finish_scaled(pixels, B, img_size))
+        return pixels, depth_map, third
+
+
+def bake_density(generator, z_geo, z_app=None, *, film=None, resolution=256, center=(0, 0, 0), cube_length, psi=0.5, max_points=1 << 24):
+    """Evaluates one identity's DENSITY once on a resolution^3 lattice of the cube of side cube_length around `center` -> DensityField.
+    FiLM parameters, cube, lattice points and slabs exactly as bake_field; sigma from _lattice_sigma (the density route where the model
+    serves it, else the full forward: the same bits).  Memory: resolution^3 x 4 bytes."""
+    n = int(resolution)
+    if n < 2:
+        raise ValueError("bake_density: resolution must be at least 2")
+    with torch.no_grad():
+        (fg, pg, fa, pa), device = _bake_film("bake_density", generator, z_geo, z_app, film, psi)
+        spacing = float(cube_length) / (n - 1)
+        origin = tuple(float(c) - float(cube_length) / 2 for c in center)
+        nat = generator.siren.native(device)
+        vol = torch.empty((n, n, n), dtype=torch.float32, device=device)
+        for a0, a1, pts, P in _bake_slabs(n, origin, spacing, device, max_points):
+            sigma, _ = _lattice_sigma(nat, pts[None].contiguous(), fg, pg, fa, pa)
+            vol[a0:a1] = sigma[0, :P].reshape(a1 - a0, n, n)
+            del sigma, pts
+    return DensityField(vol, origin, (spacing,) * 3, (fg, pg, fa, pa))
+
+
+def _film_meta(film):
+    """film_from_inversion's (freq_geo, freq_app, phase_geo, phase_app) as the meta dict bake_field / bake_density take"""
+    return dict(truncated_frequencies_geo=film[0], truncated_frequencies_app=film[1], truncated_phase_shifts_geo=film[2], truncated_phase_shifts_app=film[3])
+
+
+def _proposal_multiview_field(generator, z_geo, z_app, avg, kw, resolution):
+    """_baked_multiview_field's density counterpart: the same FiLM parameters, the same cube"""
+    film = _multiview_film(generator, z_geo, z_app, avg, kw)
+    cube = baked_cube_length(kw["fov"], kw["ray_start"], kw["ray_end"], num_steps=kw["num_steps"])
+    return bake_density(generator, None, film=film, resolution=resolution, cube_length=cube)
+
+
+def _proposal_inversion_field(generator, film, render_options, resolution):
+    """_baked_inversion_field's density counterpart"""
+    cube = baked_cube_length(render_options["fov"], render_options["ray_start"], render_options["ray_end"], num_steps=render_options["num_steps"])
+    return bake_density(generator, None, film=_film_meta(film), resolution=resolution, cube_length=cube)
+
+
+def _refuse_proposal_with(who, proposal, **others):
+    """proposal= places the samples of the exact colour render; it goes with none of the routes named in `others`"""
+    if proposal is None:
+        return
+    taken = [k for k, v in others.items() if v is not None and v is not False]
+    if taken:
+        raise ValueError(f"{who}: proposal renders the network's own pixels at depths placed from a baked density lattice; it does not "
+                         f"combine with {' / '.join(taken)}")
+    if int(proposal) < 2:
+        raise ValueError(f"{who}: proposal is a lattice resolution of at least 2")
 
 
 # ---- geometry views: surface normals and a shaded "shape" image for the pixels of a render (INTEGRATION.md J) --------------------------
@@ -701,12 +832,16 @@ def _inversion_pose(pose):
     return None if pose is None else (float(pose[0]), float(pose[1]))
 
 
-def render_inversion_views(generator, meta, render_options, angles=(0.0,), max_batch_size=2400000, lock_view_dependence=False, pose=None, baked=None):
+def render_inversion_views(generator, meta, render_options, angles=(0.0,), max_batch_size=2400000, lock_view_dependence=False, pose=None, baked=None,
+                           proposal=None):
     """staged_forward_with_frequencies of an inversion state at yaws pi/2 + angle (:419-431, :441-446) -> [(angle, frame [1,22,S,S])].
     pose: (yaw, pitch) to centre the angles on instead -- what inverse_render(optimize_pose=True) recovered.
     baked: a lattice resolution -- bake the inverted identity once (view direction locked) and render every view from the lattice
-    (BakedField.render: an approximation).  None = the exact renders."""
+    (BakedField.render: an approximation).  None = the exact renders.
+    proposal: a lattice resolution -- bake the inverted identity's density once and place every view's samples from it (DensityField.render,
+    INTEGRATION.md L; lock_view_dependence is honoured).  Not with baked."""
     import math
+    _refuse_proposal_with("render_inversion_views", proposal, baked=baked)
     film = film_from_inversion(meta)
     pose = _inversion_pose(pose)
     if pose is not None:
@@ -715,9 +850,11 @@ def render_inversion_views(generator, meta, render_options, angles=(0.0,), max_b
     out = []
     with torch.no_grad():
         field = None if baked is None else _baked_inversion_field(generator, film, render_options, baked)
+        if proposal is not None:
+            field = _proposal_inversion_field(generator, film, render_options, proposal)
         for angle in angles:
             if field is not None:
-                img, _, _ = field.render(generator, h_mean=centre + angle, **render_options)
+                img, _, _ = field.render(generator, h_mean=centre + angle, lock_view_dependence=lock_view_dependence, **render_options)
             else:
                 img, _, _ = generator.staged_forward_with_frequencies(*film, h_mean=centre + angle, max_batch_size=max_batch_size,
                                                                       lock_view_dependence=lock_view_dependence, **render_options)
@@ -725,14 +862,17 @@ def render_inversion_views(generator, meta, render_options, angles=(0.0,), max_b
     return out
 
 
-def render_inversion_recon(generator, meta, render_options, trajectory, max_batch_size=2400000, lock_view_dependence=False, pose=None, baked=None):
+def render_inversion_recon(generator, meta, render_options, trajectory, max_batch_size=2400000, lock_view_dependence=False, pose=None, baked=None,
+                           proposal=None):
     """The frames of run_render_recon_video (:462-501): per trajectory entry one staged render of the inverted identity at (pitch, yaw) --
     the trajectory's fov is NOT applied (the reference sets only h_mean / v_mean) -- as uint8 [S, 3 S, 3] RGB panels
     [image | label colours | 0.5 / 0.5 blend] (the reference hands them to cv2 as BGR).
     pose: (yaw, pitch) the trajectory -- written around the frontal (pi / 2, pi / 2) -- is moved to: what inverse_render(optimize_pose=True)
-    recovered.  baked: a lattice resolution -- bake once, render every frame from the lattice (as render_inversion_views)."""
+    recovered.  baked: a lattice resolution -- bake once, render every frame from the lattice (as render_inversion_views).
+    proposal: a lattice resolution -- bake the density once, place every frame's samples from it (as render_inversion_views); not with baked."""
     import math
     from . import imageio_lite
+    _refuse_proposal_with("render_inversion_recon", proposal, baked=baked)
     film = film_from_inversion(meta)
     pose = _inversion_pose(pose)
     d_yaw, d_pitch = (0.0, 0.0) if pose is None else (pose[0] - math.pi / 2, pose[1] - math.pi / 2)
@@ -741,10 +881,12 @@ def render_inversion_recon(generator, meta, render_options, trajectory, max_batc
     to_u8 = lambda t: imageio_lite.to_uint8_hwc(imageio_lite.make_grid(t, normalize=True))     # tensor_to_PIL (:114-119)
     with torch.no_grad():
         field = None if baked is None else _baked_inversion_field(generator, film, kw, baked)
+        if proposal is not None:
+            field = _proposal_inversion_field(generator, film, kw, proposal)
         for _, pitch, yaw, _ in trajectory:
             kw.update(h_mean=float(yaw) + d_yaw, v_mean=float(pitch) + d_pitch)
             if field is not None:
-                frame, _, _ = field.render(generator, **kw)
+                frame, _, _ = field.render(generator, lock_view_dependence=lock_view_dependence, **kw)
             else:
                 frame, _, _ = generator.staged_forward_with_frequencies(*film, max_batch_size=max_batch_size, lock_view_dependence=lock_view_dependence, **kw)
             image, sem = to_u8(frame[:, -3:].cpu()), to_u8(mask2color(frame[:, :-3], generator.device))

@@ -1698,6 +1698,106 @@ extern "C" int fenerf_render_density(const FenerfModel* m, int B, int R, int N, 
   return run_composite(cp, true, stream);
 }
 
+// ---- proposal lattice: the coarse pass of a render as a lookup into a baked density lattice (fenerf_proposal.hip) ----
+namespace {
+// everything fenerf_proposal_depths refuses, for both entries that reach its kernel; *p is complete but for z_fine / weights
+int proposal_params(const char* who, const float* vol, int n0, int n1, int n2, const float* origin, const float* spacing, float outside_last, int B,
+                    int R, int N, const float* origins, const float* dirs, const float* z_coarse, const float* u, const float* noise_coarse,
+                    const FenerfCompositeOpts* opts, ProposalParams* p) {
+  if (int rc = check_lattice(who, n0, n1, n2)) return rc;
+  if (!vol || !origin || !spacing) return fail(FENERF_E_INVALID, std::string(who) + ": vol / origin / spacing is NULL");
+  for (int k = 0; k < 3; ++k)
+    if (!(std::isfinite(spacing[k]) && spacing[k] > 0.f)) return fail(FENERF_E_INVALID, std::string(who) + ": spacing must be finite and positive");
+  if (!opts) return fail(FENERF_E_INVALID, std::string(who) + ": opts is NULL");
+  if (int rc = check_opts(opts)) return rc;
+  if (B < 0 || R < 0) return fail(FENERF_E_INVALID, std::string(who) + ": negative count");
+  if (N < 3 || 2 * N > FENERF_MAX_RAY_SAMPLES) return fail(FENERF_E_INVALID, std::string(who) + ": 3 to 512 samples per ray (FENERF_MAX_RAY_SAMPLES / 2)");
+  if (!origins || !dirs || !z_coarse || !u) return fail(FENERF_E_INVALID, std::string(who) + ": origins / dirs / z_coarse / u is NULL");
+  memset(p, 0, sizeof(*p));
+  p->vol = vol; p->n0 = n0; p->n1 = n1; p->n2 = n2;
+  for (int k = 0; k < 3; ++k) { p->origin[k] = origin[k]; p->spacing[k] = spacing[k]; }
+  p->outside_last = outside_last;
+  p->BR = (long long)B * R; p->N = N;
+  p->origins = origins; p->dirs = dirs; p->z = z_coarse; p->u = u; p->noise = noise_coarse;
+  p->clamp_mode = opts->clamp_mode; p->noise_std = opts->noise_std;
+  return FENERF_OK;
+}
+int run_proposal(const ProposalParams& p, void* stream) {
+  PhaseScope ph(PH_RESAMPLE, stream);      // the launch that places the fine samples
+  return launch_proposal_depths(p, stream);
+}
+struct RenderProposalWs {
+  size_t zf, rows, total;
+};
+RenderProposalWs render_proposal_ws(int B, int R, int N, int C) {
+  RenderProposalWs w;
+  const size_t pts = (size_t)B * R * N;
+  size_t off = 0;
+  w.zf = off; off += align_up(pts * sizeof(float), 256);
+  w.rows = off; off += align_up(pts * C * sizeof(float), 256);
+  w.total = off;
+  return w;
+}
+}  // namespace
+
+extern "C" int fenerf_proposal_depths(const float* vol, int n0, int n1, int n2, const float origin[3], const float spacing[3], float outside_last,
+                                      int B, int R, int N, const float* origins, const float* dirs, const float* z_coarse, const float* u,
+                                      const float* noise_coarse, const FenerfCompositeOpts* opts, float* z_fine, float* coarse_weights,
+                                      void* stream) {
+  ProposalParams p;
+  if (int rc = proposal_params("fenerf_proposal_depths", vol, n0, n1, n2, origin, spacing, outside_last, B, R, N, origins, dirs, z_coarse, u,
+                               noise_coarse, opts, &p))
+    return rc;
+  if (!z_fine) return fail(FENERF_E_INVALID, "fenerf_proposal_depths: z_fine is NULL");
+  if (p.BR == 0) return FENERF_OK;
+  p.z_fine = z_fine; p.weights = coarse_weights;
+  return run_proposal(p, stream);
+}
+
+extern "C" size_t fenerf_render_proposal_workspace_bytes(int B, int R, int N, int C) {
+  if (B <= 0 || R <= 0 || N < 3 || 2 * N > FENERF_MAX_RAY_SAMPLES || C < 2 || C > 64) return 0;
+  return render_proposal_ws(B, R, N, C).total;
+}
+
+extern "C" int fenerf_render_proposal(const FenerfModel* m, const float* vol, int n0, int n1, int n2, const float origin[3], const float spacing[3],
+                                      float outside_last, int B, int R, int N, int lock_view, const float* origins, const float* dirs,
+                                      const float* z_coarse, const float* u, const float* noise_coarse, const float* noise_final,
+                                      const float* freq_geo, const float* phase_geo, const float* freq_app, const float* phase_app,
+                                      const FenerfCompositeOpts* opts, float* out_rgb, float* out_depth, float* out_weights, float* out_wsum,
+                                      void* film_ws, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!m) return fail(FENERF_E_INVALID, "fenerf_render_proposal: model is NULL");
+  ProposalParams pp;
+  if (int rc = proposal_params("fenerf_render_proposal", vol, n0, n1, n2, origin, spacing, outside_last, B, R, N, origins, dirs, z_coarse, u,
+                               noise_coarse, opts, &pp))
+    return rc;
+  if (!out_rgb) return fail(FENERF_E_INVALID, "fenerf_render_proposal: out_rgb is NULL");
+  if (!freq_geo || !phase_geo || !freq_app || !phase_app || !film_ws)
+    return fail(FENERF_E_INVALID, "fenerf_render_proposal: film parameter / workspace pointer is NULL");
+  if (opts->fill_mode == FENERF_FILL_EVAL_WHITE_BACK && m->C != 4) return fail(FENERF_E_INVALID, "eval_white_back needs a 3-channel model");
+  if (pp.BR == 0) return FENERF_OK;
+  const RenderProposalWs ws = render_proposal_ws(B, R, N, m->C);
+  if (!workspace || workspace_bytes < ws.total)
+    return fail(FENERF_E_INVALID, "fenerf_render_proposal: workspace too small (see fenerf_render_proposal_workspace_bytes)");
+  char* base = (char*)workspace;
+  float* zf = (float*)(base + ws.zf);
+  float* rows = (float*)(base + ws.rows);
+  pp.z_fine = zf;
+  int rc = run_proposal(pp, stream);                         // 1. fine depths from the lattice, ascending
+  if (rc) return rc;
+  const float *fp, *ppf;                                     // 2. the one SIREN pass: fenerf_siren_forward_rays at those depths
+  rc = film_prep(m, B, freq_geo, phase_geo, freq_app, phase_app, film_ws, &fp, &ppf, stream);
+  if (rc) return rc;
+  rc = run_siren(m, ray_params(m, fp, ppf, B, R, N, origins, dirs, zf, lock_view, rows), stream);
+  if (rc) return rc;
+  CompositeParams cp;                                        // 3. fenerf_composite: the depths are sorted, nothing to merge
+  memset(&cp, 0, sizeof(cp));
+  cp.BR = pp.BR; cp.M = N; cp.C = m->C; cp.N = N;
+  cp.rows_a = rows; cp.z_a = zf; cp.noise = noise_final; cp.o = *opts;
+  cp.out_rgb = out_rgb; cp.out_depth = out_depth; cp.out_weights = out_weights; cp.out_wsum = out_wsum;
+  cp.out_ch = out_channels(m->C, opts);
+  return run_composite(cp, false, stream);
+}
+
 // =====================================================================================================================================
 // The differentiable hierarchical render as TWO calls (round 5; SURVEY.md 8b "fenerf_render_backward"): what rounds 1-4 orchestrated in
 // Python (fenerf_amd/generators/autograd.py::_hierarchical_forward / HierarchicalRenderFunction.backward, siren/autograd.py::

@@ -285,6 +285,26 @@ struct VolumeParams {
   float* rows;             // [P][C]
 };
 int launch_volume_sample(const VolumeParams& p, void* stream);
+// fenerf_proposal.hip: the coarse pass of a render on a baked density lattice vol [n0][n1][n2] (one channel, ld = 1) -- trilinear sigma at
+// origins + dirs * z, the coarse weights, the resampled depths -- with the fine depths of every ray left in ascending order
+struct ProposalParams {
+  const float* vol;
+  int n0, n1, n2;
+  float origin[3], spacing[3];
+  float outside_last;      // sigma of a sample outside the lattice
+  long long BR;
+  int N;
+  const float* origins;    // [BR][3]
+  const float* dirs;       // [BR][3]
+  const float* z;          // [BR][N] coarse depths
+  const float* u;          // [BR][N]
+  const float* noise;      // [BR][N] or nullptr
+  int clamp_mode;          // of the coarse composite, with noise_std: what it reads of a FenerfCompositeOpts
+  float noise_std;
+  float* z_fine;           // [BR][N] out, ascending (stable, NaN last)
+  float* weights;          // [BR][N] out: the coarse weights, or nullptr
+};
+int launch_proposal_depths(const ProposalParams& p, void* stream);
 int launch_pad_rows(const float* src, float* dst, long long nb, long long P, long long Pp, int C, bool to_padded, void* stream);
 int launch_multi_add(const MultiAdd& J, void* stream);
 int launch_film_fold(const FilmFold& J, void* stream);

@@ -1027,6 +1027,35 @@ class NativeModel:
                                                _stream()))
         return rgb, depth, weights, wsum
 
+    def render_proposal(self, vol, origin, spacing, origins, dirs, z_coarse, u, noise_coarse, noise_final, fg, pg, fa, pa, opts,
+                        outside_last=0.0, lock_view=False, want_weights=False, want_wsum=False):
+        """render() with its coarse SIREN pass replaced by a lookup into a baked density lattice vol [n0,n1,n2] (fenerf_render_proposal,
+        include/fenerf.h "proposal lattice"): proposal_depths -> siren_forward_rays at the sorted fine depths -> composite.  noise_final
+        [B,R,N] by sorted position.  Returns (rgb [B,R,C'], depth [B,R], weights [B,R,N] or None, wsum [B,R] or None)."""
+        B, R, N = z_coarse.shape
+        dev = self.device
+        largs = _density_lattice_args(vol, origin, spacing, outside_last)
+        fg, pg, fa, pa = self._film(B, fg, pg, fa, pa)
+        origins, dirs, z_coarse = _f32(origins, dev), _f32(dirs, dev), _f32(z_coarse, dev)
+        u = _f32(u, dev) if u is not None else None
+        noise_coarse = _f32(noise_coarse, dev) if noise_coarse is not None else None
+        noise_final = _f32(noise_final, dev) if noise_final is not None else None
+        pad = opts.fill_mode in (_lib.FILL["seg_padding_background"], _lib.FILL["eval_seg_padding_background"])
+        Cout = self.C if pad else self.C - 1
+        rgb = torch.empty((B, R, Cout), dtype=torch.float32, device=dev)
+        depth = torch.empty((B, R), dtype=torch.float32, device=dev)
+        weights = torch.empty((B, R, N), dtype=torch.float32, device=dev) if want_weights else None
+        wsum = torch.empty((B, R), dtype=torch.float32, device=dev) if want_wsum else None
+        l = _lib.lib()
+        with torch.cuda.device(dev):
+            film = self._workspace("film", l.fenerf_film_workspace_bytes(self._h, B))
+            ws = self._workspace("render_proposal", l.fenerf_render_proposal_workspace_bytes(B, R, N, self.C))
+            _lib.check(l.fenerf_render_proposal(self._h, *largs, B, R, N, int(lock_view), _ptr(origins), _ptr(dirs), _ptr(z_coarse), _ptr(u),
+                                                _ptr(noise_coarse), _ptr(noise_final), _ptr(fg), _ptr(pg), _ptr(fa), _ptr(pa), C.byref(opts),
+                                                _ptr(rgb), _ptr(depth), _ptr(weights), _ptr(wsum), C.c_void_p(film.data_ptr()),
+                                                C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream()))
+        return rgb, depth, weights, wsum
+
     # ---- the geometry route: labels and sigma without the colour branch (include/fenerf.h "The geometry route")
     def supports_density(self):
         """True when siren_density / siren_density_rays / render_density serve this model: an f16x3 model whose forward mode keeps
@@ -1668,6 +1697,31 @@ def volume_render(vol, origin, spacing, origins, dirs, z_coarse, u, noise_coarse
                                           _ptr(noise_final), C.byref(opts), _ptr(rgb), _ptr(depth), _ptr(weights), _ptr(wsum),
                                           C.c_void_p(ws.data_ptr()), C.c_size_t(int(nbytes)), _stream()))
     return rgb, depth, weights, wsum
+
+
+def _density_lattice_args(vol, origin, spacing, outside_last):
+    """the lattice arguments of the fenerf_proposal_* entries, from a device density lattice [n0,n1,n2]"""
+    assert vol.is_cuda and vol.dim() == 3 and vol.dtype == torch.float32 and vol.is_contiguous(), "expected a contiguous fp32 device lattice [n0,n1,n2]"
+    n0, n1, n2 = vol.shape
+    o3, s3 = (C.c_float * 3)(*(float(x) for x in origin)), (C.c_float * 3)(*(float(x) for x in spacing))
+    return C.c_void_p(vol.data_ptr()), n0, n1, n2, o3, s3, float(outside_last)
+
+
+def proposal_depths(vol, origin, spacing, origins, dirs, z_coarse, u, noise_coarse, opts, outside_last=0.0, want_weights=False):
+    """The coarse pass of a hierarchical render on a baked density lattice vol [n0,n1,n2] (fenerf_proposal_depths, include/fenerf.h "proposal
+    lattice"): trilinear sigma at origins + dirs * z_coarse -> coarse weights -> resampled depths, sorted.  origins / dirs [B,R,3], z_coarse
+    [B,R,N], u [B*R,N], noise_coarse [B,R,N] or None -> (z_fine [B,R,N] ascending, coarse weights [B,R,N] or None)."""
+    dev = vol.device
+    args = _density_lattice_args(vol, origin, spacing, outside_last)
+    B, R, N = z_coarse.shape
+    origins, dirs, z_coarse, u = _f32(origins, dev), _f32(dirs, dev), _f32(z_coarse, dev), _f32(u, dev)
+    noise_coarse = _f32(noise_coarse, dev) if noise_coarse is not None else None
+    zf = torch.empty((B, R, N), dtype=torch.float32, device=dev)
+    w = torch.empty((B, R, N), dtype=torch.float32, device=dev) if want_weights else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_proposal_depths(*args, B, R, N, _ptr(origins), _ptr(dirs), _ptr(z_coarse), _ptr(u), _ptr(noise_coarse),
+                                                     C.byref(opts), _ptr(zf), _ptr(w), _stream()))
+    return zf, w
 
 
 def surface_points(origins, dirs, depth, alpha=None, alpha_min=0.5):

@@ -980,6 +980,49 @@ int fenerf_render_density(const FenerfModel* m, int B, int R, int N, int hierarc
                           float* out_labels, float* out_depth, float* out_weights, float* out_wsum, void* workspace,
                           size_t workspace_bytes, void* stream);
 
+/* ---- proposal lattice: the coarse pass of a render as a lookup into a baked DENSITY lattice (fenerf_proposal.hip) ----
+ * replaces: the coarse half of generators.py:479-499 -- the coarse SIREN evaluation, its weights-only fancy_integration and the
+ * importance resampling -- for renders of an identity whose density has been baked once.  sigma depends on position alone (not on the
+ * view direction, not on the appearance code: siren.py:1514, :1522-1527), so one lattice of sigma serves every view of an identity,
+ * view-dependent colour included.  The coarse pass exists only to place the fine samples; here it reads the lattice, and the ONE SIREN
+ * pass that remains runs at the depths it proposes.  An opt-in APPROXIMATION of sample placement and sample count (N importance samples
+ * are composited, not N + N merged ones); every composited row is the network's own.
+ *
+ * fenerf_proposal_depths: vol [dev] [n0][n1][n2] fp32 (one channel per lattice point: C = 1, ld = 1 of the baked radiance lattice above),
+ *   origin / spacing [host] [3], outside_last = sigma of a sample outside the lattice; origins / dirs [dev] [B*R][3], z_coarse [dev] [B][R][N],
+ *   u [dev] [B*R][N], noise_coarse [dev] [B][R][N] or NULL, opts (clamp_mode and noise_std are read, as by fenerf_volume_render's coarse
+ *   composite) -> z_fine [dev] [B*R][N] ascending, coarse_weights [dev] [B*R][N] or NULL (not written).  One wave per ray:
+ *   1. sigma at origins + dirs * z_coarse: fenerf_volume_sample_rays with C = 1; rules 1-7 of the baked radiance lattice hold.
+ *   2. the weights fenerf_composite computes from rows [0 | sigma] with noise_coarse (the kernel's own per-ray body).
+ *   3. the depths fenerf_resample draws from z_coarse, those weights and u.
+ *   4. sorted ascending in the total order of fenerf_merge_composite: stable, NaN after +Inf (torch.sort).
+ *   z_fine is bit for bit torch.sort(fenerf_resample(z_coarse, w, u)) with w from fenerf_composite on [0 | fenerf_volume_sample_rays];
+ *   coarse_weights is bit for bit that w.  A non-finite depth or lattice value stays in its own ray.  No atomics: the same bytes on every run.
+ *   FENERF_E_INVALID, before anything is launched: vol, origin, spacing, origins, dirs, z_coarse, u or z_fine NULL; opts NULL; an axis below
+ *   2 points or more than 2^31 - 1 lattice points; spacing[k] not finite or not positive; B or R negative; N outside 3 .. 512
+ *   (FENERF_MAX_RAY_SAMPLES / 2).  FENERF_E_CLAMP_MODE: an unknown clamp mode.  B * R = 0 launches nothing and returns FENERF_OK.
+ *
+ * fenerf_render_proposal = three launches: fenerf_proposal_depths -> fenerf_siren_forward_rays at z_fine (lock_view as given; 0 = the
+ *   colour sees the ray's direction) -> fenerf_composite with noise_final [B][R][N] (indexed by sorted position) and `opts`, through the
+ *   launchers the public entries use: bit for bit that chain of public calls, in every forward mode fenerf_siren_forward_rays serves.
+ *   Outputs as fenerf_render_forward with N samples per ray: out_rgb, out_depth, out_weights [B*R][N] or NULL, out_wsum or NULL.
+ *   film_ws: fenerf_film_workspace_bytes(m, B) bytes; workspace: fenerf_render_proposal_workspace_bytes(B, R, N, C of the
+ *   model) bytes [dev] (z_fine and the [B*R][N][C] rows; 0 for invalid arguments, like fenerf_volume_render_workspace_bytes).  Not differentiable.
+ *   FENERF_E_INVALID: everything fenerf_proposal_depths refuses (but z_fine, which lives in the workspace); m, out_rgb, a film parameter
+ *   or film_ws NULL; a workspace that is too small.  B * R = 0 launches nothing and returns FENERF_OK.
+ * Phase timers: the proposal launch counts under "resample".
+ * These entries were added without changing a struct or an existing signature: FENERF_ABI_VERSION is unchanged. */
+int fenerf_proposal_depths(const float* vol, int n0, int n1, int n2, const float origin[3], const float spacing[3], float outside_last, int B,
+                           int R, int N, const float* origins, const float* dirs, const float* z_coarse, const float* u,
+                           const float* noise_coarse, const FenerfCompositeOpts* opts, float* z_fine, float* coarse_weights, void* stream);
+size_t fenerf_render_proposal_workspace_bytes(int B, int R, int N, int C);
+int fenerf_render_proposal(const FenerfModel* m, const float* vol, int n0, int n1, int n2, const float origin[3], const float spacing[3],
+                           float outside_last, int B, int R, int N, int lock_view, const float* origins, const float* dirs,
+                           const float* z_coarse, const float* u, const float* noise_coarse, const float* noise_final,
+                           const float* freq_geo, const float* phase_geo, const float* freq_app, const float* phase_app,
+                           const FenerfCompositeOpts* opts, float* out_rgb, float* out_depth, float* out_weights, float* out_wsum,
+                           void* film_ws, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

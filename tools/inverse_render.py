@@ -88,7 +88,19 @@ def build_parser():
     parser.add_argument('--baked', type=int, default=None, metavar='RES',
                         help='--recon: bake the inverted identity once into a RES^3 lattice (view direction locked) and render the frames by '
                              'trilinear lookup: an approximation, RES^3 x 96 bytes of device memory (default: the exact renders)')
+    parser.add_argument('--proposal', type=int, default=None, metavar='RES',
+                        help='--recon: bake the inverted identity\'s density once into a RES^3 lattice and place every frame\'s samples from it: '
+                             'one SIREN pass per frame, view-dependent colour kept; RES^3 x 4 bytes of device memory (not with --baked)')
     return parser
+
+
+def parse_options(argv=None):
+    """the parsed arguments, with the combinations no route serves refused by the parser"""
+    parser = build_parser()
+    opt = parser.parse_args(argv)
+    if opt.proposal is not None and opt.baked is not None:
+        parser.error("--proposal and --baked are two routes for the same frames: give one")
+    return opt
 
 
 def run_inverse_render(opt, generator, img_path, seg_path, percept=None):
@@ -158,7 +170,8 @@ def run_render_recon_video(opt, generator, checkpoint_path):
     render_options = callers.inversion_render_options(opt.fov, opt.fill_color, opt.preview_size, opt.preview_steps)
     frames = callers.render_inversion_recon(generator, meta, render_options, callers.inversion_trajectory(opt.trajectory, opt.num_frames, opt.fov),
                                             opt.max_batch_size, opt.lock_view_dependence,
-                                            pose=(meta['yaw'], meta['pitch']) if 'yaw' in meta else None, baked=opt.baked)
+                                            pose=(meta['yaw'], meta['pitch']) if 'yaw' in meta else None, baked=opt.baked,
+                                            proposal=opt.proposal)
     out = os.path.join(opt.save_dir, f'reconstructed_debug_{opt.trajectory}_{opt.fill_color}.avi')
     writer = imageio_lite.AviWriter(out, fps=25)
     for f in frames:
@@ -171,7 +184,7 @@ def run_render_recon_video(opt, generator, checkpoint_path):
 def main(argv=None):
     from fenerf_amd import host
     host.respect_cpu_quota()          # torch's CPU thread pool no larger than the cores this process is granted (fenerf_amd/host.py)
-    opt = build_parser().parse_args(argv)
+    opt = parse_options(argv)
     import torch
     from fenerf_amd import callers
     if not torch.cuda.is_available():

@@ -36,8 +36,23 @@ def build_parser():
     parser.add_argument('--labels_only', action='store_true',
                         help='render only the semantic row (grid_<seed>_SEG.png, the same pixels) through the density route: no colour branch, no '
                              'RGB grid (not in the reference; not with --baked or --geometry)')
+    parser.add_argument('--proposal', type=int, default=None, metavar='RES',
+                        help='bake each identity\'s density once into a RES^3 lattice and place every view\'s samples from it: one SIREN pass per '
+                             'view at the resampled depths, view-dependent colour kept; approximates sample placement only, RES^3 x 4 bytes of '
+                             'device memory (not in the reference; not with --baked, --labels_only or --geometry)')
     add_geometry_arguments(parser)
     return parser
+
+
+def parse_options(argv=None):
+    """the parsed arguments, with the combinations no route serves refused by the parser"""
+    parser = build_parser()
+    opt = parser.parse_args(argv)
+    if opt.labels_only and (opt.baked is not None or opt.geometry):
+        parser.error("--labels_only takes neither --baked nor --geometry")
+    if opt.proposal is not None and (opt.baked is not None or opt.labels_only or opt.geometry):
+        parser.error("--proposal places the samples of the exact colour render; it takes none of --baked, --labels_only, --geometry")
+    return opt
 
 
 def add_geometry_arguments(parser):
@@ -69,7 +84,7 @@ def resolve_curriculum(name):
 def main(argv=None):
     from fenerf_amd import host
     host.respect_cpu_quota()          # torch's CPU thread pool no larger than the cores this process is granted (fenerf_amd/host.py)
-    opt = build_parser().parse_args(argv)
+    opt = parse_options(argv)
     import torch
     from fenerf_amd import callers, imageio_lite
     if not torch.cuda.is_available():
@@ -78,8 +93,6 @@ def main(argv=None):
     curriculum = resolve_curriculum(opt.curriculum)
     os.makedirs(opt.output_dir, exist_ok=True)
     generator = callers.load_generator(opt.path, device, use_ema=not opt.no_ema)
-    if opt.labels_only and (opt.baked is not None or opt.geometry):
-        raise SystemExit("--labels_only takes neither --baked nor --geometry")
     for seed in opt.seeds:
         if opt.labels_only:
             segmaps, _ = callers.render_multiview(generator, curriculum, int(seed), device, image_size=opt.image_size,
@@ -91,7 +104,7 @@ def main(argv=None):
         images, segmaps, *views = callers.render_multiview(generator, curriculum, int(seed), device, image_size=opt.image_size,
                                                            ray_step_multiplier=opt.ray_step_multiplier,
                                                            lock_view_dependence=opt.lock_view_dependence, baked=opt.baked,
-                                                           geometry=geometry_options(opt))
+                                                           geometry=geometry_options(opt), proposal=opt.proposal)
         imageio_lite.save_image(images, os.path.join(opt.output_dir, f'grid_{seed}_RGB.png'), normalize=True, value_range=(-1, 1))
         imageio_lite.save_image(segmaps, os.path.join(opt.output_dir, f'grid_{seed}_SEG.png'))
         if views:
