@@ -107,6 +107,11 @@ _SIGS = {
     "fenerf_siren_forward_pointwise": (_i, [_vp, _i, _i64] + [_vp] * 9),
     "fenerf_siren_forward_rays": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i] + [_vp] * 7),
     "fenerf_ray_setup": (_i, [_i, _i, _i, C.c_float, C.c_float, C.c_float] + [_vp] * 9),
+    # free camera (fenerf_camera.hip): rays of a window of a W x H grid from cam2world / intrinsics, and their gradients' 17 sums
+    "fenerf_camera_rays": (_i, [_i] * 8 + [_vp, _vp, C.c_float, C.c_float] + [_vp] * 5),
+    "fenerf_camera_grads": (_i, [_i] * 7 + [_vp] * 7 + [_sz, _vp]),
+    "fenerf_camera_grads_workspace_bytes": (_sz, [_i, _i]),
+    "fenerf_camera_grads_chain_length": (_i, [_i]),
     "fenerf_siren_time_rays": (_i, [_vp, _i, _i, _i] + [_vp] * 9 + [_i, C.POINTER(C.c_float), _vp]),
     "fenerf_local_model_create": (_i, [C.POINTER(FenerfModelDesc), C.POINTER(FenerfLocalMapDesc), C.POINTER(_vp)]),
     "fenerf_local_model_destroy": (None, [_vp]),

@@ -91,6 +91,10 @@ def load_generator(path, device, use_ema=True, reset_render_options=True):
     return generator
 
 
+# what a Camera replaces in a kwargs bag written for the angle camera
+_ANGLE_CAMERA_KEYS = ("img_size", "fov", "h_mean", "v_mean", "h_stddev", "v_stddev", "sample_dist")
+
+
 def _latent_dims(generator, default=256):
     """(z_geo_dim, z_app_dim): the reference hard-codes 256 (render_multiview...:79-80); read from the module when it says otherwise."""
     return int(getattr(generator, "z_geo_dim", default)), int(getattr(generator, "z_app_dim", default))
@@ -98,7 +102,7 @@ def _latent_dims(generator, default=256):
 
 def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.25, 0.0, 0.25, 0.5), image_size=256,
                      ray_step_multiplier=2, lock_view_dependence=False, z_dim=None, latents=None, baked=None, geometry=False, labels_only=False,
-                     proposal=None):
+                     proposal=None, cameras=None):
     """Five yaw angles of one identity (render_multiview_images_double_semantic.py:66-85).
     -> (images [V,3,S,S] in [-1,1], segmaps [V,3,S,S] in [0,1]) on the CPU.
     geometry: True, or a dict of render_geometry's options (light, ambient, background, alpha_min, space) -- every view goes through
@@ -110,8 +114,15 @@ def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.
     serves it) -> (segmaps [V,3,S,S] in [0,1] -- the default call's, bit for bit --, depth maps [V,S,S]); not with baked or geometry.
     proposal: a lattice resolution -- the identity's DENSITY is baked once (bake_density) and every view places its samples from the
     lattice and evaluates the network there (DensityField.render: one SIREN pass, view-dependent colour kept).  Not
-    with baked, geometry or labels_only.  None = the exact renders."""
+    with baked, geometry or labels_only.  None = the exact renders.
+    cameras: a list of fenerf_amd.camera.Camera (one image each, frames of one size) -- the views are theirs instead of the five yaw angles
+    (generator.staged_forward_camera: roll, distance, a window of the image; image_size and face_angles are then not read).  The exact
+    colour renders only: not with baked, geometry, labels_only or proposal."""
     _refuse_proposal_with("render_multiview", proposal, baked=baked, geometry=geometry, labels_only=labels_only)
+    if cameras is not None and (baked is not None or geometry or labels_only or proposal is not None):
+        raise ValueError("render_multiview: cameras take the exact colour renders; none of baked, geometry, labels_only, proposal")
+    if cameras is not None and len(cameras) == 0:
+        raise ValueError("render_multiview: cameras is an empty list (None = the five yaw angles)")
     if labels_only and (baked is not None or geometry):
         raise ValueError("render_multiview: labels_only renders the exact semantic row; it takes neither baked nor geometry")
     kw = multiview_kwargs(curriculum, image_size, ray_step_multiplier, lock_view_dependence)
@@ -120,14 +131,20 @@ def render_multiview(generator, curriculum, seed, device, face_angles=(-0.5, -0.
     images, segmaps, normals, shadeds, depths = [], [], [], [], []
     geo = dict(geometry) if isinstance(geometry, dict) else {}
     field = None
-    for a in face_angles:
-        kw["h_mean"] = a + h_mean
+    for a in (face_angles if cameras is None else cameras):
+        if cameras is None:
+            kw["h_mean"] = a + h_mean
         torch.manual_seed(seed)
         z_geo = torch.randn((1, zg_dim), device=device)
         z_app = torch.randn((1, za_dim), device=device)
         if latents is not None:
             z_geo, z_app = (torch.as_tensor(t, dtype=torch.float32, device=device) for t in latents)
         with torch.no_grad():
+            if cameras is not None:
+                img, _ = generator.staged_forward_camera(z_geo, z_app, a, **{k: v for k, v in kw.items() if k not in _ANGLE_CAMERA_KEYS})
+                images.append(img[:, -3:])
+                segmaps.append(mask2color(img[:, :-3], device, scale=255.0))
+                continue
             if labels_only:
                 seg, depth = generator.staged_geometry(z_geo, z_app, **kw)
                 segmaps.append(mask2color(seg, device, scale=255.0))
@@ -898,7 +915,7 @@ def render_inversion_recon(generator, meta, render_options, trajectory, max_batc
 def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_psi=0.0, lambda_seg=1.0, lambda_img=1.0,
                    lambda_percept=0.0, lambda_norm=0.0, percept=None, z_dim=256, lr=1e-2, on_step=None, latent_noise=0.03,
                    n_mean_latents=10000, record_offsets=False, optimize_pose=False, lr_pose=None, init_pose=None, gt_depth=None, depth_mask=None,
-                   lambda_depth=0.0):
+                   lambda_depth=0.0, pose_model="angles", optimize_focal=False):
     """GAN inversion in FiLM space (inverse_render_double_semantic.py:306-410): optimise additive offsets on the geometry /
     appearance frequencies and phase shifts with Adam (lr 1e-2, weight_decay 1e-4, StepLR(100, 0.75)) under annealed
     latent noise so that generator.forward_with_frequencies reproduces gt_image [1,3,S,S] and gt_seg [1,18,S,S] (both in
@@ -916,7 +933,19 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
     gt_depth [1,S,S] (an RGB-D capture, a second view's geometry; depth_mask [1,S,S] or None = every pixel) with lambda_depth > 0 adds
     lambda_depth * mean(mask * |depth - gt_depth|) on the render's depth map, which then carries the graph
     (forward_with_frequencies(return_depth=True)); the result gains `depth_losses`, the unweighted term per iteration.  With the defaults
-    the loop is what it was: no return_depth, the same launches."""
+    the loop is what it was: no return_depth, the same launches.
+    pose_model (with optimize_pose): "angles" -- the two angles above, the default -- or "se3": a free camera (fenerf_amd.camera) around
+    the options' pose, Camera.from_angles(yaw, pitch, fov).perturbed(rotvec, shift, log_focal) with rotvec / shift [1,3] (and log_focal [1]
+    with optimize_focal) starting at zero in the pose Adam group: roll, distance and translation (and focal length) move too.  Every
+    iteration renders through generator.forward_camera_with_frequencies; the draws are the angle route's.  The result and on_step's dict
+    then carry `cam2world` [1,3,4] / `intrinsics` [1,5] (detached), and `yaw` / `pitch` report the pose the camera started from."""
+    if pose_model not in ("angles", "se3"):
+        raise ValueError(f"inverse_render: pose_model {pose_model!r} (angles | se3)")
+    if pose_model == "se3" and not optimize_pose:
+        raise ValueError("inverse_render: pose_model='se3' is a model of the optimised pose; set optimize_pose=True")
+    if optimize_focal and pose_model != "se3":
+        raise ValueError("inverse_render: optimize_focal needs pose_model='se3' (the angle camera has one fixed fov)")
+    se3 = optimize_pose and pose_model == "se3"
     device = generator.device
     siren = generator.siren
     draws = generator.draws
@@ -941,12 +970,31 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
     else:
         opt_params = [o_gf, o_gp, o_af, o_ap]
     yaw, pitch = options.get("h_mean"), options.get("v_mean")
-    if optimize_pose:
+    base_camera = pose_params = None
+    if se3:
+        from .camera import Camera
+        if init_pose is not None:
+            yaw, pitch = init_pose
+        S = options["img_size"]
+        with torch.no_grad():
+            base_camera = Camera.from_angles(yaw, pitch, options["fov"], (S, S), device=device)
+        rotvec, shift = (torch.zeros((1, 3), device=device).requires_grad_() for _ in range(2))
+        log_focal = torch.zeros((1,), device=device).requires_grad_() if optimize_focal else None
+        pose_params = [rotvec, shift] + ([log_focal] if optimize_focal else [])
+        camera_options = {k: v for k, v in options.items() if k not in _ANGLE_CAMERA_KEYS}
+        opt_params = [dict(params=opt_params), dict(params=pose_params, lr=lr if lr_pose is None else lr_pose, weight_decay=0.0)]
+    elif optimize_pose:
         leaf = lambda v: torch.as_tensor(v, dtype=torch.float32).detach().to(device).reshape(()).clone().requires_grad_()
         yaw, pitch = leaf(yaw if init_pose is None else init_pose[0]), leaf(pitch if init_pose is None else init_pose[1])
         options = dict(options, h_mean=yaw, v_mean=pitch)
         opt_params = [dict(params=opt_params), dict(params=[yaw, pitch], lr=lr if lr_pose is None else lr_pose, weight_decay=0.0)]
-    pose_now = lambda: dict(yaw=yaw.detach().clone() if optimize_pose else yaw, pitch=pitch.detach().clone() if optimize_pose else pitch)
+    pose_now = lambda: dict(yaw=yaw.detach().clone() if optimize_pose and not se3 else yaw,
+                            pitch=pitch.detach().clone() if optimize_pose and not se3 else pitch)
+
+    def camera_now():
+        with torch.no_grad():
+            c = base_camera.perturbed(rotvec, shift, log_focal)
+        return dict(cam2world=c.cam2world.clone(), intrinsics=c.intrinsics.clone())
     optimizer = torch.optim.Adam(opt_params, lr=lr, weight_decay=1e-4)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, 100, gamma=0.75)
     mse = torch.nn.MSELoss(reduction="mean")
@@ -960,7 +1008,12 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
         # draw order and arithmetic of the reference (:381-384): geo freq, geo phase, app freq, app phase; (0.03 * randn) * k
         n_gf, n_gp = latent_noise * draws.randn(tuple(w_gf.shape), device) * k, latent_noise * draws.randn(tuple(w_gp.shape), device) * k
         n_af, n_ap = latent_noise * draws.randn(tuple(w_af.shape), device) * k, latent_noise * draws.randn(tuple(w_ap.shape), device) * k
-        if use_depth:
+        if se3:
+            out = generator.forward_camera_with_frequencies(w_gf + n_gf + o_gf, w_af + n_af + o_af, w_gp + n_gp + o_gp, w_ap + n_ap + o_ap,
+                                                            base_camera.perturbed(rotvec, shift, log_focal), return_depth=use_depth,
+                                                            **camera_options)
+            frame, depth = out[0], (out[2] if use_depth else None)
+        elif use_depth:
             frame, _, depth = generator.forward_with_frequencies(w_gf + n_gf + o_gf, w_af + n_af + o_af, w_gp + n_gp + o_gp, w_ap + n_ap + o_ap,
                                                                  return_depth=True, **options)
         else:
@@ -988,12 +1041,15 @@ def inverse_render(generator, gt_image, gt_seg, options, n_iterations=700, init_
         if on_step is not None:      # (i, loss, the reference's checkpoint dict at this iteration: what its in-loop preview renders use, :419-452)
             on_step(i, losses[-1], dict(w_geo_frequencies=w_gf, w_geo_phase_shifts=w_gp, w_app_frequencies=w_af, w_app_phase_shifts=w_ap,
                                         w_geo_frequency_offsets=o_gf.detach(), w_geo_phase_shift_offsets=o_gp.detach(),
-                                        w_app_frequency_offsets=o_af.detach(), w_app_phase_shift_offsets=o_ap.detach(), **pose_now()))
+                                        w_app_frequency_offsets=o_af.detach(), w_app_phase_shift_offsets=o_ap.detach(), **pose_now(),
+                                        **(camera_now() if se3 else {})))
     if losses and on_step is None:
         losses = torch.stack(losses).cpu().tolist()
     extra = dict(offset_history=history) if record_offsets else {}
     if use_depth:
         extra["depth_losses"] = torch.stack(depth_losses).cpu().tolist() if depth_losses else []
+    if se3:
+        extra.update(camera_now())
     return dict(**extra, w_geo_frequencies=w_gf, w_geo_phase_shifts=w_gp, w_app_frequencies=w_af, w_app_phase_shifts=w_ap,
                 w_geo_frequency_offsets=o_gf.detach(), w_geo_phase_shift_offsets=o_gp.detach(),
                 w_app_frequency_offsets=o_af.detach(), w_app_phase_shift_offsets=o_ap.detach(), losses=losses,

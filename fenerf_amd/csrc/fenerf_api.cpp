@@ -726,6 +726,52 @@ extern "C" int fenerf_ray_setup(int B, int img_size, int N, float z_cam, float r
   { PhaseScope ph(PH_RAY_SETUP, stream); return launch_ray_setup(B, img_size, N, z_cam, ray_start, ray_end, u_jitter, theta, phi, origins, dirs, z, pitch, yaw, stream); }
 }
 
+// the window [x0, x0 + w) x [y0, y0 + h) of a W x H pixel grid, for B images
+static int check_camera_window(const char* who, int B, int W, int H, int x0, int y0, int w, int h) {
+  const std::string name(who);
+  if (B < 1) return fail(FENERF_E_INVALID, name + ": need B >= 1");
+  if (W < 1 || H < 1) return fail(FENERF_E_INVALID, name + ": need a pixel grid of W, H >= 1");
+  if (w < 0 || h < 0 || x0 < 0 || y0 < 0 || (long long)x0 + w > W || (long long)y0 + h > H)
+    return fail(FENERF_E_INVALID, name + ": the window [" + std::to_string(x0) + ", " + std::to_string((long long)x0 + w) + ") x [" + std::to_string(y0) +
+                                  ", " + std::to_string((long long)y0 + h) + ") lies outside the " + std::to_string(W) + " x " + std::to_string(H) + " grid");
+  if (w == 0 || h == 0) return fail(FENERF_E_INVALID, name + ": the window holds no pixel (w * h == 0)");
+  // one thread per ray in a one-dimensional grid of 256-thread workgroups, ray indices held in int within an image
+  if ((long long)B * w * h > 0x7fffffffLL) return fail(FENERF_E_INVALID, name + ": B * w * h is more than 2^31 - 1 rays");
+  return FENERF_OK;
+}
+
+extern "C" int fenerf_camera_rays(int B, int W, int H, int x0, int y0, int w, int h, int N, const float* cam2world, const float* intrinsics,
+                                  float ray_start, float ray_end, const float* u_jitter, float* origins, float* dirs, float* z, void* stream) {
+  int rc = check_camera_window("fenerf_camera_rays", B, W, H, x0, y0, w, h);
+  if (rc) return rc;
+  if (N < 1) return fail(FENERF_E_INVALID, "fenerf_camera_rays: need N >= 1");
+  if (!cam2world || !intrinsics || !u_jitter || !origins || !dirs || !z) return fail(FENERF_E_INVALID, "fenerf_camera_rays: NULL pointer");
+  PhaseScope ph(PH_RAY_SETUP, stream);
+  return launch_camera_rays(B, W, H, x0, y0, w, h, N, cam2world, intrinsics, ray_start, ray_end, u_jitter, origins, dirs, z, stream);
+}
+
+extern "C" size_t fenerf_camera_grads_workspace_bytes(int B, int R) {
+  if (B < 1 || R < 1) return 0;
+  return (size_t)B * camera_grads_groups(R) * 17 * sizeof(float);
+}
+
+extern "C" int fenerf_camera_grads_chain_length(int R) { return R < 1 ? 0 : camera_grads_chain_length(R); }
+
+extern "C" int fenerf_camera_grads(int B, int W, int H, int x0, int y0, int w, int h, const float* cam2world, const float* intrinsics,
+                                   const float* d_origins, const float* d_dirs, float* d_cam2world, float* d_intrinsics, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  int rc = check_camera_window("fenerf_camera_grads", B, W, H, x0, y0, w, h);
+  if (rc) return rc;
+  if (B > 65535) return fail(FENERF_E_INVALID, "fenerf_camera_grads: need B <= 65535 (one grid row per image)");
+  if (!cam2world || !intrinsics || !d_cam2world || !d_intrinsics) return fail(FENERF_E_INVALID, "fenerf_camera_grads: NULL pointer");
+  const size_t need = fenerf_camera_grads_workspace_bytes(B, w * h);
+  if (!workspace || workspace_bytes < need)
+    return fail(FENERF_E_INVALID, "fenerf_camera_grads: workspace of " + std::to_string(workspace_bytes) + " bytes, need " + std::to_string(need) +
+                                  " (fenerf_camera_grads_workspace_bytes)");
+  PhaseScope ph(PH_OTHER, stream);
+  return launch_camera_grads(B, W, H, x0, y0, w, h, cam2world, intrinsics, d_origins, d_dirs, d_cam2world, d_intrinsics, (float*)workspace, stream);
+}
+
 extern "C" int fenerf_composite(int64_t BR, int M, int C, const float* rgb_sigma, const float* z, const float* noise,
                                 const FenerfCompositeOpts* opts, float* out_rgb, float* out_depth, float* out_weights,
                                 float* out_wsum, void* stream) {

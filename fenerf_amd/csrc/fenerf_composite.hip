@@ -10,6 +10,7 @@
 
 #include "fenerf_composite_ray.h"
 #include "fenerf_internal.h"
+#include "fenerf_raymath.h"
 
 namespace fenerf {
 
@@ -346,25 +347,7 @@ __global__ __launch_bounds__(256) void resample_kernel(long long BR, int K, int 
 // (volumetric_rendering.py:109-168, :220-248) in one launch instead of ~40 tiny ATen ops.
 // One thread per ray; the per-image camera basis is recomputed per thread (a few dozen flops).
 // ------------------------------------------------------------------------------------------------
-// torch.linspace kernel: step = (end-start)/(steps-1); i < steps/2 ? start + step*i : end - step*(steps-1-i).
-// FUSED: each of the two as ONE fused multiply-add, a single rounding -- what torch's builds contract them into (x86 with AVX2 / AVX-512).
-// The sample depths are FUSED: the depths the reference recorded (tests/golden, 24 samples) are those bits, and a separately rounded product
-// is one ulp off at sample 9 of every ray (at sample 5 of 12 in (0.1, 5)).
-// The pixel grid is NOT fused and so DIFFERS FROM TORCH, by one ulp at about half of its values (124 of linspace(-1, 1, 256)): torch fuses
-// it like the depths.  Known and left for a change of its own: the rays of the 128 x 128, 24 + 24 image move with it, and the flip
-// statistics that tests/test_gpu_parity.py pins on that image (test_resampling_flips_against_an_fp64_arbiter) have to be measured again.
-template <bool FUSED>
-__device__ __forceinline__ float torch_linspace(float start, float end, int steps, int i) {
-  if (steps == 1) return start;
-  const float step = __fdiv_rn(__fsub_rn(end, start), (float)(steps - 1));
-  if (FUSED) return i < steps / 2 ? __fmaf_rn(step, (float)i, start) : __fmaf_rn(-step, (float)(steps - 1 - i), end);
-  return i < steps / 2 ? __fadd_rn(start, __fmul_rn(step, (float)i)) : __fsub_rn(end, __fmul_rn(step, (float)(steps - 1 - i)));
-}
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
-  const float n = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
-  x = __fdiv_rn(x, n); y = __fdiv_rn(y, n); z = __fdiv_rn(z, n);
-}
-
+// (torch_linspace, normalize3 and the jittered depths: fenerf_raymath.h, shared with camera_rays_kernel)
 __global__ __launch_bounds__(256) void ray_setup_kernel(int B, int S, int N, float z_cam, float ray_start, float ray_end,
                                                         const float* __restrict__ u_jitter, const float* __restrict__ theta_in,
                                                         const float* __restrict__ phi_in, float* __restrict__ origins,
@@ -404,11 +387,7 @@ __global__ __launch_bounds__(256) void ray_setup_kernel(int B, int S, int N, flo
   dirs[idx * 3 + 0] = wx; dirs[idx * 3 + 1] = wy; dirs[idx * 3 + 2] = wz;
   origins[idx * 3 + 0] = ox; origins[idx * 3 + 1] = oy; origins[idx * 3 + 2] = oz;
   // stratified jitter (:133-139): z_k = linspace(start,end,N)[k] + (u - 0.5) * (z_1 - z_0)
-  const float step = N > 1 ? __fsub_rn(torch_linspace<true>(ray_start, ray_end, N, 1), torch_linspace<true>(ray_start, ray_end, N, 0)) : 0.f;
-  for (int k = 0; k < N; ++k) {
-    const float u = u_jitter[idx * N + k];
-    z_out[idx * N + k] = __fadd_rn(torch_linspace<true>(ray_start, ray_end, N, k), __fmul_rn(__fsub_rn(u, 0.5f), step));
-  }
+  jittered_depths(ray_start, ray_end, N, u_jitter + idx * N, z_out + idx * N);
   if (r == 0) { pitch[b] = phi; yaw[b] = theta; }
 }
 

@@ -243,6 +243,14 @@ int launch_sample_pdf(long long BR, int K, int NS, const float* bins, const floa
 int launch_ray_setup(int B, int S, int N, float z_cam, float ray_start, float ray_end, const float* u_jitter,
                      const float* theta, const float* phi, float* origins, float* dirs, float* z, float* pitch, float* yaw,
                      void* stream);
+// fenerf_camera.hip: rays of a window of a W x H grid from cam2world [B][3][4] / intrinsics [B][5], and the 17 gradient sums per image
+// (partial: B * camera_grads_groups(w * h) * 17 floats; either of d_origins / d_dirs may be nullptr)
+int launch_camera_rays(int B, int W, int H, int x0, int y0, int w, int h, int N, const float* cam2world, const float* intrinsics,
+                       float ray_start, float ray_end, const float* u_jitter, float* origins, float* dirs, float* z, void* stream);
+int camera_grads_groups(long long R);
+int camera_grads_chain_length(long long R);
+int launch_camera_grads(int B, int W, int H, int x0, int y0, int w, int h, const float* cam2world, const float* intrinsics,
+                        const float* d_origins, const float* d_dirs, float* d_cam2world, float* d_intrinsics, float* partial, void* stream);
 // fenerf_render_grad.hip: the small kernels of fenerf_render_forward_save / fenerf_render_backward
 #define FENERF_MULTI_ADD_MAX 64
 struct MultiAdd { float* dst[FENERF_MULTI_ADD_MAX]; const float* src[FENERF_MULTI_ADD_MAX]; long long n[FENERF_MULTI_ADD_MAX]; int count; };

@@ -93,21 +93,29 @@ class _Generator3dBase(nn.Module):
         return super().train(mode)
 
     def _render(self, film, img_size, fov, ray_start, ray_end, num_steps, h_stddev, v_stddev, h_mean, v_mean,
-                hierarchical_sample, sample_dist, lock_view_dependence, kwargs, use_fill, third, field_render=None, rays_out=None):
+                hierarchical_sample, sample_dist, lock_view_dependence, kwargs, use_fill, third, field_render=None, rays_out=None, camera=None):
         """film = (freq_geo, phase_geo, freq_app, phase_app) raw mapping outputs.
         third: None | 'weights' | 'auto' (what fancy_integration would have returned third for this fill_mode) | 'wsum' (the weight sum
         whatever the fill_mode).
         field_render: a callable with NativeModel.render's signature that stands in for it (callers.BakedField: lookups in a baked lattice
         instead of the two SIREN passes); rays, draws, options and everything behind the call are the same.
         rays_out: a dict that receives the render's `origins` / `dirs` [B,R,3] and `wsum` [B,R] or None (callers.render_geometry).
+        camera: a fenerf_amd.camera.Camera whose rays stand in for sample_rays' (the jitter is drawn, no angles are; img_size, fov and
+        the four angle arguments are not read; pitch and yaw come back as None).
         Returns (pixels [B,R,C'], depth [B,R], third tensor or None, pitch, yaw)."""
         B = film[0].shape[0]
         dev = self.device
-        R, N = img_size * img_size, num_steps
+        N = num_steps
         d = self.draws
-        # draw order: jitter rand [B,R,N,1] -> theta randn [B,1] -> phi randn [B,1]   (volumetric_rendering.py:135,193-194)
-        origins, dirs, z_vals, pitch, yaw = sample_rays(B, N, dev, fov, (img_size, img_size), ray_start, ray_end, h_stddev,
-                                                        v_stddev, h_mean, v_mean, sample_dist, draws=d)
+        if camera is not None:
+            R = camera.frame[0] * camera.frame[1]
+            origins, dirs, z_vals = self._camera_rays(camera, B, N, ray_start, ray_end)
+            pitch = yaw = None
+        else:
+            R = img_size * img_size
+            # draw order: jitter rand [B,R,N,1] -> theta randn [B,1] -> phi randn [B,1]   (volumetric_rendering.py:135,193-194)
+            origins, dirs, z_vals, pitch, yaw = sample_rays(B, N, dev, fov, (img_size, img_size), ray_start, ray_end, h_stddev,
+                                                            v_stddev, h_mean, v_mean, sample_dist, draws=d)
         noise_std = kwargs["nerf_noise"]
         clamp_mode = kwargs["clamp_mode"]
         opts = _lib.composite_opts(clamp_mode, noise_std, kwargs.get("last_back", False), kwargs.get("white_back", False),
@@ -289,6 +297,55 @@ class _Generator3dBase(nn.Module):
                                              depth_grad=depth_grad)         # (refuses a differentiable depth)
         node = HierarchicalRenderDepthFunction if depth_grad else HierarchicalRenderFunction
         return node.apply(self.siren, opts, copts, bool(lock_view_dependence), origins, dirs, z_c, u, nc_, nf_, fg, pg, fa, pa, *params)
+
+    # ---- free camera (fenerf_amd.camera.Camera): the rays come from the camera, everything behind them is what it is above ----------
+    def _camera_rays(self, camera, B, N, ray_start, ray_end):
+        if camera.batch != B:
+            raise ValueError(f"camera of {camera.batch} image(s) for FiLM parameters of {B}")
+        if torch.device(camera.cam2world.device) != torch.device(self.device):
+            camera = camera.to(self.device)
+        origins, dirs, z = camera.rays(N, ray_start, ray_end, self.draws)       # the one draw: jitter rand [B,R,N,1]
+        return origins, dirs, z.reshape(B, -1, N)
+
+    def _finish_frame(self, pixels, batch_size, frame):
+        """_finish_scaled for a w x h frame: [B, h w, C'] -> [B, C', h, w] * 2 - 1 (the image-epilogue launch for a square one)"""
+        w, h = frame
+        if w == h:
+            return self._finish_scaled(pixels, batch_size, w)
+        if self.softmax_label:
+            pixels = torch.cat([torch.nn.Softmax(dim=-1)(pixels[..., :-3]), pixels[..., -3:]], dim=-1)
+        return pixels.reshape((batch_size, h, w, -1)).permute(0, 3, 1, 2).contiguous() * 2 - 1
+
+    def _camera_frame(self, film, camera, ray_start, ray_end, num_steps, hierarchical_sample, lock_view_dependence, return_depth, rays_out,
+                      kwargs):
+        """forward / forward_with_frequencies with a Camera in place of (img_size, fov, the four angle arguments): draws in the order
+        of _render / _render_grad without the two angle draws (jitter, then _render_rays'), the same kernels behind the rays.
+        -> (pixels [B,C-1,h,w] in [-1,1], camera.cam2world) or, with return_depth, (pixels, camera.cam2world, depth [B,h,w]).
+        A camera that requires grad makes the render differentiable as an h_mean tensor does: the dense one-node render, fp32 dump.
+        rays_out: a dict that receives the `origins` / `dirs` tensors of the graph."""
+        B = film[0].shape[0]
+        origins, dirs, z_c = self._camera_rays(camera, B, num_steps, ray_start, ray_end)
+        if rays_out is not None:
+            rays_out.update(origins=origins, dirs=dirs)
+        rgb, depth = self._render_rays(film, origins, dirs, z_c, hierarchical_sample, lock_view_dependence, kwargs,
+                                       self._wants_grad(film, origins, dirs), depth_grad=return_depth)
+        w, h = camera.frame
+        pixels = self._finish_frame(rgb, B, camera.frame)
+        if not return_depth:
+            return pixels, camera.cam2world
+        return pixels, camera.cam2world, depth.reshape(B, h, w)
+
+    def _staged_camera(self, film, camera, ray_start, ray_end, num_steps, hierarchical_sample, lock_view_dependence, kwargs, third):
+        """the render of a staged_forward (fill modes honoured) through a Camera -> (pixels [B,C',h,w] * 2 - 1 on the device, depth map
+        [B,h,w] on the CPU, `third` as _render returns it)"""
+        B = film[0].shape[0]
+        w, h = camera.frame
+        pixels, depth, t, _, _ = self._render(film, None, None, ray_start, ray_end, num_steps, None, None, None, None, hierarchical_sample,
+                                              None, lock_view_dependence, kwargs, use_fill=True, third=third, camera=camera.detach())
+        depth_map = native.to_host(depth.reshape(B, h, w).contiguous())
+        if t is not None:
+            t = native.to_host(t.reshape((B, h, w, -1)).permute(0, 3, 1, 2).contiguous() * 2 - 1)
+        return self._finish_frame(pixels, B, camera.frame), depth_map, t
 
     @staticmethod
     def _outputs(pixels, poses, depth, img_size, return_depth):
@@ -527,6 +584,47 @@ class DoubleImplicitGenerator3d(_Generator3dBase):
         return self._outputs(pixels, torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
 
 
+    # ---- the same four entries with a Camera (fenerf_amd.camera) in place of img_size, fov and the angle arguments ----
+    def forward_camera(self, z_geo, z_app, camera, ray_start, ray_end, num_steps, hierarchical_sample, lock_view_dependence=False,
+                       return_depth=False, rays_out=None, **kwargs):
+        """forward through `camera` -> (pixels [B, output_dim-1, h, w] in [-1,1], camera.cam2world[, depth [B,h,w]])"""
+        fg, pg = self.siren.geo_mapping_network(z_geo)
+        fa, pa = self.siren.app_mapping_network(z_app)
+        return self._camera_frame((fg, pg, fa, pa), camera, ray_start, ray_end, num_steps, hierarchical_sample, lock_view_dependence,
+                                  return_depth, rays_out, kwargs)
+
+    def forward_camera_with_frequencies(self, frequencies_geo, frequencies_app, phase_shifts_geo, phase_shifts_app, camera, ray_start, ray_end,
+                                        num_steps, hierarchical_sample, lock_view_dependence=False, return_depth=False, rays_out=None, **kwargs):
+        """forward_with_frequencies through `camera`"""
+        return self._camera_frame((frequencies_geo, phase_shifts_geo, frequencies_app, phase_shifts_app), camera, ray_start, ray_end, num_steps,
+                                  hierarchical_sample, lock_view_dependence, return_depth, rays_out, kwargs)
+
+    def staged_forward_camera(self, z_geo, z_app, camera, ray_start, ray_end, num_steps, psi=1, lock_view_dependence=False,
+                              max_batch_size=50000, hierarchical_sample=False, **kwargs):
+        """staged_forward through `camera` -> (pixels.cpu() [B,C',h,w], depth_map.cpu() [B,h,w])"""
+        self.generate_avg_frequencies()
+        with torch.no_grad():
+            raw_fg, raw_pg = self.siren.geo_mapping_network(z_geo)
+            raw_fa, raw_pa = self.siren.app_mapping_network(z_app)
+            fg = self.avg_frequencies_geo + psi * (raw_fg - self.avg_frequencies_geo)
+            pg = self.avg_phase_shifts_geo + psi * (raw_pg - self.avg_phase_shifts_geo)
+            fa = self.avg_frequencies_app + psi * (raw_fa - self.avg_frequencies_app)
+            pa = self.avg_phase_shifts_app + psi * (raw_pa - self.avg_phase_shifts_app)
+            pixels, depth_map, _ = self._staged_camera((fg, pg, fa, pa), camera, ray_start, ray_end, num_steps, hierarchical_sample,
+                                                       lock_view_dependence, kwargs, third=None)
+            return native.to_host(pixels), depth_map
+
+    def staged_forward_camera_with_frequencies(self, truncated_frequencies_geo, truncated_frequencies_app, truncated_phase_shifts_geo,
+                                               truncated_phase_shifts_app, camera, ray_start, ray_end, num_steps, psi=0.7,
+                                               lock_view_dependence=False, max_batch_size=50000, hierarchical_sample=False, **kwargs):
+        """staged_forward_with_frequencies through `camera` -> (pixels.cpu(), depth.cpu(), third.cpu() * 2 - 1)"""
+        with torch.no_grad():
+            pixels, depth_map, third = self._staged_camera(
+                (truncated_frequencies_geo, truncated_phase_shifts_geo, truncated_frequencies_app, truncated_phase_shifts_app), camera,
+                ray_start, ray_end, num_steps, hierarchical_sample, lock_view_dependence, kwargs, third="auto")
+            return native.to_host(pixels), depth_map, third
+
+
 class ImplicitGenerator3d(_Generator3dBase):
     """Single-latent pi-GAN generator (generators.py:13-431), used with SPATIALSIRENBASELINE (curriculum `CelebA`)."""
 
@@ -661,6 +759,36 @@ class ImplicitGenerator3d(_Generator3dBase):
         return self._outputs(pixels, torch.cat([pitch, yaw], -1), depth, img_size, return_depth)
 
 
+    # ---- the same four entries with a Camera (fenerf_amd.camera) in place of img_size, fov and the angle arguments ----
+    def forward_camera(self, z, camera, ray_start, ray_end, num_steps, hierarchical_sample, lock_view_dependence=False, return_depth=False,
+                       rays_out=None, **kwargs):
+        """forward through `camera` -> (pixels [B,3,h,w], camera.cam2world[, depth [B,h,w]])"""
+        frequencies, phase_shifts = self.siren.mapping_network(z)
+        return self._camera_frame(self._film(frequencies, phase_shifts), camera, ray_start, ray_end, num_steps, hierarchical_sample,
+                                  lock_view_dependence, return_depth, rays_out, kwargs)
+
+    def forward_camera_with_frequencies(self, frequencies, phase_shifts, camera, ray_start, ray_end, num_steps, hierarchical_sample,
+                                        lock_view_dependence=False, return_depth=False, rays_out=None, **kwargs):
+        """forward_with_frequencies through `camera`"""
+        return self._camera_frame(self._film(frequencies, phase_shifts), camera, ray_start, ray_end, num_steps, hierarchical_sample,
+                                  lock_view_dependence, return_depth, rays_out, kwargs)
+
+    def staged_forward_camera(self, z, camera, ray_start, ray_end, num_steps, psi=1, lock_view_dependence=False, max_batch_size=50000,
+                              hierarchical_sample=False, **kwargs):
+        """staged_forward through `camera` -> (pixels (device), depth_map.cpu(), weights_sum.cpu() * 2 - 1)"""
+        with torch.no_grad():
+            f, p = self._staged_film(z, psi)
+            return self._staged_camera(self._film(f, p), camera, ray_start, ray_end, num_steps, hierarchical_sample, lock_view_dependence,
+                                       kwargs, third="auto")
+
+    def staged_forward_camera_with_frequencies(self, truncated_frequencies, truncated_phase_shifts, camera, ray_start, ray_end, num_steps,
+                                               psi=0.7, lock_view_dependence=False, max_batch_size=50000, hierarchical_sample=False, **kwargs):
+        """staged_forward_with_frequencies through `camera` -> (pixels (device), depth_map.cpu())"""
+        with torch.no_grad():
+            return self._staged_camera(self._film(truncated_frequencies, truncated_phase_shifts), camera, ray_start, ray_end, num_steps,
+                                       hierarchical_sample, lock_view_dependence, kwargs, third=None)[:2]
+
+
 class StyleGenerator3d(ImplicitGenerator3d):
     """The reference's third generator class (generators.py:914-1294; no curriculum or script of the reference instantiates it): a copy
     of ImplicitGenerator3d WITHOUT average frequencies -- `set_device` draws no 10,000 latents, `staged_forward` evaluates
@@ -685,6 +813,14 @@ class StyleGenerator3d(ImplicitGenerator3d):
     def staged_forward_with_frequencies(self, truncated_frequencies, truncated_phase_shifts, *args, **kwargs):
         kwargs.pop("fill_color", None)
         return super().staged_forward_with_frequencies(truncated_frequencies, truncated_phase_shifts, *args, **kwargs)
+
+    def staged_forward_camera(self, z, *args, **kwargs):
+        kwargs.pop("fill_color", None)
+        return super().staged_forward_camera(z, *args, **kwargs)
+
+    def staged_forward_camera_with_frequencies(self, truncated_frequencies, truncated_phase_shifts, *args, **kwargs):
+        kwargs.pop("fill_color", None)
+        return super().staged_forward_camera_with_frequencies(truncated_frequencies, truncated_phase_shifts, *args, **kwargs)
 
     def staged_geometry(self, z, *args, **kwargs):
         kwargs.pop("fill_color", None)

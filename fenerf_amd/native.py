@@ -1372,6 +1372,58 @@ def ray_setup(B, img_size, N, z_cam, ray_start, ray_end, u_jitter, theta, phi):
     return origins, dirs, z, pitch, yaw
 
 
+def _camera_window(size, window):
+    W, H = (int(v) for v in size)
+    x0, y0, w, h = (0, 0, W, H) if window is None else (int(v) for v in window)
+    return W, H, x0, y0, w, h
+
+
+def camera_rays(cam2world, intrinsics, size, window, N, ray_start, ray_end, u_jitter):
+    """fenerf_camera_rays (include/fenerf.h): cam2world [B,3,4], intrinsics [B,5] = (kx, ky, cx, cy, zc), size = (W, H), window = (x0, y0,
+    w, h) or None (the full grid), u_jitter [B,w*h,N(,1)] device tensors -> (origins [B,R,3], dirs [B,R,3], z [B,R,N]), R = w * h, row-major
+    within the window."""
+    dev = u_jitter.device
+    W, H, x0, y0, w, h = _camera_window(size, window)
+    B, R = int(cam2world.shape[0]), w * h
+    M, K = _f32(cam2world, dev).reshape(B, 3, 4), _f32(intrinsics, dev).reshape(B, 5)
+    u = _f32(u_jitter, dev).reshape(B, R, N) if R > 0 and N > 0 else _f32(u_jitter, dev)
+    origins = torch.empty((B, R, 3), dtype=torch.float32, device=dev)
+    dirs = torch.empty((B, R, 3), dtype=torch.float32, device=dev)
+    z = torch.empty((B, R, max(N, 0)), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_camera_rays(B, W, H, x0, y0, w, h, N, _ptr(M), _ptr(K), float(ray_start), float(ray_end), _ptr(u),
+                                                 _ptr(origins), _ptr(dirs), _ptr(z), _stream()))
+    return origins, dirs, z
+
+
+def camera_grads_chain_length(R):
+    """L(R): the most additions one ray's term passes through in fenerf_camera_grads' sums over R rays (include/fenerf.h)"""
+    return int(_lib.lib().fenerf_camera_grads_chain_length(int(R)))
+
+
+def camera_grads(cam2world, intrinsics, size, window, d_origins, d_dirs, workspace=None):
+    """fenerf_camera_grads (include/fenerf.h): d_origins / d_dirs [B,R,3] (either None) of the rays camera_rays made for the same camera
+    -> (d_cam2world [B,3,4], d_intrinsics [B,5]); a fixed order of additions, no atomics.  workspace: a uint8 device tensor to use
+    instead of a fresh one of fenerf_camera_grads_workspace_bytes."""
+    dev = cam2world.device
+    W, H, x0, y0, w, h = _camera_window(size, window)
+    B, R = int(cam2world.shape[0]), w * h
+    M, K = _f32(cam2world, dev).reshape(B, 3, 4), _f32(intrinsics, dev).reshape(B, 5)
+    d_o = _f32(d_origins, dev) if d_origins is not None else None
+    d_d = _f32(d_dirs, dev) if d_dirs is not None else None
+    for t in (d_o, d_d):
+        if t is not None and t.numel() != B * R * 3:
+            raise ValueError(f"camera_grads: d_origins / d_dirs must hold [{B}, {R}, 3]")
+    d_M = torch.empty((B, 3, 4), dtype=torch.float32, device=dev)
+    d_K = torch.empty((B, 5), dtype=torch.float32, device=dev)
+    if workspace is None:
+        workspace = torch.empty((max(1, int(_lib.lib().fenerf_camera_grads_workspace_bytes(B, R))),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().fenerf_camera_grads(B, W, H, x0, y0, w, h, _ptr(M), _ptr(K), _ptr(d_o), _ptr(d_d), _ptr(d_M), _ptr(d_K),
+                                                  C.c_void_p(workspace.data_ptr()), workspace.numel(), _stream()))
+    return d_M, d_K
+
+
 def composite(rgb_sigma, z, noise, opts, want_weights=True, want_wsum=True):
     """fancy_integration on [..., M, C] / [..., M] device tensors -> (rgb, depth, weights, wsum)."""
     lead = rgb_sigma.shape[:-2]

@@ -392,6 +392,38 @@ int fenerf_ray_setup(int B, int img_size, int N, float z_cam, float ray_start, f
                      const float* theta, const float* phi, float* origins, float* dirs, float* z, float* pitch, float* yaw,
                      void* stream);
 
+/* Free camera.  replaces: nothing of the reference -- it has the one camera of fenerf_ray_setup (on the unit sphere, looking at the
+ * origin, world-up +y, square image, one fov; the pose hand-over of its inversion is commented out, inverse_render_double_semantic.py:
+ * 422-423).  Here: the rays of the window [x0, x0 + w) x [y0, y0 + h) of a W x H pixel grid, row-major within the window (R = w * h
+ * rays per image), from a camera-to-world matrix cam2world [B][3][4] (row-major; columns 0-2 the camera's right, up and backward axes --
+ * it looks along -z --, column 3 its position) and intrinsics [B][5] = (kx, ky, cx, cy, zc), both on the device.  For pixel (col, row)
+ * of the FULL grid, every operation rounded on its own:
+ *     X = linspace(-1, 1, W)[col], Y = linspace(1, -1, H)[row]        (the unfused grid of fenerf_ray_setup)
+ *     v = (kx (X - cx), ky (Y - cy), zc);  c = v / |v|
+ *     dirs[i] = (M[i][0] c.x + M[i][1] c.y) + M[i][2] c.z   (not normalised again);   origins[i] = M[i][3]
+ * and depths z [B][R][N] from u_jitter [B][R][N] exactly as fenerf_ray_setup makes them.  The reference's camera is intrinsics =
+ * (1, 1, 0, 0, -1 / tan(fov / 2)) with its look-at matrix: for those the three outputs are fenerf_ray_setup's bits.  A window's rays are
+ * the bits of those rays of the full grid.  FENERF_E_INVALID: a window outside the grid, w * h == 0, N < 1, a NULL pointer, more than
+ * 2^31 - 1 rays in all (B * w * h).  One launch, timed under the ray_setup phase.
+ *
+ * fenerf_camera_grads is its backward: d_origins / d_dirs [B][R][3] (either may be NULL) -> d_cam2world [B][3][4], d_intrinsics [B][5].
+ * Per ray, with n = |v|, g = M[:, :3]^T d_dirs and gv = (g - c (c . g)) / n:
+ *     d_M[i][j] = sum_r d_dirs[r][i] c_j (j < 3);   d_M[i][3] = sum_r d_origins[r][i]
+ *     d_kx = sum gv.x (X - cx);  d_cx = -sum gv.x kx;  d_ky, d_cy likewise;  d_zc = sum gv.z
+ * A NULL d_dirs leaves the rotation and intrinsics gradients zero, a NULL d_origins column 3.  The 17 sums are taken without atomics and
+ * in a fixed order (per-lane partial sums over a strided run of rays, the lanes of a wave, the waves of a workgroup in wave order, then
+ * -- in a second small launch -- the workgroups in index order): the same bits for every launch.  No term passes through more than
+ * fenerf_camera_grads_chain_length(R) additions: at most 35 up to R = 2^20.  workspace: fenerf_camera_grads_workspace_bytes(B, R) bytes
+ * (FENERF_E_INVALID for less; also for B > 65535).  Its two launches are one launch group timed under the "other" phase, as
+ * fenerf_ray_grads is. */
+int fenerf_camera_rays(int B, int W, int H, int x0, int y0, int w, int h, int N, const float* cam2world, const float* intrinsics,
+                       float ray_start, float ray_end, const float* u_jitter, float* origins, float* dirs, float* z, void* stream);
+int fenerf_camera_grads(int B, int W, int H, int x0, int y0, int w, int h, const float* cam2world, const float* intrinsics,
+                        const float* d_origins, const float* d_dirs, float* d_cam2world, float* d_intrinsics, void* workspace,
+                        size_t workspace_bytes, void* stream);
+size_t fenerf_camera_grads_workspace_bytes(int B, int R);
+int fenerf_camera_grads_chain_length(int R);
+
 /* Measurement hook (bench.py roofline leg; replaces nothing): runs the FiLM pre-pass once, then `iters` back-to-back
  * launches of ONLY the SIREN kernel of fenerf_siren_forward_rays, bracketed by hipEvents recorded on `stream`;
  * synchronises and returns the average kernel duration in milliseconds. */

@@ -81,6 +81,11 @@ def build_parser():
                         help="optimise the camera's yaw / pitch with the FiLM offsets (the reference assumes a frontal, externally estimated pose); "
                              "the recovered pose is saved with the checkpoint and centres the preview / recon renders")
     parser.add_argument('--lr_pose', type=float, default=None, help='learning rate of the yaw / pitch parameter group (default: the offsets\' 1e-2)')
+    parser.add_argument('--pose_model', choices=['angles', 'se3'], default='angles',
+                        help="--optimize_pose: 'angles' optimises yaw / pitch; 'se3' a free camera around the frontal pose (rotation vector and "
+                             "shift: roll, distance and translation move too); its cam2world / intrinsics are saved with the checkpoint, the "
+                             "preview / recon renders stay at the frontal pose")
+    parser.add_argument('--optimize_focal', action='store_true', help='--pose_model se3: optimise the log focal length as well')
     parser.add_argument('--depth_path', type=str, default=None,
                         help='FILE.npy: a depth map [image_size, image_size] (camera distance along the ray, the units of ray_start / ray_end) for '
                              'a depth term on the render\'s differentiable depth; non-finite or non-positive entries are masked out')
@@ -100,6 +105,10 @@ def parse_options(argv=None):
     opt = parser.parse_args(argv)
     if opt.proposal is not None and opt.baked is not None:
         parser.error("--proposal and --baked are two routes for the same frames: give one")
+    if opt.pose_model == 'se3' and not opt.optimize_pose:
+        parser.error("--pose_model se3 is a model of the optimised pose: give --optimize_pose")
+    if opt.optimize_focal and opt.pose_model != 'se3':
+        parser.error("--optimize_focal needs --pose_model se3")
     return opt
 
 
@@ -126,7 +135,7 @@ def run_inverse_render(opt, generator, img_path, seg_path, percept=None):
         gt_seg_19 = torch.nn.functional.interpolate(gt_seg_19, size=(opt.preview_size, opt.preview_size), mode="nearest")
 
     def on_step(i, loss, meta):
-        pose = (meta['yaw'], meta['pitch']) if opt.optimize_pose else None
+        pose = (meta['yaw'], meta['pitch']) if opt.optimize_pose and opt.pose_model == 'angles' else None
         if i % 200 == 0:
             for angle, img in callers.render_inversion_views(generator, meta, render_options, PREVIEW_ANGLES, opt.max_batch_size, opt.lock_view_dependence, pose=pose):
                 imageio_lite.save_image(img[:, -3:].cpu(), os.path.join(opt.save_dir, f"{i}_{angle}_img.jpg"), normalize=True)
@@ -146,17 +155,20 @@ def run_inverse_render(opt, generator, img_path, seg_path, percept=None):
                                  lambda_seg=opt.lambda_seg, lambda_img=opt.lambda_img, lambda_percept=opt.lambda_percept,
                                  lambda_norm=opt.lambda_norm if opt.latent_normalize else 0.0, percept=percept, z_dim=z_dim, on_step=on_step,
                                  optimize_pose=opt.optimize_pose, lr_pose=opt.lr_pose, gt_depth=gt_depth, depth_mask=depth_mask,
-                                 lambda_depth=opt.lambda_depth if gt_depth is not None else 0.0)
+                                 lambda_depth=opt.lambda_depth if gt_depth is not None else 0.0, pose_model=opt.pose_model,
+                                 optimize_focal=opt.optimize_focal)
     meta = {k: res[k] for k in ('w_geo_frequencies', 'w_geo_phase_shifts', 'w_geo_frequency_offsets', 'w_geo_phase_shift_offsets',
                                 'w_app_frequencies', 'w_app_phase_shifts', 'w_app_frequency_offsets', 'w_app_phase_shift_offsets')}
-    if opt.optimize_pose:
+    if opt.optimize_pose and opt.pose_model == 'se3':
+        meta.update(cam2world=res['cam2world'].cpu(), intrinsics=res['intrinsics'].cpu())
+    elif opt.optimize_pose:
         meta.update(yaw=res['yaw'], pitch=res['pitch'])
     checkpoint_path = os.path.join(opt.save_dir, f'freq_phase_offset_{opt.name}.pth')
     torch.save(meta, checkpoint_path)
     np.save(os.path.join(opt.save_dir, 'mious.npy'), mious)
     print(f"{os.path.basename(img_path)}: loss {res['losses'][0]:.5f} -> {res['losses'][-1]:.5f} in {opt.iteration} iterations"
           + (f", frontal mIoU {mious[0]:.3f} -> {mious[-1]:.3f}" if mious else "")
-          + (f", yaw {res['yaw']:.4f} pitch {res['pitch']:.4f}" if opt.optimize_pose else "")
+          + (f", yaw {res['yaw']:.4f} pitch {res['pitch']:.4f}" if opt.optimize_pose and opt.pose_model == 'angles' else "")
           + (f", depth term {res['depth_losses'][0]:.5f} -> {res['depth_losses'][-1]:.5f}" if res.get('depth_losses') else "")
           + f" -> {checkpoint_path}")
     return checkpoint_path

@@ -40,6 +40,12 @@ def build_parser():
                         help='bake each identity\'s density once into a RES^3 lattice and place every view\'s samples from it: one SIREN pass per '
                              'view at the resampled depths, view-dependent colour kept; approximates sample placement only, RES^3 x 4 bytes of '
                              'device memory (not in the reference; not with --baked, --labels_only or --geometry)')
+    parser.add_argument('--roll', type=float, default=None, metavar='DEG',
+                        help='roll every view by DEG degrees about its view axis (a free camera, fenerf_amd.camera; not in the reference)')
+    parser.add_argument('--radius', type=float, default=None, metavar='X',
+                        help='camera distance from the origin (the reference: 1; a free camera)')
+    parser.add_argument('--crop', type=int, nargs=4, default=None, metavar=('X0', 'Y0', 'W', 'H'),
+                        help='render only this window of every --image_size view (a free camera)')
     add_geometry_arguments(parser)
     return parser
 
@@ -52,7 +58,34 @@ def parse_options(argv=None):
         parser.error("--labels_only takes neither --baked nor --geometry")
     if opt.proposal is not None and (opt.baked is not None or opt.labels_only or opt.geometry):
         parser.error("--proposal places the samples of the exact colour render; it takes none of --baked, --labels_only, --geometry")
+    if uses_camera(opt) and (opt.baked is not None or opt.labels_only or opt.geometry or opt.proposal is not None):
+        parser.error("--roll / --radius / --crop render the exact colour views; they take none of --baked, --labels_only, --geometry, --proposal")
+    if opt.crop is not None:
+        x0, y0, w, h = opt.crop
+        if x0 < 0 or y0 < 0 or w < 1 or h < 1 or x0 + w > opt.image_size or y0 + h > opt.image_size:
+            parser.error(f"--crop {x0} {y0} {w} {h} is empty or lies outside the {opt.image_size} x {opt.image_size} image")
+    if opt.radius is not None and not opt.radius > 0:
+        parser.error("--radius must be positive")
     return opt
+
+
+def uses_camera(opt):
+    return opt.roll is not None or opt.radius is not None or opt.crop is not None
+
+
+FACE_ANGLES = (-0.5, -0.25, 0.0, 0.25, 0.5)
+
+
+def view_cameras(opt, curriculum, device):
+    """the five views of render_multiview as free cameras with the flags' roll, radius and window"""
+    import math
+    from fenerf_amd.camera import Camera
+    cams = []
+    for a in FACE_ANGLES:
+        cam = Camera.from_angles(a + curriculum['h_mean'], curriculum['v_mean'], curriculum['fov'], (opt.image_size, opt.image_size),
+                                 radius=1.0 if opt.radius is None else opt.radius, roll=math.radians(opt.roll or 0.0), device=device)
+        cams.append(cam if opt.crop is None else cam.crop(*opt.crop))
+    return cams
 
 
 def add_geometry_arguments(parser):
@@ -104,7 +137,8 @@ def main(argv=None):
         images, segmaps, *views = callers.render_multiview(generator, curriculum, int(seed), device, image_size=opt.image_size,
                                                            ray_step_multiplier=opt.ray_step_multiplier,
                                                            lock_view_dependence=opt.lock_view_dependence, baked=opt.baked,
-                                                           geometry=geometry_options(opt), proposal=opt.proposal)
+                                                           geometry=geometry_options(opt), proposal=opt.proposal,
+                                                           cameras=view_cameras(opt, curriculum, device) if uses_camera(opt) else None)
         imageio_lite.save_image(images, os.path.join(opt.output_dir, f'grid_{seed}_RGB.png'), normalize=True, value_range=(-1, 1))
         imageio_lite.save_image(segmaps, os.path.join(opt.output_dir, f'grid_{seed}_SEG.png'))
         if views:
